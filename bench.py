@@ -12,6 +12,11 @@ Launch: python bench.py [--gpus N --steps K --warmup W]; for N > 1 either under 
 process per GPU, WORLD_SIZE = N, RCCL communicator per process) or as one process driving N GPUs through one
 multi-device context (sail_create_multi: ncclCommInitAll + grouped reduce). Any other combination of --gpus and
 WORLD_SIZE exits non-zero. Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step, ...).
+--dump-outputs DIR also writes what the last timed step computed (dump_outputs). --full adds everything else the
+benchmark measures or checks, after the timed steps: the check of the frame against the CPU oracle, the roofline
+figures (the op-counting oracle run, the committed PMC summaries), the filter pass's figures and the CPU baselines.
 """
 from __future__ import annotations
 
@@ -234,6 +239,30 @@ def validate_frame(ctx, sc, masks, mvp, W, H, B, spp, inv, seeds, part, ngpu):
     return rep
 
 
+DUMP_BUDGET_BYTES = 64_000_000  # --dump-outputs: all files of one run together stay under this
+
+
+def dump_outputs(dirpath, arrays, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: writes each array of `arrays` (name -> what a caller of the timed path receives: (H, W, C)
+    float32 images) as dirpath/<name>.npy in float32. The budget is shared equally; an image larger than its share is
+    written as a sample instead: the rows (pixels) of its (H*W, C) view at the sorted indices
+    numpy.random.default_rng(0).choice(H*W, n, replace=False), the same pixels in every run of the same shape, so two
+    builds' files compare element for element. Returns {name: {"shape", "sampled_pixels", "of_pixels"}}."""
+    os.makedirs(dirpath, exist_ok=True)
+    share = budget // max(len(arrays), 1)
+    written = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        px = a.reshape(-1, a.shape[-1])
+        n = share // (px.shape[1] * 4)
+        sampled = px.shape[0] > n
+        if sampled:
+            a = px[np.sort(np.random.default_rng(0).choice(px.shape[0], n, replace=False))]
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+        written[name] = {"shape": list(a.shape), "sampled_pixels": int(n) if sampled else None, "of_pixels": int(px.shape[0])}
+    return written
+
+
 class _StdoutToStderr:
     """Points file descriptor 1 at stderr (C-level prints included) between __enter__ and __exit__."""
 
@@ -255,6 +284,63 @@ class _StdoutToStderr:
         return False
 
 
+def full_report(rec, args, ctx, cfg, sc, masks, mvp, flt, validation, tiles_px, launch_spp, avg_launch_s, ngpu, device):
+    """--full: adds to the result line what takes work beyond the timed steps: the roofline (the op-counting oracle
+    run, the committed PMC summary of this kernel build), the frame's validation, the filter pass's figures and the
+    CPU baselines."""
+    W, H, B = cfg["width"], cfg["height"], cfg["bounces"]
+    segs_per_launch = tiles_px * launch_spp * B
+    ops_seg, ops_live = ops_per_segment(sc, masks, mvp, W, H, B)
+    achieved_tflops = ops_seg * segs_per_launch / avg_launch_s / 1e12
+    achieved_live = ops_live * segs_per_launch / avg_launch_s / 1e12
+    hbm_gbs = (tiles_px * 32) / avg_launch_s / 1e9   # float4 accumulator read + write per pixel per launch
+    kinfo = ctx.kernel_info()
+    kernel_id = f"{kinfo['name']}@{kinfo['build_id']}"
+    traffic, traffic_src, pmc = profiled_traffic(cfg["workload"], tiles_px, launch_spp, B, kernel_id)
+    rec["roofline"] = {
+        # headline: the live-op model (ops some output reads: the last bounce's dead throughput update, next
+        # ray, BSDF sample and material weight left out), so skipped dead work is never credited
+        "bound": "valu", "achieved": round(achieved_live, 3), "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s",
+        "frac": round(achieved_live / FP32_PEAK_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_src,
+        "ops_per_segment_live": round(ops_live, 2),
+        "formula": "ops_per_segment_live x pixels x launch_spp x bounces / avg_launch_s / 157.3e12",
+        # the op model counts every add/mul/min/max/divide/transcendental as one op: its ceiling is one op
+        # per lane per cycle (the FP32 peak above counts an FMA as two), so this is the pipe's fraction
+        "frac_one_op_per_lane": round(achieved_live / (FP32_PEAK_TFLOPS / 2), 4),
+        # the full op model: every op of the reference program, dead last-bounce ops included
+        "ops_per_segment_full": round(ops_seg, 2), "achieved_full": round(achieved_tflops, 3),
+        "frac_full": round(achieved_tflops / FP32_PEAK_TFLOPS, 4),
+        "kernel": ctx.kernel_name(),
+        "kernel_id": kernel_id,
+        "jit": {"state": ["none", "pending", "ready", "failed"][kinfo["jit_state"]],
+                "code_object_from": ["hipRTC in this process", "user disk cache", "cache shipped with the library"][kinfo["jit_from_cache"]],
+                "compile_ms": round(kinfo["jit_compile_ms"], 1), **({"error": kinfo["jit_error"]} if kinfo["jit_error"] else {})},
+        "avg_launch_ms": round(avg_launch_s * 1e3, 4),
+        # one launch = the HIP events around the trace kernel and, with sample groups (a "_grouped" kernel),
+        # the sail_accum_kernel that adds the staged samples in order after it
+        "launch_span": "trace kernel + sail_accum_kernel" if ctx.kernel_name().endswith("_grouped") else "trace kernel",
+        "hbm": {"achieved": round(hbm_gbs, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(hbm_gbs / HBM_PEAK_GBS, 6), "bytes_per_launch": tiles_px * 32},
+        "valu_issue": valu_issue(pmc, device),
+    }
+    rec["validation"] = validation
+    if flt:
+        fms = ctx.filter_ms()
+        fbytes = W * H * (16 + 16)  # mean-image read once from HBM (taps hit L2) + float4 write
+        rec["filter"] = {"kind": flt["name"], "kernel": "sail_filter_kernel", "avg_ms": round(fms, 4),
+                         "bound": "hbm", "bytes_per_pass": fbytes, "achieved": round(fbytes / (fms * 1e-3) / 1e9, 1),
+                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(fbytes / (fms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
+    if not args.no_cpu_baseline and ngpu == 1:
+        # the north star's JS/Node software shader; the C++ restatement is timed beside it for reference
+        cpp = cpu_baseline(sc, masks, mvp, W, H, B, budget_s=5.0)
+        js = cpu_baseline_js(sc, masks, mvp, W, H, B)
+        nthr = max(1, min(16, os.cpu_count() or 1))  # the CPU share for one GPU is 16 cores
+        jsmt = cpu_baseline_js(sc, masks, mvp, W, H, B, budget_s=6.0, threads=nthr) if (js and nthr > 1) else None
+        rec["cpu_baseline"] = dict(js, cpp_port=cpp, worker_threads=jsmt) if js else cpp
+        if js and not args.no_c1_full:
+            rec["cpu_baseline"]["c1_full"] = cpu_baseline_c1_full()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -264,14 +350,21 @@ def main():
     ap.add_argument("--spp", type=int, default=None)
     ap.add_argument("--launch-spp", type=int, default=0,
                     help="samples per kernel launch (default 0: the library's choice by kernel form, sail_set_launch_samples)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-c1-full", action="store_true", help="skip the ~30 s full C1 render of the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also check the frame against the CPU oracle and report the roofline, the "
+                         "filter pass and the CPU baselines (a plain run prints the headline figures alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed as DIR/<name>.npy (float32; accum: the "
+                         "float4 accumulator, filtered: the reconstruction filter's image where the config has one)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-c1-full", action="store_true",
+                    help="with --full: skip the ~30 s full C1 render of the CPU baseline")
     ap.add_argument("--force-rccl", action="store_true",
                     help="one process: the multi-device context's RCCL reduce even at --gpus 1 (SAIL_DEBUG_FORCE_RCCL)")
     ap.add_argument("--wavefront", action="store_true",
                     help="study: the pre-cull path by the wavefront split instead of the megakernel (SAIL_DEBUG_WAVEFRONT)")
     ap.add_argument("--no-validate", action="store_true",
-                    help="skip the check of the reduced frame after the timed steps (counts + oracle crops)")
+                    help="with --full: skip the check of the reduced frame after the timed steps (counts + oracle crops)")
     ap.add_argument("--force-comm", action="store_true",
                     help="exercise the torch.distributed + RCCL reduce path even with one rank")
     ap.add_argument("--debug", action="append", default=[], metavar="OPTION=VALUE",
@@ -336,13 +429,15 @@ def main():
         dist.broadcast_object_list(uid, src=0)
         ctx.comm_init(uid[0], world, rank)
 
+    last = {}  # the last step's filtered image (--dump-outputs)
+
     def step():
         ctx.reset()
         ctx.render_schedule(inv, seeds, sc["eye"], B)
         if use_comm or multi:
             ctx.reduce(0)
         if flt and rank == 0:  # reconstruction filter of the reduced frame (window.glsl, gaussian r = 2)
-            ctx.filter(capi.FILTER_WINDOW, fweights, flt["radius"][0], flt["radius"][1], 2.2)
+            last["filtered"] = ctx.filter(capi.FILTER_WINDOW, fweights, flt["radius"][0], flt["radius"][1], 2.2)
 
     def barrier_sync():
         ctx.sync()
@@ -375,8 +470,10 @@ def main():
     total_segments = W * H * spp * B * args.steps  # nominal; closed scene: every path runs all bounces
     value = total_segments / elapsed / 1e6
     ngpu = args.gpus if multi else world
+    if rank == 0 and args.dump_outputs:  # what the last timed step left: the (reduced) accumulator, the filtered image
+        dump_outputs(args.dump_outputs, {"accum": ctx.read_accum(), **last})
     validation = None
-    if rank == 0 and not args.no_validate:  # after the timed region: the frame the steps produced is checked
+    if rank == 0 and args.full and not args.no_validate:  # after the timed region: the frame the steps produced is checked
         validation = validate_frame(ctx, sc, masks, mvp, W, H, B, spp, inv, seeds, part, ngpu)
     if rank == 0:
         avg_launch_s = (kernel_ms / max(launches, 1)) / 1e3
@@ -391,14 +488,6 @@ def main():
         # samples in launches of at most that many; stats count every device's launches)
         per_dev = launches / (args.gpus if multi else 1) / args.steps
         launch_spp = args.launch_spp or int(round(spp / per_dev))
-        segs_per_launch = tiles_px * launch_spp * B
-        ops_seg, ops_live = ops_per_segment(sc, masks, mvp, W, H, B)
-        achieved_tflops = ops_seg * segs_per_launch / avg_launch_s / 1e12
-        achieved_live = ops_live * segs_per_launch / avg_launch_s / 1e12
-        hbm_gbs = (tiles_px * 32) / avg_launch_s / 1e9   # float4 accumulator read + write per pixel per launch
-        kinfo = ctx.kernel_info()
-        kernel_id = f"{kinfo['name']}@{kinfo['build_id']}"
-        traffic, traffic_src, pmc = profiled_traffic(cfg["workload"], tiles_px, launch_spp, B, kernel_id)
         rec = {
             "metric": "Msamples/s (paths x bounces) at 1920x1080 Cornell box" if args.config == "C2"
                       else f"Msamples/s (paths x bounces), {cfg['workload']}",
@@ -418,50 +507,11 @@ def main():
                        "launch_spp": launch_spp, "partition": f"tiles64x{ngpu}",
                        "processes": "one per GPU" if world > 1 else ("one (multi-device context)" if multi else "one"), "segments_per_step": W * H * spp * B,
                        **({"debug": debug} if debug else {})},
-            "roofline": {
-                # headline: the live-op model (ops some output reads: the last bounce's dead throughput update, next
-                # ray, BSDF sample and material weight left out), so skipped dead work is never credited
-                "bound": "valu", "achieved": round(achieved_live, 3), "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s",
-                "frac": round(achieved_live / FP32_PEAK_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_src,
-                "ops_per_segment_live": round(ops_live, 2),
-                "formula": "ops_per_segment_live x pixels x launch_spp x bounces / avg_launch_s / 157.3e12",
-                # the op model counts every add/mul/min/max/divide/transcendental as one op: its ceiling is one op
-                # per lane per cycle (the FP32 peak above counts an FMA as two), so this is the pipe's fraction
-                "frac_one_op_per_lane": round(achieved_live / (FP32_PEAK_TFLOPS / 2), 4),
-                # the full op model: every op of the reference program, dead last-bounce ops included
-                "ops_per_segment_full": round(ops_seg, 2), "achieved_full": round(achieved_tflops, 3),
-                "frac_full": round(achieved_tflops / FP32_PEAK_TFLOPS, 4),
-                "kernel": ctx.kernel_name(),
-                "kernel_id": kernel_id,
-                "jit": {"state": ["none", "pending", "ready", "failed"][kinfo["jit_state"]],
-                        "code_object_from": ["hipRTC in this process", "user disk cache", "cache shipped with the library"][kinfo["jit_from_cache"]],
-                        "compile_ms": round(kinfo["jit_compile_ms"], 1), **({"error": kinfo["jit_error"]} if kinfo["jit_error"] else {})},
-                "avg_launch_ms": round(avg_launch_s * 1e3, 4),
-                # one launch = the HIP events around the trace kernel and, with sample groups (a "_grouped" kernel),
-                # the sail_accum_kernel that adds the staged samples in order after it
-                "launch_span": "trace kernel + sail_accum_kernel" if ctx.kernel_name().endswith("_grouped") else "trace kernel",
-                "hbm": {"achieved": round(hbm_gbs, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                        "frac": round(hbm_gbs / HBM_PEAK_GBS, 6), "bytes_per_launch": tiles_px * 32},
-                "valu_issue": valu_issue(pmc, local_rank),
-            },
         }
-        rec["validation"] = validation
         if flt:
-            fms = ctx.filter_ms()
-            fbytes = W * H * (16 + 16)  # mean-image read once from HBM (taps hit L2) + float4 write
-            rec["filter"] = {"kind": flt["name"], "kernel": "sail_filter_kernel", "avg_ms": round(fms, 4),
-                             "bound": "hbm", "bytes_per_pass": fbytes, "achieved": round(fbytes / (fms * 1e-3) / 1e9, 1),
-                             "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(fbytes / (fms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
             rec["config"]["partition"] = f"{cfg.get('partition', 'tiles')}x{ngpu}"
-        if not args.no_cpu_baseline and ngpu == 1:
-            # the north star's JS/Node software shader; the C++ restatement is timed beside it for reference
-            cpp = cpu_baseline(sc, masks, mvp, W, H, B, budget_s=5.0)
-            js = cpu_baseline_js(sc, masks, mvp, W, H, B)
-            nthr = max(1, min(16, os.cpu_count() or 1))  # the box's CPU share for one GPU is 16 cores
-            jsmt = cpu_baseline_js(sc, masks, mvp, W, H, B, budget_s=6.0, threads=nthr) if (js and nthr > 1) else None
-            rec["cpu_baseline"] = dict(js, cpp_port=cpp, worker_threads=jsmt) if js else cpp
-            if js and not args.no_c1_full:
-                rec["cpu_baseline"]["c1_full"] = cpu_baseline_c1_full()
+        if args.full:
+            full_report(rec, args, ctx, cfg, sc, masks, mvp, flt, validation, tiles_px, launch_spp, avg_launch_s, ngpu, local_rank)
         print(json.dumps(rec), flush=True)
     ctx.close()
     if dist is not None:

@@ -5,6 +5,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 ROOT=$(pwd)
 mkdir -p ${PMC_OUT:-gpurun_out/pmc}
 cd /tmp && export TMPDIR=/tmp
+PMC_BENCH_ARGS="--full ${PMC_BENCH_ARGS:-}"  # the summaries read roofline.kernel_id from the bench line
 run() {
   local name=$1; shift
   timeout -k 10 300 rocprofv3 --pmc "$@" -d $ROOT/${PMC_OUT:-gpurun_out/pmc}/$name -o run --output-format csv -- \

@@ -15,5 +15,5 @@ for cfg in ${PMC_CONFIGS:-C2 C3 C4}; do
       SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU
   fi
   timeout -k 10 300 rocprofv3 --pmc "$@" -d $ROOT/$OUT/$cfg -o run --output-format csv -- \
-    python3 $ROOT/bench.py --config $cfg --steps 1 --warmup 0 --spp 32 --no-cpu-baseline > $ROOT/$OUT/$cfg.log 2>&1 || exit 1
+    python3 $ROOT/bench.py --config $cfg --full --steps 1 --warmup 0 --spp 32 --no-cpu-baseline > $ROOT/$OUT/$cfg.log 2>&1 || exit 1
 done

@@ -5,6 +5,7 @@ ROOT=$(pwd)
 OUT=${PMC_OUT:-gpurun_out/pmc_mix}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
+PMC_BENCH_ARGS="--full ${PMC_BENCH_ARGS:-}"  # the summaries read roofline.kernel_id from the bench line
 run() {
   local name=$1; shift
   timeout -k 10 300 rocprofv3 --pmc "$@" -d $ROOT/$OUT/$name -o run --output-format csv -- \

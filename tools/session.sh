@@ -43,22 +43,22 @@ for step in "$@"; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { cat $OUT/smoke.log; exit 3; }
       cat $OUT/smoke.log ;;
     bench)
-      timeout -k 10 600 python bench.py > $OUT/bench.log 2> $OUT/bench.err || { tail $OUT/bench.err; exit 4; }
+      timeout -k 10 600 python bench.py --full > $OUT/bench.log 2> $OUT/bench.err || { tail $OUT/bench.err; exit 4; }
       cut -c1-400 $OUT/bench.log ;;
     bench_quick)
-      timeout -k 10 300 python bench.py --no-cpu-baseline > $OUT/bench_quick.log 2> $OUT/bench_quick.err || { tail $OUT/bench_quick.err; exit 4; }
+      timeout -k 10 300 python bench.py --full --no-cpu-baseline > $OUT/bench_quick.log 2> $OUT/bench_quick.err || { tail $OUT/bench_quick.err; exit 4; }
       cut -c1-400 $OUT/bench_quick.log ;;
     bench_rccl)
-      timeout -k 10 300 python bench.py --force-rccl --no-cpu-baseline > $OUT/bench_rccl.log 2> $OUT/bench_rccl.err || { tail $OUT/bench_rccl.err; exit 4; }
+      timeout -k 10 300 python bench.py --full --force-rccl --no-cpu-baseline > $OUT/bench_rccl.log 2> $OUT/bench_rccl.err || { tail $OUT/bench_rccl.err; exit 4; }
       cut -c1-300 $OUT/bench_rccl.log ;;
     bench_c3|bench_c4|bench_c5)
       cfg=$(echo ${step#bench_} | tr a-z A-Z)
-      timeout -k 10 400 python bench.py --config $cfg --steps 1 --warmup 1 --no-cpu-baseline > $OUT/$step.log 2> $OUT/$step.err || { tail $OUT/$step.err; exit 5; }
+      timeout -k 10 400 python bench.py --full --config $cfg --steps 1 --warmup 1 --no-cpu-baseline > $OUT/$step.log 2> $OUT/$step.err || { tail $OUT/$step.err; exit 5; }
       cut -c1-400 $OUT/$step.log ;;
-    prof_c2) prof prof_c2 --steps 3 --warmup 1 --no-cpu-baseline || exit 6 ;;
-    prof_c3) prof prof_c3 --config C3 --steps 1 --warmup 1 --no-cpu-baseline || exit 6 ;;
-    prof_c4) prof prof_c4 --config C4 --steps 1 --warmup 1 --spp 64 --no-cpu-baseline || exit 6 ;;
-    prof_c5) prof prof_c5 --config C5 --steps 1 --warmup 1 --no-cpu-baseline || exit 6 ;;
+    prof_c2) prof prof_c2 --full --steps 3 --warmup 1 --no-cpu-baseline || exit 6 ;;
+    prof_c3) prof prof_c3 --full --config C3 --steps 1 --warmup 1 --no-cpu-baseline || exit 6 ;;
+    prof_c4) prof prof_c4 --full --config C4 --steps 1 --warmup 1 --spp 64 --no-cpu-baseline || exit 6 ;;
+    prof_c5) prof prof_c5 --full --config C5 --steps 1 --warmup 1 --no-cpu-baseline || exit 6 ;;
     pmc_c2|pmc_c3|pmc_c4|pmc_c5)
       c=${step#pmc_}; cfg=$(echo $c | tr a-z A-Z)
       PMC_OUT=$OUT/$step PMC_CONFIG=$cfg PMC_SPP=${LS[$c]} bash tools/pmc.sh > /dev/null || exit 7  # one launch
@@ -81,7 +81,7 @@ for step in "$@"; do
       cat $OUT/phases.jsonl ;;
     torchrun)  # bench.py under torch.distributed.run at N = 1 (the launcher the driver uses for N > 1)
       timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 \
-        --master-port 29517 bench.py --gpus 1 --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_torchrun.log \
+        --master-port 29517 bench.py --full --gpus 1 --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_torchrun.log \
         2> $OUT/bench_torchrun.err || { tail $OUT/bench_torchrun.err; exit 13; }
       cut -c1-300 $OUT/bench_torchrun.log ;;
     jit_times)  # run-time kernel build latency per form, cold and warm (tools/jit_compile_times.py)
