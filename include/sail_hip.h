@@ -168,6 +168,48 @@ int sail_filter(sail_ctx* ctx, int kind, const float* weights16, float rx, float
                 float* out_rgba, uint8_t* out_rgba8);
 int sail_get_stats(sail_ctx* ctx, sail_stats* out);
 
+/* ---- device-side noise estimate and render-until-converged (no reference counterpart: the reference accumulates until
+ * the user stops looking; the half-buffer estimate of progressive tracers such as Cycles and pbrt-v4) ----
+ * The context keeps a snapshot P (the "mark") of the accumulator it shows, S (its own, or the reduced frame). An estimate
+ * compares the mean a of the samples before the mark with the mean b of those since, per pixel, in f32 and in this order:
+ *   n = S.w, h = P.w                       (SAIL_ACCUM_MIX: n, h = the sample index now and at the mark, as f32)
+ *   e = 0 unless h > 0 and n > h           (no samples, or none since the mark)
+ *   a = P / h, b = (S - P) / (n - h), m = S / n   per channel   (MIX: a = P, m = S, b = (n m - h a) / (n - h))
+ *   e = (0.5 ((|a.r-b.r| + |a.g-b.g|) + |a.b-b.b|)) / (1e-4 + sqrt(max((m.r + m.g) + m.b, 0) / 3))
+ * With equal halves 0.5 |a - b| is |m - a|, the error of the OLDER half's mean: a conservative estimate for the whole
+ * frame, whose mean has twice the samples. A non-finite e (a NaN or Inf in the accumulator) counts in `nonfinite` and
+ * adds nothing to any sum: one bad pixel does not keep a frame from converging. One pass over S and P on the device
+ * (sail_noise_kernel: a sum per 16x16 tile, no atomics, so equal data give equal bits); the host adds the tiles in double.
+ * sail_reset, sail_set_scene, sail_update_objects, sail_set_accum_mode and sail_set_partition drop the mark;
+ * sail_load_accum keeps it (a loaded checkpoint continues a render). SAIL_ACCUM_COMPAT8 is refused (SAIL_E_STATE): its
+ * 8-bit store makes the halves' difference meaningless. On a multi-device context both calls reduce first and work on
+ * device 0's frame, like sail_filter. */
+typedef struct sail_noise_info {
+  double mean, max_tile;       /* sum of the tiles' sums / (W H); largest tile sum / in-frame pixels of that tile */
+  uint64_t k, k_mark;          /* sample index now and at the mark */
+  uint64_t nonfinite;          /* pixels whose error is not finite */
+  int tiles_x, tiles_y;        /* 16x16 tiles */
+  double kernel_ms;            /* device time of the pass (HIP events) */
+} sail_noise_info;
+/* P = the shown accumulator, k_mark = k */
+int sail_noise_mark(sail_ctx* ctx);
+/* tile_err (may be NULL): tiles_x * tiles_y mean errors per tile, row 0 = bottom; pixel_err (may be NULL): W * H errors
+ * (0 where not finite); remark != 0 also sets the mark to the current accumulator in the same pass. SAIL_E_STATE without
+ * a mark or with no sample since it. */
+int sail_noise_estimate(sail_ctx* ctx, sail_noise_info* out, float* tile_err, float* pixel_err, int remark);
+/* host only: the next look of the doubling schedule. k < min_spp -> min_spp; else min(2k, max_spp); k >= max_spp -> k */
+int sail_plan_until(uint64_t k, uint64_t min_spp, uint64_t max_spp, uint64_t* next);
+typedef struct sail_until_step { uint64_t k; double mean, max_tile; } sail_until_step;
+/* Render the frozen schedule (sail_schedule) from the context's sample index on, looking at sail_plan_until's indices:
+ * mark at the first look (its step reports mean = max_tile = +inf: no estimate yet), estimate + remark at each later one,
+ * stop when mean <= target (*converged = 1) or k == max_spp (0). The frame equals sail_render_schedule over the same
+ * indices bit for bit. history (may be NULL) receives the first `capacity` looks, *looks (may be NULL) the number of looks
+ * made; *out is the last estimate (mean = max_tile = +inf when no look estimated). A context already at or past max_spp
+ * renders nothing. No scene, SAIL_ACCUM_COMPAT8 or a half-loaded checkpoint: SAIL_E_STATE before anything is rendered. max_spp is at most 2^31 - 1 (the schedule's index type). */
+int sail_render_until(sail_ctx* ctx, const double mvp_rowmajor[16], const float eye[3], int max_bounces, double target,
+                      uint64_t min_spp, uint64_t max_spp, sail_noise_info* out, int* converged,
+                      sail_until_step* history, int capacity, int* looks);
+
 /* ---- checkpoint / resume of a progressive render (no reference counterpart: the reference restarts its
  * accumulation on every camera or object change, src/core/renderer.js:57-60, src/scene/scene.js:65-68) ----
  * A context's accumulation is `parts` raw accumulators (1 for sail_create, one per device for sail_create_multi),

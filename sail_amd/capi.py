@@ -48,6 +48,7 @@ EXPORTS = (
     "sail_abi_version", "sail_accum_parts", "sail_save_accum", "sail_load_accum", "sail_jit_compile",
     "sail_get_kernel_info", "sail_kernel_ready", "sail_set_jit_cache", "sail_jit_prebuild",
     "sail_plan_reduce", "sail_plan_keep", "sail_plan_load_part",
+    "sail_noise_mark", "sail_noise_estimate", "sail_plan_until", "sail_render_until",
 )
 
 
@@ -75,6 +76,16 @@ class KernelInfo(ctypes.Structure):
 class ReducePlan(ctypes.Structure):
     _fields_ = [("receives", ctypes.c_int), ("tiles", ctypes.c_int), ("aov_owner", ctypes.c_int),
                 ("send_own_aovs", ctypes.c_int), ("samples", ctypes.c_uint64)]
+
+
+class NoiseInfo(ctypes.Structure):
+    _fields_ = [("mean", ctypes.c_double), ("max_tile", ctypes.c_double), ("k", ctypes.c_uint64), ("k_mark", ctypes.c_uint64),
+                ("nonfinite", ctypes.c_uint64), ("tiles_x", ctypes.c_int), ("tiles_y", ctypes.c_int),
+                ("kernel_ms", ctypes.c_double)]
+
+
+class UntilStep(ctypes.Structure):
+    _fields_ = [("k", ctypes.c_uint64), ("mean", ctypes.c_double), ("max_tile", ctypes.c_double)]
 
 
 _SHAPES = {"cube": 1, "sphere": 2, "rectangle": 3, "cone": 4, "cylinder": 5, "disk": 6,
@@ -162,6 +173,12 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
         "sail_plan_keep": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, f32p, f32p]),
         "sail_plan_load_part": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_int,
                                                ctypes.c_int, ctypes.c_uint64]),
+        "sail_noise_mark": (ctypes.c_int, [vp]),
+        "sail_noise_estimate": (ctypes.c_int, [vp, ctypes.POINTER(NoiseInfo), f32p, f32p, ctypes.c_int]),
+        "sail_plan_until": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+        "sail_render_until": (ctypes.c_int, [vp, f64p, f32p, ctypes.c_int, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint64,
+                                             ctypes.POINTER(NoiseInfo), ctypes.POINTER(ctypes.c_int),
+                                             ctypes.POINTER(UntilStep), ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -269,6 +286,25 @@ class LoadParts:
     @property
     def complete(self) -> bool:
         return self.missing.value == 0
+
+
+def plan_until(k: int, min_spp: int, max_spp: int) -> int:
+    """The next look of render_until's doubling schedule after k samples (sail_plan_until, host-only): min_spp first,
+    then 2k capped at max_spp; k itself once max_spp is reached."""
+    lib = load()
+    for v in (k, min_spp, max_spp):
+        if not 0 <= int(v) < 1 << 64:
+            raise SailError(f"plan_until: {v} is not an unsigned 64-bit count")
+    nxt = ctypes.c_uint64(0)
+    rc = lib.sail_plan_until(int(k), int(min_spp), int(max_spp), ctypes.byref(nxt))
+    if rc:
+        raise SailError(f"sail_plan_until: {rc}: {lib.sail_last_error(None).decode()}")
+    return int(nxt.value)
+
+
+def _noise_dict(n: NoiseInfo) -> dict:
+    return {"mean": n.mean, "max_tile": n.max_tile, "k": int(n.k), "k_mark": int(n.k_mark), "nonfinite": int(n.nonfinite),
+            "tiles_x": n.tiles_x, "tiles_y": n.tiles_y, "kernel_ms": n.kernel_ms}
 
 
 def prim_bounds(objects, n: int, tn: int) -> np.ndarray:
@@ -452,6 +488,47 @@ class Context:
         t = np.zeros(len(r), dtype=np.float32)
         self._check(self.lib.sail_pick(self.h, _ptr(r), len(r), _ptr(idx, ctypes.c_int32), _ptr(t)), "sail_pick")
         return idx, t
+
+    def noise_mark(self):
+        """Snapshot the shown accumulator as the noise estimate's mark (sail_noise_mark)."""
+        self._check(self.lib.sail_noise_mark(self.h), "sail_noise_mark")
+
+    def noise_estimate(self, tiles: bool = False, pixels: bool = False, remark: bool = False) -> dict:
+        """The frame's noise against the mark (sail_noise_estimate): mean, max_tile, k, k_mark, nonfinite, tiles_x,
+        tiles_y, kernel_ms; with `tiles` the (tiles_y, tiles_x) mean error per 16x16 tile as "tile_err", with `pixels` the
+        (H, W) map as "pixel_err". remark: the mark becomes the current accumulator in the same pass."""
+        n = NoiseInfo()
+        tx, ty = (self.W + 15) // 16, (self.H + 15) // 16
+        t = np.zeros((ty, tx), dtype=np.float32) if tiles else None
+        p = np.zeros((self.H, self.W), dtype=np.float32) if pixels else None
+        self._check(self.lib.sail_noise_estimate(self.h, ctypes.byref(n), _ptr(t), _ptr(p), int(bool(remark))),
+                    "sail_noise_estimate")
+        out = _noise_dict(n)
+        if tiles:
+            out["tile_err"] = t
+        if pixels:
+            out["pixel_err"] = p
+        return out
+
+    def render_until(self, mvp, eye, max_bounces: int, target: float, min_spp: int = 16, max_spp: int = 65536) -> dict:
+        """Render the frozen schedule from the context's sample index until the noise estimate's mean is <= target or
+        max_spp samples are in (sail_render_until). Returns the last estimate's fields plus "converged" and "history",
+        a list of {k, mean, max_tile} per look (the first look only marks: its mean is inf)."""
+        m = np.ascontiguousarray(np.asarray(mvp, dtype=np.float64).reshape(16))
+        e = _f32(eye)
+        for v in (min_spp, max_spp):
+            if not 0 <= int(v) < 1 << 64:
+                raise SailError(f"render_until: {v} is not an unsigned 64-bit count")
+        n, conv, looks = NoiseInfo(), ctypes.c_int(0), ctypes.c_int(0)
+        cap = 64  # looks double k: more cannot happen below 2^31 samples
+        hist = (UntilStep * cap)()
+        self._check(self.lib.sail_render_until(self.h, _ptr(m, ctypes.c_double), _ptr(e), int(max_bounces), float(target),
+                                               int(min_spp), int(max_spp), ctypes.byref(n), ctypes.byref(conv), hist, cap,
+                                               ctypes.byref(looks)), "sail_render_until")
+        out = _noise_dict(n)
+        out["converged"] = bool(conv.value)
+        out["history"] = [{"k": int(s.k), "mean": s.mean, "max_tile": s.max_tile} for s in hist[:min(looks.value, cap)]]
+        return out
 
     def filter_ms(self) -> float:
         v = ctypes.c_double()

@@ -26,6 +26,9 @@ hipError_t sail_launch_negzero_unowned(float4* a, float4* b, int W, int H, int r
 hipError_t sail_launch_wavefront(const SailTraceArgs& A, const SailWfState& S, hipStream_t s);
 hipError_t sail_launch_pick(const SailPrim* prims, int n, const float* rays, int count, int32_t* index, float* t,
                             hipStream_t s);
+// sail_noise.hip: the noise estimate's per-tile pass
+#include "sail_noise.h"
+hipError_t sail_launch_noise(const SailNoiseArgs& A, hipStream_t s);
 
 namespace {
 
@@ -179,6 +182,14 @@ struct sail_ctx {
   double kernelMs = 0.0, lastLaunchMs = 0.0;
   double lastFilterMs = 0.0;  // device time of the last display-filter pass
   uint32_t launches = 0;
+  // Noise estimate (sail_noise_mark / sail_noise_estimate): the mark, a snapshot of the shown accumulator at sample index
+  // noiseK, allocated on first mark; resetAccum drops it (sail_load_accum keeps it). On a multi-device context device
+  // 0's sub-context holds it (the reduced frame lives there). noiseOut: per tile a float sum then a uint32 count.
+  float4* noiseMark = nullptr;
+  bool noiseHave = false;
+  uint64_t noiseK = 0;
+  float* noiseOut = nullptr;
+  float* noisePix = nullptr;  // the optional per-pixel map, allocated on first use
   nccl_comm_t comm = nullptr;
   int commRanks = 0, commRank = 0;
   // Reduced frame (root of sail_reduce / device 0 of a multi-device context): the sum of every rank's
@@ -434,6 +445,7 @@ void cornerDirs(const float* M, const float* eye, float out[4][3]) {
 int resetAccum(sail_ctx* c) {
   c->reduced = false;
   c->queued.clear();  // queued one-sample frames belong to the accumulation being discarded
+  c->noiseHave = false;  // so does the noise estimate's mark (sail_load_accum puts it back: it continues a render)
   const size_t bytes = (size_t)c->W * c->H * sizeof(float4);
   HIPCHK(c, hipMemsetAsync(c->accum, 0, bytes, c->stream));
   if (c->aovN) HIPCHK(c, hipMemsetAsync(c->aovN, 0, bytes, c->stream));
@@ -1185,7 +1197,8 @@ void sail_destroy(sail_ctx* c) {
   if (c->comm && g_rccl.commDestroy) g_rccl.commDestroy(c->comm);
   for (auto& pr : c->pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
   for (auto e : c->evPool) (void)hipEventDestroy(e);
-  void* bufs[] = {c->accum, c->frame, c->frameN, c->frameP, c->aovN, c->aovP, c->filterOut, c->filterOut8, c->stage, c->segCounter, c->prims, c->tp, c->lt, c->lightObjRow, c->samples, c->wf};
+  void* bufs[] = {c->accum, c->frame, c->frameN, c->frameP, c->aovN, c->aovP, c->filterOut, c->filterOut8, c->stage, c->segCounter, c->prims, c->tp, c->lt, c->lightObjRow, c->samples, c->wf,
+                  c->noiseMark, c->noiseOut, c->noisePix};
   for (void* b : bufs) if (b) (void)hipFree(b);
   if (c->samplesPinned) (void)hipHostFree(c->samplesPinned);
   if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1705,6 +1718,170 @@ int sail_get_stats(sail_ctx* c, sail_stats* s) {
   return SAIL_OK;
 }
 
+// ---- noise estimate and render-until-converged (include/sail_hip.h; the kernel is sail_noise.hip) -------------------------
+int sail_noise_mark(sail_ctx* c) {
+  if (!c) return SAIL_E_INVALID;
+  if (!c->subs.empty()) {  // device 0's reduced frame, like sail_filter
+    if (int rc = loadIncomplete(c, "sail_noise_mark")) return rc;
+    if (int rc = groupReduce(c)) return rc;
+    return relay(c, sail_noise_mark(c->subs[0]), c->subs[0]);
+  }
+  if (c->accumMode == SAIL_ACCUM_COMPAT8)
+    return fail(c, SAIL_E_STATE, "sail_noise_mark: SAIL_ACCUM_COMPAT8 stores 8-bit frames, whose halves cannot be compared");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = sail_sync(c)) return rc;
+  const size_t bytes = (size_t)c->W * c->H * sizeof(float4);
+  if (!c->noiseMark && hipMalloc(&c->noiseMark, bytes) != hipSuccess) {
+    c->noiseMark = nullptr;
+    return fail(c, SAIL_E_OOM, "noise mark");
+  }
+  HIPCHK(c, hipMemcpyAsync(c->noiseMark, shownAccum(c), bytes, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->noiseHave = true;
+  c->noiseK = c->k;
+  return SAIL_OK;
+}
+
+int sail_noise_estimate(sail_ctx* c, sail_noise_info* out, float* tile_err, float* pixel_err, int remark) {
+  if (!c || !out) return SAIL_E_INVALID;
+  if (!c->subs.empty()) {
+    if (int rc = loadIncomplete(c, "sail_noise_estimate")) return rc;
+    if (int rc = groupReduce(c)) return rc;
+    return relay(c, sail_noise_estimate(c->subs[0], out, tile_err, pixel_err, remark), c->subs[0]);
+  }
+  if (c->accumMode == SAIL_ACCUM_COMPAT8)
+    return fail(c, SAIL_E_STATE, "sail_noise_estimate: SAIL_ACCUM_COMPAT8 stores 8-bit frames, whose halves cannot be compared");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = sail_sync(c)) return rc;
+  if (!c->noiseHave || !c->noiseMark)
+    return fail(c, SAIL_E_STATE, "sail_noise_estimate: no mark (sail_noise_mark first; a reset or a new scene drops it)");
+  if (c->k <= c->noiseK)
+    return fail(c, SAIL_E_STATE, "sail_noise_estimate: no sample since the mark (k = %llu, marked at %llu)",
+                (unsigned long long)c->k, (unsigned long long)c->noiseK);
+  const int tx = (c->W + 15) / 16, ty = (c->H + 15) / 16;
+  const size_t nt = (size_t)tx * ty, np = (size_t)c->W * c->H;
+  if (!c->noiseOut && hipMalloc(&c->noiseOut, nt * 8) != hipSuccess) {
+    c->noiseOut = nullptr;
+    return fail(c, SAIL_E_OOM, "noise tiles");
+  }
+  if (pixel_err && !c->noisePix && hipMalloc(&c->noisePix, np * sizeof(float)) != hipSuccess) {
+    c->noisePix = nullptr;
+    return fail(c, SAIL_E_OOM, "noise map");
+  }
+  SailNoiseArgs A;
+  memset(&A, 0, sizeof A);
+  A.S = shownAccum(c); A.P = c->noiseMark;
+  A.tileSum = c->noiseOut; A.tileBad = (uint32_t*)(c->noiseOut + nt);
+  A.pixErr = pixel_err ? c->noisePix : nullptr;
+  A.W = c->W; A.H = c->H;
+  A.mix = c->accumMode == SAIL_ACCUM_MIX;
+  A.kf = (float)c->k; A.hf = (float)c->noiseK;
+  A.remark = remark != 0;
+  std::vector<float> host(nt * 2);
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (int rc = getEvent(c, &e0)) return rc;
+  if (int rc = getEvent(c, &e1)) { c->evPool.push_back(e0); return rc; }
+  float ms = 0.0f;
+  hipError_t e = hipEventRecord(e0, c->stream);
+  if (e == hipSuccess) e = sail_launch_noise(A, c->stream);
+  if (e == hipSuccess) e = hipEventRecord(e1, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+  c->evPool.push_back(e0);
+  c->evPool.push_back(e1);
+  if (e == hipSuccess) e = hipMemcpy(host.data(), c->noiseOut, nt * 8, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && pixel_err) e = hipMemcpy(pixel_err, c->noisePix, np * sizeof(float), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(c, SAIL_E_HIP, "sail_noise_estimate: %s", hipGetErrorString(e));
+  // the tiles in index order, in double
+  const uint32_t* bad = (const uint32_t*)(host.data() + nt);
+  double sum = 0.0, maxTile = 0.0;
+  uint64_t nonfinite = 0;
+  for (int j = 0; j < ty; j++)
+    for (int i = 0; i < tx; i++) {
+      const size_t t = (size_t)j * tx + i;
+      const int w = c->W - i * 16 < 16 ? c->W - i * 16 : 16, h = c->H - j * 16 < 16 ? c->H - j * 16 : 16;
+      const double tileMean = (double)host[t] / (double)(w * h);
+      sum += (double)host[t];
+      if (tileMean > maxTile) maxTile = tileMean;
+      nonfinite += bad[t];
+      if (tile_err) tile_err[t] = (float)tileMean;
+    }
+  memset(out, 0, sizeof *out);
+  out->mean = sum / (double)np;
+  out->max_tile = maxTile;
+  out->k = c->k;
+  out->k_mark = c->noiseK;
+  out->nonfinite = nonfinite;
+  out->tiles_x = tx; out->tiles_y = ty;
+  out->kernel_ms = ms;
+  if (remark) c->noiseK = c->k;  // the kernel stored S into the mark
+  return SAIL_OK;
+}
+
+int sail_plan_until(uint64_t k, uint64_t min_spp, uint64_t max_spp, uint64_t* next) {
+  if (!next || min_spp < 1 || max_spp < min_spp)
+    return fail(nullptr, SAIL_E_INVALID, "sail_plan_until: need 1 <= min_spp <= max_spp (min %llu, max %llu)",
+                (unsigned long long)min_spp, (unsigned long long)max_spp);
+  if (k < min_spp) *next = min_spp;
+  else if (k >= max_spp) *next = k;
+  else *next = k > max_spp / 2 ? max_spp : (2 * k < max_spp ? 2 * k : max_spp);
+  return SAIL_OK;
+}
+
+int sail_render_until(sail_ctx* c, const double mvp[16], const float eye[3], int maxBounces, double target,
+                      uint64_t min_spp, uint64_t max_spp, sail_noise_info* out, int* converged, sail_until_step* history,
+                      int capacity, int* looks) {
+  if (!c) return SAIL_E_INVALID;
+  // the frozen schedule indexes samples with an int (sail_schedule)
+  if (!mvp || !eye || !out || min_spp < 1 || max_spp < min_spp || max_spp > 2147483647ull || target != target || capacity < 0)
+    return fail(c, SAIL_E_INVALID, "sail_render_until: bad arguments (min_spp %llu, max_spp %llu, target %g)",
+                (unsigned long long)min_spp, (unsigned long long)max_spp, target);
+  // what the looks would refuse is refused before anything is rendered
+  if (c->accumMode == SAIL_ACCUM_COMPAT8)
+    return fail(c, SAIL_E_STATE, "sail_render_until: SAIL_ACCUM_COMPAT8 stores 8-bit frames, whose halves cannot be compared");
+  if (!c->haveScene) return fail(c, SAIL_E_STATE, "sail_render_until before sail_set_scene");
+  if (int rc = loadIncomplete(c, "sail_render_until")) return rc;
+  uint64_t k = c->subs.empty() ? c->k : c->subs[0]->k;
+  memset(out, 0, sizeof *out);
+  out->mean = out->max_tile = INFINITY;  // until the first estimate
+  out->k = out->k_mark = k;
+  out->tiles_x = (c->W + 15) / 16; out->tiles_y = (c->H + 15) / 16;
+  int nlooks = 0, conv = 0;
+  bool marked = false;
+  constexpr uint64_t kChunk = 4096;  // samples whose matrices are built at a time (launches split anywhere bit for bit)
+  std::vector<float> inv, seeds;
+  for (;;) {
+    uint64_t next = k;
+    if (int rc = sail_plan_until(k, min_spp, max_spp, &next)) return fail(c, rc, "sail_render_until: %s", sail_last_error(nullptr));
+    if (next == k) break;  // at max_spp
+    while (k < next) {
+      const int spp = (int)(next - k < kChunk ? next - k : kChunk);
+      inv.resize((size_t)spp * 16);
+      seeds.resize((size_t)spp);
+      if (int rc = sail_schedule(mvp, c->W, c->H, (int)k, spp, inv.data(), seeds.data()))
+        return fail(c, rc, "sail_render_until: sail_schedule failed (a singular camera matrix?)");
+      if (int rc = sail_render_schedule(c, inv.data(), seeds.data(), eye, spp, maxBounces)) return rc;
+      k += (uint64_t)spp;
+    }
+    sail_until_step step{k, INFINITY, INFINITY};
+    if (!marked) {  // the first look only marks: no estimate yet
+      if (int rc = sail_noise_mark(c)) return rc;
+      marked = true;
+      out->k = out->k_mark = k;
+    } else {
+      if (int rc = sail_noise_estimate(c, out, nullptr, nullptr, 1)) return rc;
+      step.mean = out->mean; step.max_tile = out->max_tile;
+      conv = out->mean <= target;
+    }
+    if (history && nlooks < capacity) history[nlooks] = step;
+    nlooks++;
+    if (conv) break;
+  }
+  if (converged) *converged = conv;
+  if (looks) *looks = nlooks;
+  return SAIL_OK;
+}
+
 int sail_accum_device_ptr(sail_ctx* c, void** ptr, size_t* bytes) {
   if (!c || !ptr || !bytes) return SAIL_E_INVALID;
   if (!c->subs.empty()) return relay(c, sail_accum_device_ptr(c->subs[0], ptr, bytes), c->subs[0]);
@@ -1826,7 +2003,9 @@ int sail_load_accum(sail_ctx* c, int part, const float* sums, uint64_t k) {
   if (part == -1 && c->world > 1 && c->partMode == SAIL_PART_SAMPLES && c->accumMode != SAIL_ACCUM_SUM)
     return fail(c, SAIL_E_INVALID, "sail_load_accum: a running mean cannot be split by samples");
   HIPCHK(c, hipSetDevice(c->device));
+  const bool marked = c->noiseHave;
   if (int rc = resetAccum(c)) return rc;  // queued samples, stats and AOVs restart; the accumulator is replaced
+  c->noiseHave = marked;  // a loaded checkpoint continues a render: the noise estimate's mark stays
   std::vector<float> mine;
   const float* src = sums;
   if (part == -1 && c->world > 1) {

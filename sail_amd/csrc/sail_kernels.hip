@@ -1,0 +1,7 @@
+// sail_kernels.hip — the library's precompiled device code as ONE translation unit, so libsail_hip.so carries one
+// gfx950 code object (tests/test_jit_compile.py disassembles "the" code object of the library). Each kernel file stays
+// its own source and compiles on its own too (the study and variant builds under tools/ do that); sail_trace.hip is not
+// touched by what is added here: its text is embedded in the library and hashed into every run-time kernel's cache key.
+// sail_noise.hip comes first: it defines no macro, so the trace kernels compile exactly as they do alone.
+#include "sail_noise.hip"
+#include "sail_trace.hip"

@@ -4,9 +4,12 @@
 // assigns `scene`, then Renderer.update(scene)), render N samples on the GPU and write the frame to disk.
 //
 //   node sail_amd/js/cli.js scene.js [--width 512] [--height 512] [--spp 64] [--bounces 5] [--device -1]
+//        [--noise X [--min-spp 16] [--max-spp 65536]]
 //        [--filter <name>] [--filter-r 'vec2(2.0,2.0)'] [--gamma 2.2] [--deterministic]
 //        [--png out.png] [--pfm out.pfm] [--exr out.exr] [--stats]
 //
+// --noise X (instead of --spp) renders until the frame's noise estimate is at most X: it looks at --min-spp samples and at
+// every doubling, up to --max-spp. --stats then also prints the spp reached, the noise and whether it converged.
 // The script sees `Sail` (the full API) and must assign `scene` (a Sail.Scene with a camera), exactly as the
 // editor text does. --filter overrides scene.filter for the PNG; the PFM and EXR are always the unfiltered mean image.
 const fs = require('fs');
@@ -16,7 +19,7 @@ const Sail = require('./index');
 const { writePFM, writePNG, writeEXR } = require('./src/image');
 
 function parse(argv) {
-  const opt = { width: 512, height: 512, spp: 64, bounces: 5, device: -1, deterministic: false, stats: false };
+  const opt = { width: 512, height: 512, spp: 64, minSpp: 16, maxSpp: 65536, bounces: 5, device: -1, deterministic: false, stats: false };
   const rest = [];
   for (let i = 0; i < argv.length; i++) {
     const a = argv[i];
@@ -24,7 +27,10 @@ function parse(argv) {
     switch (a) {
       case '--width': opt.width = parseInt(val(), 10); break;
       case '--height': opt.height = parseInt(val(), 10); break;
-      case '--spp': opt.spp = parseInt(val(), 10); break;
+      case '--spp': opt.spp = parseInt(val(), 10); opt.sppGiven = true; break;
+      case '--noise': opt.noise = parseFloat(val()); break;
+      case '--min-spp': opt.minSpp = parseInt(val(), 10); opt.untilGiven = a; break;
+      case '--max-spp': opt.maxSpp = parseInt(val(), 10); opt.untilGiven = a; break;
       case '--bounces': opt.bounces = parseInt(val(), 10); break;
       case '--device': opt.device = parseInt(val(), 10); break;
       case '--filter': opt.filter = val(); break;
@@ -41,6 +47,9 @@ function parse(argv) {
         rest.push(a);
     }
   }
+  if (opt.noise !== undefined && opt.sppGiven) throw new Error('--noise and --spp exclude each other');
+  if (opt.noise !== undefined && Number.isNaN(opt.noise)) throw new Error('--noise needs a number');
+  if (opt.noise === undefined && opt.untilGiven) throw new Error(`${opt.untilGiven} needs --noise`);
   opt.script = rest[0];
   return opt;
 }
@@ -57,7 +66,7 @@ function loadScene(file) {
 function main() {
   const opt = parse(process.argv.slice(2));
   if (opt.help || !opt.script) {
-    process.stdout.write(fs.readFileSync(__filename, 'utf8').split('\n').slice(2, 11).map((l) => l.replace(/^\/\/ ?/, '')).join('\n') + '\n');
+    process.stdout.write(fs.readFileSync(__filename, 'utf8').split('\n').slice(2, 14).map((l) => l.replace(/^\/\/ ?/, '')).join('\n') + '\n');
     return opt.help ? 0 : 2;
   }
   const scene = loadScene(opt.script);
@@ -69,7 +78,9 @@ function main() {
     deterministic: opt.deterministic, accumulation: 'sum', aov: needAov, display: false });
   r.update(scene);
   const t0 = process.hrtime.bigint();
-  r.renderSamples(scene, opt.spp);
+  let until = null;
+  if (opt.noise !== undefined) until = r.renderUntil(scene, { noise: opt.noise, minSpp: opt.minSpp, maxSpp: opt.maxSpp });
+  else r.renderSamples(scene, opt.spp);
   const mean = r.readPixels();
   const ms = Number(process.hrtime.bigint() - t0) / 1e6;
   if (opt.pfm) writePFM(opt.pfm, opt.width, opt.height, mean);
@@ -77,8 +88,11 @@ function main() {
   if (opt.png) writePNG(opt.png, opt.width, opt.height, r.image());
   if (opt.stats) {
     const st = r.stats();
-    process.stdout.write(JSON.stringify({ width: opt.width, height: opt.height, spp: opt.spp, bounces: opt.bounces,
-      ms, segments: st.segments, kernelMs: st.kernelMs, filter: scene.filter.name }) + '\n');
+    const out = { width: opt.width, height: opt.height, spp: until ? until.k : opt.spp, bounces: opt.bounces,
+      ms, segments: st.segments, kernelMs: st.kernelMs, filter: scene.filter.name };
+    // (a frame that never reached a second look has no estimate: its noise is infinite, null in JSON)
+    if (until) Object.assign(out, { noise: until.mean, converged: until.converged });
+    process.stdout.write(JSON.stringify(out) + '\n');
   }
   r.destroy();
   return 0;

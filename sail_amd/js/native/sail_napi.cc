@@ -385,6 +385,81 @@ napi_value Stats(napi_env env, napi_callback_info info) {
   napi_set_named_property(env, out, "launches", num(env, s.launches));
   return out;
 }
+// noise estimate (sail_noise_mark, sail_noise_estimate, sail_render_until)
+napi_value NoiseMark(napi_env env, napi_callback_info info) { return Simple(env, info, sail_noise_mark, "sail_noise_mark"); }
+napi_value noiseObject(napi_env env, const sail_noise_info& n) {
+  napi_value out;
+  NAPI_OK(napi_create_object(env, &out));
+  napi_set_named_property(env, out, "mean", num(env, n.mean));
+  napi_set_named_property(env, out, "maxTile", num(env, n.max_tile));
+  napi_set_named_property(env, out, "k", num(env, (double)n.k));
+  napi_set_named_property(env, out, "kMark", num(env, (double)n.k_mark));
+  napi_set_named_property(env, out, "nonfinite", num(env, (double)n.nonfinite));
+  napi_set_named_property(env, out, "tilesX", num(env, n.tiles_x));
+  napi_set_named_property(env, out, "tilesY", num(env, n.tiles_y));
+  napi_set_named_property(env, out, "kernelMs", num(env, n.kernel_ms));
+  return out;
+}
+napi_value Noise(napi_env env, napi_callback_info info) {  // (ctx, remark, wantTiles) -> {mean, maxTile, ..., tileErr?}
+  napi_value a[3];
+  if (!args(env, info, 3, a)) return nullptr;
+  Handle* h;
+  if (!getHandle(env, a[0], &h)) return nullptr;
+  bool remark = false, tiles = false;
+  napi_get_value_bool(env, a[1], &remark);
+  napi_get_value_bool(env, a[2], &tiles);
+  void* pt = nullptr;
+  napi_value tileErr = nullptr;
+  if (tiles) tileErr = makeTyped(env, napi_float32_array, (size_t)((h->W + 15) / 16) * (size_t)((h->H + 15) / 16), 4, &pt);
+  sail_noise_info n;
+  const int rc = sail_noise_estimate(h->ctx, &n, (float*)pt, nullptr, remark ? 1 : 0);
+  if (rc) return throwSail(env, "sail_noise_estimate", rc, h->ctx);
+  napi_value out = noiseObject(env, n);
+  if (out && tiles) NAPI_OK(napi_set_named_property(env, out, "tileErr", tileErr));
+  return out;
+}
+// (ctx, mvp f64[16] row-major, eye f32[3], bounces, target, minSpp, maxSpp) -> {k, mean, maxTile, converged, history}
+napi_value RenderUntil(napi_env env, napi_callback_info info) {
+  napi_value a[7];
+  if (!args(env, info, 7, a)) return nullptr;
+  Handle* h;
+  double* m;
+  float* eye;
+  size_t nm, ne;
+  int b;
+  double target, mn, mx;
+  if (!getHandle(env, a[0], &h) || !getArray(env, a[1], napi_float64_array, &m, &nm) ||
+      !getArray(env, a[2], napi_float32_array, &eye, &ne) || !getInt(env, a[3], &b) || !getDouble(env, a[4], &target) ||
+      !getDouble(env, a[5], &mn) || !getDouble(env, a[6], &mx))
+    return nullptr;
+  if (nm < 16 || ne < 3) { napi_throw_range_error(env, nullptr, "mvp needs 16 doubles and eye 3 floats"); return nullptr; }
+  if (!(mn >= 0.0 && mn <= 2147483647.0 && mx >= 0.0 && mx <= 2147483647.0) || mn != (double)(uint64_t)mn || mx != (double)(uint64_t)mx) {
+    napi_throw_range_error(env, nullptr, "minSpp and maxSpp must be non-negative integers below 2^31");
+    return nullptr;
+  }
+  sail_noise_info n;
+  sail_until_step hist[64];
+  int conv = 0, looks = 0;
+  const int rc = sail_render_until(h->ctx, m, eye, b, target, (uint64_t)mn, (uint64_t)mx, &n, &conv, hist, 64, &looks);
+  if (rc) return throwSail(env, "sail_render_until", rc, h->ctx);
+  napi_value out = noiseObject(env, n);
+  if (!out) return nullptr;
+  napi_value cv, list;
+  NAPI_OK(napi_get_boolean(env, conv != 0, &cv));
+  NAPI_OK(napi_set_named_property(env, out, "converged", cv));
+  const int nl = looks < 64 ? looks : 64;
+  NAPI_OK(napi_create_array_with_length(env, (size_t)nl, &list));
+  for (int i = 0; i < nl; i++) {
+    napi_value s;
+    NAPI_OK(napi_create_object(env, &s));
+    napi_set_named_property(env, s, "k", num(env, (double)hist[i].k));
+    napi_set_named_property(env, s, "mean", num(env, hist[i].mean));
+    napi_set_named_property(env, s, "maxTile", num(env, hist[i].max_tile));
+    napi_set_element(env, list, (uint32_t)i, s);
+  }
+  NAPI_OK(napi_set_named_property(env, out, "history", list));
+  return out;
+}
 // (ctx, timeoutMs) -> whether the scene's run-time kernel is loaded (sail_kernel_ready; -1 waits for its build)
 napi_value KernelReady(napi_env env, napi_callback_info info) {
   napi_value a[2];
@@ -539,6 +614,9 @@ napi_value Init(napi_env env, napi_value exports) {
       {"loadAccum", 0, LoadAccum, 0, 0, 0, napi_enumerable, 0},
       {"filter", 0, Filter, 0, 0, 0, napi_enumerable, 0},
       {"stats", 0, Stats, 0, 0, 0, napi_enumerable, 0},
+      {"noiseMark", 0, NoiseMark, 0, 0, 0, napi_enumerable, 0},
+      {"noise", 0, Noise, 0, 0, 0, napi_enumerable, 0},
+      {"renderUntil", 0, RenderUntil, 0, 0, 0, napi_enumerable, 0},
       {"kernelReady", 0, KernelReady, 0, 0, 0, napi_enumerable, 0},
       {"kernelInfo", 0, KernelInfo, 0, 0, 0, napi_enumerable, 0},
       {"pick", 0, Pick, 0, 0, 0, napi_enumerable, 0},

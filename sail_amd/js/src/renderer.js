@@ -9,7 +9,9 @@
 //                                    jittered inverse camera matrix and a time seed -> sail_render, then the
 //                                    display filter (renderer.js:63) -> sail_filter, painted to the canvas
 // Extensions (same API object): renderSamples(scene, spp) runs a whole deterministic sample schedule in
-// one call; readPixels() / readAOV() / image() read the float frame back (the reference never reads back).
+// one call; readPixels() / readAOV() / image() read the float frame back (the reference never reads back);
+// renderUntil(scene, {noise, minSpp, maxSpp}) renders until the device-side noise estimate is at most `noise`
+// (noiseMark() / noise() are its two halves: sail_noise_mark / sail_noise_estimate).
 const native = require('./native');
 const { filterConfig } = require('./filter');
 
@@ -114,6 +116,32 @@ class Renderer {
     scene.sampleCount += spp;
     if (this.display) this.present();
   }
+
+  // Render the deterministic schedule until the frame's noise estimate is at most `noise` or maxSpp samples are in
+  // (sail_render_until: looks at minSpp, then at every doubling). Moving scenes and a zero sampleCount restart the
+  // frame as in renderSamples. Returns {k, mean, maxTile, converged, history: [{k, mean, maxTile}]}.
+  renderUntil(scene, { noise, minSpp = 16, maxSpp = 65536 } = {}) {
+    if (typeof noise !== 'number' || Number.isNaN(noise)) throw new Error('Renderer.renderUntil: noise (the target) must be a number');
+    if (scene.moving) { scene.sampleCount = 0; this.updateObjects(scene); }
+    if (scene.sampleCount === 0) this.lib.reset(this.ctx);
+    let r;
+    try {
+      r = this.lib.renderUntil(this.ctx, this._mvp(scene), Float32Array.from(scene.eye.elements), this.maxBounces,
+        noise, minSpp, maxSpp);
+    } catch (e) {
+      // looks rendered before the failure stay in the frame: keep the scene's count at the context's, so that the next
+      // render continues the schedule instead of drawing the same sample indices again
+      try { scene.sampleCount = this.lib.stats(this.ctx).samples; } catch (e2) { /* the first error is the one to report */ }
+      throw e;
+    }
+    scene.sampleCount = r.k;
+    if (this.display) this.present();
+    return { k: r.k, mean: r.mean, maxTile: r.maxTile, converged: r.converged, history: r.history };
+  }
+  // the noise estimate by hand: noiseMark() snapshots the frame, noise() compares the frame with the snapshot
+  // ({mean, maxTile, k, kMark, nonfinite, tilesX, tilesY, kernelMs, tileErr?}); remark moves the mark to now
+  noiseMark() { this.lib.noiseMark(this.ctx); }
+  noise({ remark = false, tiles = false } = {}) { return this.lib.noise(this.ctx, !!remark, !!tiles); }
 
   // the display pass: pixelFilter over the accumulated frame -> RGBA8 (row 0 = bottom, GL order)
   image() {

@@ -1,7 +1,7 @@
 #!/bin/sh
 # Builds experimental variants of libsail_hip.so (same sources, different -D flags) into sail_amd/lib/variants/.
 # Usage: tools/build_variants.sh name1 "-DFLAG=1" name2 "-DFLAG=2" ...
-# A flags string may start with "src=<file under csrc/>" to build that source instead of sail_trace.hip.
+# A flags string may start with "src=<file under csrc/>" to build that source in place of sail_trace.hip.
 set -e
 cd "$(dirname "$0")/../sail_amd"
 mkdir -p lib/variants build/variants
@@ -14,9 +14,11 @@ $HIPCC $COMMON -c csrc/sail_jit.cpp -o build/variants/sail_jit.o
 $HIPCC $COMMON -c build/variants/sail_jit_src.cpp -o build/variants/sail_jit_src.o
 while [ $# -ge 2 ]; do
   name=$1; flags=$2; shift 2
-  src=sail_trace.hip
-  case "$flags" in src=*) src=${flags%% *}; src=${src#src=}; flags=${flags#src=$src}; esac
-  $HIPCC $COMMON $flags -Icsrc -c csrc/$src -o build/variants/trace_$name.o
+  # the device code is one translation unit, like the product: sail_kernels.hip (sail_noise.hip + sail_trace.hip), or
+  # sail_noise.hip force-included in front of the source that stands in for sail_trace.hip
+  src=sail_kernels.hip; pre=""
+  case "$flags" in src=*) src=${flags%% *}; src=${src#src=}; flags=${flags#src=$src}; pre="-include csrc/sail_noise.hip"; esac
+  $HIPCC $COMMON $flags -Icsrc $pre -c csrc/$src -o build/variants/trace_$name.o
   $HIPCC -shared -fPIC --offload-arch=gfx950 build/variants/trace_$name.o build/variants/sail_capi.o \
     build/variants/sail_hostmath.o build/variants/sail_jit.o build/variants/sail_jit_src.o -o lib/variants/libsail_hip_$name.so -ldl
   echo "built $name ($flags)"
