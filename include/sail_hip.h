@@ -202,13 +202,67 @@ int sail_plan_until(uint64_t k, uint64_t min_spp, uint64_t max_spp, uint64_t* ne
 typedef struct sail_until_step { uint64_t k; double mean, max_tile; } sail_until_step;
 /* Render the frozen schedule (sail_schedule) from the context's sample index on, looking at sail_plan_until's indices:
  * mark at the first look (its step reports mean = max_tile = +inf: no estimate yet), estimate + remark at each later one,
- * stop when mean <= target (*converged = 1) or k == max_spp (0). The frame equals sail_render_schedule over the same
+ * stop when mean <= target (*converged = 1) or k == max_spp (0). The look it stops at does not re-mark: a frame that had a
+ * second look keeps the mark of the look before, for sail_denoise. The frame equals sail_render_schedule over the same
  * indices bit for bit. history (may be NULL) receives the first `capacity` looks, *looks (may be NULL) the number of looks
  * made; *out is the last estimate (mean = max_tile = +inf when no look estimated). A context already at or past max_spp
  * renders nothing. No scene, SAIL_ACCUM_COMPAT8 or a half-loaded checkpoint: SAIL_E_STATE before anything is rendered. max_spp is at most 2^31 - 1 (the schedule's index type). */
 int sail_render_until(sail_ctx* ctx, const double mvp_rowmajor[16], const float eye[3], int max_bounces, double target,
                       uint64_t min_spp, uint64_t max_spp, sail_noise_info* out, int* converged,
                       sail_until_step* history, int capacity, int* looks);
+
+/* ---- variance-guided a-trous denoiser of a progressive frame (no reference counterpart: the reference's only denoiser is
+ * the `wavelet` display filter, whose edge stops are constants; the edge-avoiding a-trous wavelet of SVGF, Schied et al.
+ * 2017, without its temporal part) ----
+ * Works on what the noise estimate keeps: S, the accumulator the context shows, P, the mark, and the normal and position
+ * AOVs N and X (SAIL_FLAG_AOV). Every operation is an f32 IEEE operation in the order written:
+ *   n, h as in sail_noise_estimate (SUM: S.w, P.w; MIX: f32 of the sample index now / at the mark)
+ *   lum(c) = ((c.r + c.g) + c.b) / 3
+ *   c0 = n > 0 ? S.rgb / n : 0                  (MIX: c0 = S.rgb)
+ *   halves = h > 0 and n > h
+ *   a = P.rgb / h; b = (S.rgb - P.rgb) / (n - h)           (MIX: a, b as in the estimate)
+ *   dl = lum(a) - lum(b);   v0 = halves ? (dl*dl) * ((h*(n-h)) / (n*n)) : 0      -- variance of the mean
+ *   v = 3x3 prefilter of v0: taps dy,dx in -1..1 row-major (dy outer), weight g[|dy|+|dx|], g = {1/4, 1/8, 1/16},
+ *       skipping taps outside the frame or not finite; v = acc / wsum, or 0 if wsum is not > 0
+ *   nd = 2 * N.xyz - 1   (decoded normal AOV);   x = X.xyz (position AOV as stored)
+ *   for it = 0 .. iterations-1, s = 1 << it, from (c, v) of the pass before:
+ *     den = (sigma_l*sigma_l) * v_p + 1e-8;   sxs = (sigma_x * (float)s) * (sigma_x * (float)s);   lp = lum(c_p)
+ *     for dy = -2..2 (outer), dx = -2..2, q = p + s*(dx, dy), skipped when outside the frame (no wrap, never loaded):
+ *       kw = k[|dy|] * k[|dx|],  k = {3/8, 1/4, 1/16}
+ *       centre tap: w = kw
+ *       else: d = max((nd_p.x*nd_q.x + nd_p.y*nd_q.y) + nd_p.z*nd_q.z, 0); six times d = d*d          (power 64)
+ *             t = x_p - x_q;  dx2 = (t.x*t.x + t.y*t.y) + t.z*t.z;  wx = 1 / (1 + dx2 / sxs)
+ *             dq = lp - lum(c_q);  wl = 1 / (1 + (dq*dq) / den)
+ *             w = ((kw * d) * wx) * wl
+ *       the tap counts only if w > 0 and c_q.r, c_q.g, c_q.b and v_q are all finite
+ *       acc += w * c_q;   vacc += (w*w) * v_q;   wsum += w
+ *     if wsum > 0: c_p = acc / wsum, v_p = vacc / (wsum*wsum);   else c_p, v_p stay
+ * The weights are rational instead of exp() on purpose: no math-library question, a float32 restatement gives the same
+ * bits. A pixel that misses the scene carries a NaN position, takes no neighbours and stays as it is; a pixel whose mean
+ * is not finite stays as it is and feeds nobody. out_rgba8 is the display transform (sail_filter's kinds 0..2, applied to
+ * the denoised texel itself) quantised as the filter kernel does: (uint8)(int)(clamp(o, 0, 1) * 255 + 0.5), alpha 255.
+ * State rules as sail_noise_estimate: queued samples are launched first; no mark, or no sample since it: SAIL_E_STATE;
+ * SAIL_ACCUM_COMPAT8, a context without SAIL_FLAG_AOV and a half-loaded checkpoint are refused (SAIL_E_STATE); a
+ * multi-device context reduces first and works on device 0's frame and AOV maps. Nothing a later call can see changes. */
+typedef struct sail_denoise_params {
+  int iterations;   /* a-trous passes with step 1, 2, 4, ...: 1..6            [4]   */
+  float sigma_l;    /* luminance edge stop, in standard deviations of the mean [1.0] */
+  float sigma_x;    /* position edge stop per pixel of step                    [0.2] */
+  int display;      /* SAIL_FILTER_COLOR | GAMMA | TONEMAPPING, for out_rgba8  [COLOR] */
+  float gamma_c;    /*                                                         [2.2] */
+} sail_denoise_params;
+typedef struct sail_denoise_info {
+  uint64_t k, k_mark, nonfinite;   /* nonfinite: pixels whose mean colour is not finite */
+  int iterations;
+  double kernel_ms, pass_ms[8];    /* HIP events: total; [0] = prepare, [1..] = each a-trous pass */
+} sail_denoise_info;
+/* host only: the bracketed defaults */
+int sail_denoise_defaults(sail_denoise_params* p);
+/* p == NULL: the defaults. out_rgba (W H 4 f32: the denoised mean, w = 1, row 0 = bottom), out_var (W H f32: the filtered
+ * variance of the mean's luminance), out_rgba8 (W H 4 bytes) and info may each be NULL. SAIL_E_INVALID: iterations outside
+ * 1..6, a sigma that is not finite and > 0, a display other than kinds 0..2. */
+int sail_denoise(sail_ctx* ctx, const sail_denoise_params* p, float* out_rgba, float* out_var, uint8_t* out_rgba8,
+                 sail_denoise_info* info);
 
 /* ---- checkpoint / resume of a progressive render (no reference counterpart: the reference restarts its
  * accumulation on every camera or object change, src/core/renderer.js:57-60, src/scene/scene.js:65-68) ----

@@ -49,6 +49,7 @@ EXPORTS = (
     "sail_get_kernel_info", "sail_kernel_ready", "sail_set_jit_cache", "sail_jit_prebuild",
     "sail_plan_reduce", "sail_plan_keep", "sail_plan_load_part",
     "sail_noise_mark", "sail_noise_estimate", "sail_plan_until", "sail_render_until",
+    "sail_denoise_defaults", "sail_denoise",
 )
 
 
@@ -86,6 +87,16 @@ class NoiseInfo(ctypes.Structure):
 
 class UntilStep(ctypes.Structure):
     _fields_ = [("k", ctypes.c_uint64), ("mean", ctypes.c_double), ("max_tile", ctypes.c_double)]
+
+
+class DenoiseParams(ctypes.Structure):
+    _fields_ = [("iterations", ctypes.c_int), ("sigma_l", ctypes.c_float), ("sigma_x", ctypes.c_float),
+                ("display", ctypes.c_int), ("gamma_c", ctypes.c_float)]
+
+
+class DenoiseInfo(ctypes.Structure):
+    _fields_ = [("k", ctypes.c_uint64), ("k_mark", ctypes.c_uint64), ("nonfinite", ctypes.c_uint64),
+                ("iterations", ctypes.c_int), ("kernel_ms", ctypes.c_double), ("pass_ms", ctypes.c_double * 8)]
 
 
 _SHAPES = {"cube": 1, "sphere": 2, "rectangle": 3, "cone": 4, "cylinder": 5, "disk": 6,
@@ -179,6 +190,9 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
         "sail_render_until": (ctypes.c_int, [vp, f64p, f32p, ctypes.c_int, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint64,
                                              ctypes.POINTER(NoiseInfo), ctypes.POINTER(ctypes.c_int),
                                              ctypes.POINTER(UntilStep), ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+        "sail_denoise_defaults": (ctypes.c_int, [ctypes.POINTER(DenoiseParams)]),
+        "sail_denoise": (ctypes.c_int, [vp, ctypes.POINTER(DenoiseParams), f32p, f32p, ctypes.POINTER(ctypes.c_uint8),
+                                        ctypes.POINTER(DenoiseInfo)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -305,6 +319,18 @@ def plan_until(k: int, min_spp: int, max_spp: int) -> int:
 def _noise_dict(n: NoiseInfo) -> dict:
     return {"mean": n.mean, "max_tile": n.max_tile, "k": int(n.k), "k_mark": int(n.k_mark), "nonfinite": int(n.nonfinite),
             "tiles_x": n.tiles_x, "tiles_y": n.tiles_y, "kernel_ms": n.kernel_ms}
+
+
+def denoise_defaults() -> dict:
+    """sail_denoise's default parameters (sail_denoise_defaults, host-only): iterations, sigma_l, sigma_x, display,
+    gamma_c."""
+    lib = load()
+    p = DenoiseParams()
+    rc = lib.sail_denoise_defaults(ctypes.byref(p))
+    if rc:
+        raise SailError(f"sail_denoise_defaults: {rc}")
+    return {"iterations": p.iterations, "sigma_l": p.sigma_l, "sigma_x": p.sigma_x, "display": p.display,
+            "gamma_c": p.gamma_c}
 
 
 def prim_bounds(objects, n: int, tn: int) -> np.ndarray:
@@ -528,6 +554,35 @@ class Context:
         out = _noise_dict(n)
         out["converged"] = bool(conv.value)
         out["history"] = [{"k": int(s.k), "mean": s.mean, "max_tile": s.max_tile} for s in hist[:min(looks.value, cap)]]
+        return out
+
+    def denoise(self, params: Optional[dict] = None, want_var: bool = False, want_u8: bool = False) -> dict:
+        """The variance-guided a-trous denoiser over the frame, the noise mark and the AOV maps (sail_denoise). `params`
+        overrides entries of denoise_defaults(). Returns "rgba" (H, W, 4) f32, with want_var "var" (H, W) f32, with
+        want_u8 "u8" (H, W, 4) uint8 (the display transform), and k, k_mark, nonfinite, iterations, kernel_ms and
+        pass_ms (prepare, then each a-trous pass)."""
+        p = None
+        if params is not None:
+            d = denoise_defaults()
+            unknown = set(params) - set(d)
+            if unknown:
+                raise SailError(f"denoise: unknown parameters {sorted(unknown)}")
+            d.update(params)
+            p = DenoiseParams(int(d["iterations"]), float(d["sigma_l"]), float(d["sigma_x"]), int(d["display"]),
+                              float(d["gamma_c"]))
+        info = DenoiseInfo()
+        rgba = np.zeros((self.H, self.W, 4), dtype=np.float32)
+        var = np.zeros((self.H, self.W), dtype=np.float32) if want_var else None
+        u8 = np.zeros((self.H, self.W, 4), dtype=np.uint8) if want_u8 else None
+        self._check(self.lib.sail_denoise(self.h, ctypes.byref(p) if p is not None else None, _ptr(rgba), _ptr(var),
+                                          _ptr(u8, ctypes.c_uint8), ctypes.byref(info)), "sail_denoise")
+        out = {"rgba": rgba, "k": int(info.k), "k_mark": int(info.k_mark), "nonfinite": int(info.nonfinite),
+               "iterations": info.iterations, "kernel_ms": info.kernel_ms,
+               "pass_ms": [info.pass_ms[i] for i in range(info.iterations + 1)]}
+        if want_var:
+            out["var"] = var
+        if want_u8:
+            out["u8"] = u8
         return out
 
     def filter_ms(self) -> float:

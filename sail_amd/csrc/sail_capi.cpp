@@ -29,6 +29,10 @@ hipError_t sail_launch_pick(const SailPrim* prims, int n, const float* rays, int
 // sail_noise.hip: the noise estimate's per-tile pass
 #include "sail_noise.h"
 hipError_t sail_launch_noise(const SailNoiseArgs& A, hipStream_t s);
+// sail_denoise.hip: the denoiser's prepare pass and one a-trous pass
+#include "sail_denoise.h"
+hipError_t sail_launch_denoise_prepare(const SailDenoisePrepareArgs& A, hipStream_t s);
+hipError_t sail_launch_denoise_atrous(const SailDenoiseAtrousArgs& A, hipStream_t s);
 
 namespace {
 
@@ -190,6 +194,9 @@ struct sail_ctx {
   uint64_t noiseK = 0;
   float* noiseOut = nullptr;
   float* noisePix = nullptr;  // the optional per-pixel map, allocated on first use
+  // Denoiser (sail_denoise): one block of work buffers, allocated on first use: two (c, v) float4 maps, the guides as a
+  // float4 and a float2 map, the variance map, the RGBA8 map and the per-tile non-finite counts
+  void* denoiseWork = nullptr;
   nccl_comm_t comm = nullptr;
   int commRanks = 0, commRank = 0;
   // Reduced frame (root of sail_reduce / device 0 of a multi-device context): the sum of every rank's
@@ -1198,7 +1205,7 @@ void sail_destroy(sail_ctx* c) {
   for (auto& pr : c->pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
   for (auto e : c->evPool) (void)hipEventDestroy(e);
   void* bufs[] = {c->accum, c->frame, c->frameN, c->frameP, c->aovN, c->aovP, c->filterOut, c->filterOut8, c->stage, c->segCounter, c->prims, c->tp, c->lt, c->lightObjRow, c->samples, c->wf,
-                  c->noiseMark, c->noiseOut, c->noisePix};
+                  c->noiseMark, c->noiseOut, c->noisePix, c->denoiseWork};
   for (void* b : bufs) if (b) (void)hipFree(b);
   if (c->samplesPinned) (void)hipHostFree(c->samplesPinned);
   if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1869,9 +1876,13 @@ int sail_render_until(sail_ctx* c, const double mvp[16], const float eye[3], int
       marked = true;
       out->k = out->k_mark = k;
     } else {
-      if (int rc = sail_noise_estimate(c, out, nullptr, nullptr, 1)) return rc;
+      // the last look (converged, or at max_spp) leaves the mark at the look before, so that the frame keeps its two
+      // halves for sail_denoise; every other look moves the mark to now
+      if (int rc = sail_noise_estimate(c, out, nullptr, nullptr, 0)) return rc;
       step.mean = out->mean; step.max_tile = out->max_tile;
       conv = out->mean <= target;
+      if (!conv && k < max_spp)
+        if (int rc = sail_noise_mark(c)) return rc;
     }
     if (history && nlooks < capacity) history[nlooks] = step;
     nlooks++;
@@ -1879,6 +1890,118 @@ int sail_render_until(sail_ctx* c, const double mvp[16], const float eye[3], int
   }
   if (converged) *converged = conv;
   if (looks) *looks = nlooks;
+  return SAIL_OK;
+}
+
+// ---- variance-guided a-trous denoiser (include/sail_hip.h; the kernels are sail_denoise.hip) --------------------------------
+int sail_denoise_defaults(sail_denoise_params* p) {
+  if (!p) return SAIL_E_INVALID;
+  p->iterations = 4;
+  p->sigma_l = 1.0f;
+  p->sigma_x = 0.2f;
+  p->display = SAIL_FILTER_COLOR;
+  p->gamma_c = 2.2f;
+  return SAIL_OK;
+}
+
+int sail_denoise(sail_ctx* c, const sail_denoise_params* params, float* out_rgba, float* out_var, uint8_t* out_rgba8,
+                 sail_denoise_info* info) {
+  if (!c) return SAIL_E_INVALID;
+  sail_denoise_params p;
+  sail_denoise_defaults(&p);
+  if (params) p = *params;
+  if (p.iterations < 1 || p.iterations > 6 || !(p.sigma_l > 0.0f) || !std::isfinite(p.sigma_l) || !(p.sigma_x > 0.0f) ||
+      !std::isfinite(p.sigma_x) || p.display < SAIL_FILTER_COLOR || p.display > SAIL_FILTER_TONEMAPPING)
+    return fail(c, SAIL_E_INVALID, "sail_denoise: bad parameters (iterations %d of 1..6, sigma_l %g and sigma_x %g finite and > 0, display %d of 0..2)",
+                p.iterations, (double)p.sigma_l, (double)p.sigma_x, p.display);
+  if (!c->subs.empty()) {  // device 0's reduced frame and AOV maps, like sail_filter
+    if (int rc = loadIncomplete(c, "sail_denoise")) return rc;
+    if (int rc = groupReduce(c)) return rc;
+    return relay(c, sail_denoise(c->subs[0], &p, out_rgba, out_var, out_rgba8, info), c->subs[0]);
+  }
+  if (!c->aovN || !c->aovP)
+    return fail(c, SAIL_E_STATE, "sail_denoise: reads the normal and position AOVs (create with SAIL_FLAG_AOV)");
+  if (c->accumMode == SAIL_ACCUM_COMPAT8)
+    return fail(c, SAIL_E_STATE, "sail_denoise: SAIL_ACCUM_COMPAT8 stores 8-bit frames, whose halves cannot be compared");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = sail_sync(c)) return rc;
+  if (!c->noiseHave || !c->noiseMark)
+    return fail(c, SAIL_E_STATE, "sail_denoise: no mark (sail_noise_mark first; a reset or a new scene drops it)");
+  if (c->k <= c->noiseK)
+    return fail(c, SAIL_E_STATE, "sail_denoise: no sample since the mark (k = %llu, marked at %llu)",
+                (unsigned long long)c->k, (unsigned long long)c->noiseK);
+  const int tx = (c->W + 15) / 16, ty = (c->H + 15) / 16;
+  const size_t nt = (size_t)tx * ty, np = (size_t)c->W * c->H;
+  // cvA | cvB | g0 (16 B each) | g1 (8 B) | var (4 B) | rgba8 (4 B) per pixel, then a count per tile
+  if (!c->denoiseWork && hipMalloc(&c->denoiseWork, np * 64 + nt * 4) != hipSuccess) {
+    c->denoiseWork = nullptr;
+    return fail(c, SAIL_E_OOM, "denoise work buffers");
+  }
+  char* base = (char*)c->denoiseWork;
+  float4* cv[2] = {(float4*)base, (float4*)(base + np * 16)};
+  float4* g0 = (float4*)(base + np * 32);
+  float2* g1 = (float2*)(base + np * 48);
+  float* dVar = (float*)(base + np * 56);
+  uint32_t* d8 = (uint32_t*)(base + np * 60);
+  uint32_t* dBad = (uint32_t*)(base + np * 64);
+  SailDenoisePrepareArgs A;
+  memset(&A, 0, sizeof A);
+  A.S = shownAccum(c); A.P = c->noiseMark; A.N = shownAovN(c); A.X = shownAovP(c);
+  A.cv = cv[0]; A.g0 = g0; A.g1 = g1; A.tileBad = dBad;
+  A.W = c->W; A.H = c->H;
+  A.mix = c->accumMode == SAIL_ACCUM_MIX;
+  A.kf = (float)c->k; A.hf = (float)c->noiseK;
+  const int nev = p.iterations + 2;  // before the prepare pass, then after every pass
+  hipEvent_t ev[8] = {};
+  for (int i = 0; i < nev; i++)
+    if (int rc = getEvent(c, &ev[i])) {
+      for (int j = 0; j < i; j++) c->evPool.push_back(ev[j]);
+      return rc;
+    }
+  hipError_t e = hipEventRecord(ev[0], c->stream);
+  if (e == hipSuccess) e = sail_launch_denoise_prepare(A, c->stream);
+  if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
+  int cur = 0;
+  for (int it = 0; it < p.iterations && e == hipSuccess; it++) {
+    const bool last = it == p.iterations - 1;
+    SailDenoiseAtrousArgs B;
+    memset(&B, 0, sizeof B);
+    B.src = cv[cur];
+    B.dst = (last && !out_rgba) ? nullptr : cv[cur ^ 1];
+    B.g0 = g0; B.g1 = g1;
+    B.outVar = (last && out_var) ? dVar : nullptr;
+    B.out8 = (last && out_rgba8) ? d8 : nullptr;
+    B.W = c->W; B.H = c->H;
+    B.step = 1 << it;
+    B.last = last;
+    B.sl2 = p.sigma_l * p.sigma_l;
+    const float sx = p.sigma_x * (float)B.step;
+    B.sxs = sx * sx;
+    B.display = p.display; B.gammaC = p.gamma_c;
+    e = sail_launch_denoise_atrous(B, c->stream);
+    if (e == hipSuccess) e = hipEventRecord(ev[it + 2], c->stream);
+    cur ^= 1;
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  float ms[8] = {}, total = 0.0f;
+  for (int i = 0; i + 1 < nev && e == hipSuccess; i++) e = hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]);
+  if (e == hipSuccess) e = hipEventElapsedTime(&total, ev[0], ev[nev - 1]);
+  for (int i = 0; i < nev; i++) c->evPool.push_back(ev[i]);
+  std::vector<uint32_t> bad(nt);
+  if (e == hipSuccess) e = hipMemcpy(bad.data(), dBad, nt * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && out_rgba) e = hipMemcpy(out_rgba, cv[cur], np * 16, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && out_var) e = hipMemcpy(out_var, dVar, np * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && out_rgba8) e = hipMemcpy(out_rgba8, d8, np * 4, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(c, SAIL_E_HIP, "sail_denoise: %s", hipGetErrorString(e));
+  if (info) {
+    memset(info, 0, sizeof *info);
+    info->k = c->k;
+    info->k_mark = c->noiseK;
+    for (uint32_t b : bad) info->nonfinite += b;
+    info->iterations = p.iterations;
+    info->kernel_ms = total;
+    for (int i = 0; i + 1 < nev; i++) info->pass_ms[i] = ms[i];
+  }
   return SAIL_OK;
 }
 

@@ -2,6 +2,8 @@
 // gfx950 code object (tests/test_jit_compile.py disassembles "the" code object of the library). Each kernel file stays
 // its own source and compiles on its own too (the study and variant builds under tools/ do that); sail_trace.hip is not
 // touched by what is added here: its text is embedded in the library and hashed into every run-time kernel's cache key.
-// sail_noise.hip comes first: it defines no macro, so the trace kernels compile exactly as they do alone.
+// sail_noise.hip and sail_denoise.hip come first: they define no macro (sail_denoise.hip includes sail_math.h, which
+// sail_trace.hip includes itself), so the trace kernels compile exactly as they do alone.
 #include "sail_noise.hip"
+#include "sail_denoise.hip"
 #include "sail_trace.hip"

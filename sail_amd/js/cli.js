@@ -4,14 +4,17 @@
 // assigns `scene`, then Renderer.update(scene)), render N samples on the GPU and write the frame to disk.
 //
 //   node sail_amd/js/cli.js scene.js [--width 512] [--height 512] [--spp 64] [--bounces 5] [--device -1]
-//        [--noise X [--min-spp 16] [--max-spp 65536]]
+//        [--noise X [--min-spp 16] [--max-spp 65536]] [--denoise [--denoise-iterations 4]]
 //        [--filter <name>] [--filter-r 'vec2(2.0,2.0)'] [--gamma 2.2] [--deterministic]
 //        [--png out.png] [--pfm out.pfm] [--exr out.exr] [--stats]
 //
 // --noise X (instead of --spp) renders until the frame's noise estimate is at most X: it looks at --min-spp samples and at
 // every doubling, up to --max-spp. --stats then also prints the spp reached, the noise and whether it converged.
+// --denoise writes the variance-guided a-trous denoiser's image instead of the frame: with --spp N it marks the frame at
+// floor(N/2) samples, with --noise X it uses the mark of the look before the last. --stats then also prints denoise_ms.
 // The script sees `Sail` (the full API) and must assign `scene` (a Sail.Scene with a camera), exactly as the
-// editor text does. --filter overrides scene.filter for the PNG; the PFM and EXR are always the unfiltered mean image.
+// editor text does. --filter overrides scene.filter for the PNG (with --denoise it becomes the denoiser's display transform:
+// color, gamma or tonemapping); without --denoise the PFM and EXR are always the unfiltered mean image.
 const fs = require('fs');
 const path = require('path');
 const vm = require('vm');
@@ -31,6 +34,8 @@ function parse(argv) {
       case '--noise': opt.noise = parseFloat(val()); break;
       case '--min-spp': opt.minSpp = parseInt(val(), 10); opt.untilGiven = a; break;
       case '--max-spp': opt.maxSpp = parseInt(val(), 10); opt.untilGiven = a; break;
+      case '--denoise': opt.denoise = true; break;
+      case '--denoise-iterations': opt.denoiseIterations = parseInt(val(), 10); break;
       case '--bounces': opt.bounces = parseInt(val(), 10); break;
       case '--device': opt.device = parseInt(val(), 10); break;
       case '--filter': opt.filter = val(); break;
@@ -50,6 +55,11 @@ function parse(argv) {
   if (opt.noise !== undefined && opt.sppGiven) throw new Error('--noise and --spp exclude each other');
   if (opt.noise !== undefined && Number.isNaN(opt.noise)) throw new Error('--noise needs a number');
   if (opt.noise === undefined && opt.untilGiven) throw new Error(`${opt.untilGiven} needs --noise`);
+  if (opt.denoiseIterations !== undefined && !opt.denoise) throw new Error('--denoise-iterations needs --denoise');
+  if (opt.denoiseIterations !== undefined && !(opt.denoiseIterations >= 1 && opt.denoiseIterations <= 6))
+    throw new Error('--denoise-iterations needs a number from 1 to 6');
+  if (opt.denoise && opt.noise === undefined && !(opt.spp >= 2))
+    throw new Error('--denoise needs --spp 2 or more: it compares the two halves of the samples');
   opt.script = rest[0];
   return opt;
 }
@@ -66,32 +76,46 @@ function loadScene(file) {
 function main() {
   const opt = parse(process.argv.slice(2));
   if (opt.help || !opt.script) {
-    process.stdout.write(fs.readFileSync(__filename, 'utf8').split('\n').slice(2, 14).map((l) => l.replace(/^\/\/ ?/, '')).join('\n') + '\n');
+    process.stdout.write(fs.readFileSync(__filename, 'utf8').split('\n').slice(2, 17).map((l) => l.replace(/^\/\/ ?/, '')).join('\n') + '\n');
     return opt.help ? 0 : 2;
   }
   const scene = loadScene(opt.script);
   if (opt.filter) scene.filter = opt.filter;
   if (opt.filterR) scene.filter.addParam('r', opt.filterR);
   if (opt.gamma) scene.filter.addParam('c', opt.gamma);
-  const needAov = ['wavelet', 'normal', 'position'].includes(scene.filter.name);
+  const pointwise = ['color', 'gamma', 'tonemapping'].includes(scene.filter.name);
+  if (opt.denoise && opt.png && !pointwise)
+    throw new Error(`--denoise --png applies the filter to the denoised texel: it needs --filter color, gamma or tonemapping, not ${scene.filter.name}`);
+  const needAov = opt.denoise || ['wavelet', 'normal', 'position'].includes(scene.filter.name);
   const r = new Sail.Renderer({ width: opt.width, height: opt.height, device: opt.device, maxBounces: opt.bounces,
     deterministic: opt.deterministic, accumulation: 'sum', aov: needAov, display: false });
   r.update(scene);
   const t0 = process.hrtime.bigint();
   let until = null;
   if (opt.noise !== undefined) until = r.renderUntil(scene, { noise: opt.noise, minSpp: opt.minSpp, maxSpp: opt.maxSpp });
-  else r.renderSamples(scene, opt.spp);
-  const mean = r.readPixels();
+  else if (opt.denoise) {  // the two halves the denoiser compares
+    r.renderSamples(scene, Math.floor(opt.spp / 2));
+    r.noiseMark();
+    r.renderSamples(scene, opt.spp - Math.floor(opt.spp / 2));
+  } else r.renderSamples(scene, opt.spp);
+  let mean, den = null;
+  if (opt.denoise) {
+    if (until && until.history.length < 2)
+      throw new Error(`--denoise: the render stopped at its first look (${until.k} spp), which only marks the frame: no second look, so there are no two halves to compare (raise --max-spp above --min-spp)`);
+    den = r.denoise({ iterations: opt.denoiseIterations, display: opt.png ? r.filter.kind : undefined, gamma: r.filter.gamma });
+    mean = den.rgba;
+  } else mean = r.readPixels();
   const ms = Number(process.hrtime.bigint() - t0) / 1e6;
   if (opt.pfm) writePFM(opt.pfm, opt.width, opt.height, mean);
   if (opt.exr) writeEXR(opt.exr, opt.width, opt.height, mean);
-  if (opt.png) writePNG(opt.png, opt.width, opt.height, r.image());
+  if (opt.png) writePNG(opt.png, opt.width, opt.height, den ? den.rgba8 : r.image());
   if (opt.stats) {
     const st = r.stats();
     const out = { width: opt.width, height: opt.height, spp: until ? until.k : opt.spp, bounces: opt.bounces,
       ms, segments: st.segments, kernelMs: st.kernelMs, filter: scene.filter.name };
     // (a frame that never reached a second look has no estimate: its noise is infinite, null in JSON)
     if (until) Object.assign(out, { noise: until.mean, converged: until.converged });
+    if (den) out.denoise_ms = den.info.kernelMs;
     process.stdout.write(JSON.stringify(out) + '\n');
   }
   r.destroy();

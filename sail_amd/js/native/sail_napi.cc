@@ -460,6 +460,52 @@ napi_value RenderUntil(napi_env env, napi_callback_info info) {
   NAPI_OK(napi_set_named_property(env, out, "history", list));
   return out;
 }
+// the denoiser (sail_denoise): (ctx, iterations, sigmaL, sigmaX, display, gamma, wantU8) -> {rgba, rgba8?, info}; a
+// parameter that is undefined or null keeps sail_denoise_defaults' value
+napi_value Denoise(napi_env env, napi_callback_info info) {
+  napi_value a[7];
+  if (!args(env, info, 7, a)) return nullptr;
+  Handle* h;
+  if (!getHandle(env, a[0], &h)) return nullptr;
+  sail_denoise_params p;
+  sail_denoise_defaults(&p);
+  double v[5] = {(double)p.iterations, p.sigma_l, p.sigma_x, (double)p.display, p.gamma_c};
+  for (int i = 0; i < 5; i++) {
+    napi_valuetype vt;
+    napi_typeof(env, a[1 + i], &vt);
+    if (vt == napi_undefined || vt == napi_null) continue;
+    if (!getDouble(env, a[1 + i], &v[i])) return nullptr;
+  }
+  if (v[0] != (double)(int)v[0] || v[3] != (double)(int)v[3]) {
+    napi_throw_range_error(env, nullptr, "iterations and display must be integers");
+    return nullptr;
+  }
+  p.iterations = (int)v[0]; p.sigma_l = (float)v[1]; p.sigma_x = (float)v[2]; p.display = (int)v[3]; p.gamma_c = (float)v[4];
+  bool wantU8 = false;
+  napi_get_value_bool(env, a[6], &wantU8);
+  const size_t np = (size_t)h->W * h->H * 4;
+  void *pf = nullptr, *p8 = nullptr;
+  napi_value f = makeTyped(env, napi_float32_array, np, 4, &pf), u8 = nullptr;
+  if (wantU8) u8 = makeTyped(env, napi_uint8_array, np, 1, &p8);
+  sail_denoise_info n;
+  const int rc = sail_denoise(h->ctx, &p, (float*)pf, nullptr, (uint8_t*)p8, &n);
+  if (rc) return throwSail(env, "sail_denoise", rc, h->ctx);
+  napi_value out, inf, passes;
+  NAPI_OK(napi_create_object(env, &out));
+  NAPI_OK(napi_create_object(env, &inf));
+  napi_set_named_property(env, inf, "k", num(env, (double)n.k));
+  napi_set_named_property(env, inf, "kMark", num(env, (double)n.k_mark));
+  napi_set_named_property(env, inf, "nonfinite", num(env, (double)n.nonfinite));
+  napi_set_named_property(env, inf, "iterations", num(env, n.iterations));
+  napi_set_named_property(env, inf, "kernelMs", num(env, n.kernel_ms));
+  NAPI_OK(napi_create_array_with_length(env, (size_t)n.iterations + 1, &passes));
+  for (int i = 0; i <= n.iterations; i++) napi_set_element(env, passes, (uint32_t)i, num(env, n.pass_ms[i]));
+  NAPI_OK(napi_set_named_property(env, inf, "passMs", passes));
+  NAPI_OK(napi_set_named_property(env, out, "rgba", f));
+  if (wantU8) NAPI_OK(napi_set_named_property(env, out, "rgba8", u8));
+  NAPI_OK(napi_set_named_property(env, out, "info", inf));
+  return out;
+}
 // (ctx, timeoutMs) -> whether the scene's run-time kernel is loaded (sail_kernel_ready; -1 waits for its build)
 napi_value KernelReady(napi_env env, napi_callback_info info) {
   napi_value a[2];
@@ -617,6 +663,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"noiseMark", 0, NoiseMark, 0, 0, 0, napi_enumerable, 0},
       {"noise", 0, Noise, 0, 0, 0, napi_enumerable, 0},
       {"renderUntil", 0, RenderUntil, 0, 0, 0, napi_enumerable, 0},
+      {"denoise", 0, Denoise, 0, 0, 0, napi_enumerable, 0},
       {"kernelReady", 0, KernelReady, 0, 0, 0, napi_enumerable, 0},
       {"kernelInfo", 0, KernelInfo, 0, 0, 0, napi_enumerable, 0},
       {"pick", 0, Pick, 0, 0, 0, napi_enumerable, 0},

@@ -11,7 +11,8 @@
 // Extensions (same API object): renderSamples(scene, spp) runs a whole deterministic sample schedule in
 // one call; readPixels() / readAOV() / image() read the float frame back (the reference never reads back);
 // renderUntil(scene, {noise, minSpp, maxSpp}) renders until the device-side noise estimate is at most `noise`
-// (noiseMark() / noise() are its two halves: sail_noise_mark / sail_noise_estimate).
+// (noiseMark() / noise() are its two halves: sail_noise_mark / sail_noise_estimate); denoise({...}) runs the
+// variance-guided a-trous denoiser over the frame, the mark and the AOV maps (sail_denoise).
 const native = require('./native');
 const { filterConfig } = require('./filter');
 
@@ -142,6 +143,22 @@ class Renderer {
   // ({mean, maxTile, k, kMark, nonfinite, tilesX, tilesY, kernelMs, tileErr?}); remark moves the mark to now
   noiseMark() { this.lib.noiseMark(this.ctx); }
   noise({ remark = false, tiles = false } = {}) { return this.lib.noise(this.ctx, !!remark, !!tiles); }
+
+  // The variance-guided a-trous denoiser over the frame, the noise mark and the AOV maps (sail_denoise): needs a mark with
+  // samples after it (noiseMark(), or a renderUntil that made a second look). Options left out keep the library's
+  // defaults (4 passes, sigmaL 1, sigmaX 0.2, display 'color', gamma 2.2); display ('color' | 'gamma' | 'tonemapping')
+  // asks for rgba8 as well. Returns {rgba: Float32Array (the denoised mean, row 0 = bottom), rgba8?, info: {k, kMark,
+  // nonfinite, iterations, kernelMs, passMs}}. The frame itself is not changed.
+  denoise({ iterations, sigmaL, sigmaX, display, gamma } = {}) {
+    if (!this.aov) throw new Error('Renderer.denoise reads the normal and position AOVs: create the Renderer with aov: true');
+    const kinds = { color: 0, gamma: 1, tonemapping: 2 };
+    let kind;
+    if (display !== undefined) {
+      kind = typeof display === 'number' ? display : kinds[display];
+      if (kind === undefined) throw new Error(`Renderer.denoise: unknown display '${display}' (color | gamma | tonemapping)`);
+    }
+    return this.lib.denoise(this.ctx, iterations, sigmaL, sigmaX, kind, gamma, display !== undefined);
+  }
 
   // the display pass: pixelFilter over the accumulated frame -> RGBA8 (row 0 = bottom, GL order)
   image() {

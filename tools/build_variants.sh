@@ -14,10 +14,10 @@ $HIPCC $COMMON -c csrc/sail_jit.cpp -o build/variants/sail_jit.o
 $HIPCC $COMMON -c build/variants/sail_jit_src.cpp -o build/variants/sail_jit_src.o
 while [ $# -ge 2 ]; do
   name=$1; flags=$2; shift 2
-  # the device code is one translation unit, like the product: sail_kernels.hip (sail_noise.hip + sail_trace.hip), or
-  # sail_noise.hip force-included in front of the source that stands in for sail_trace.hip
+  # the device code is one translation unit, like the product: sail_kernels.hip (sail_noise.hip + sail_denoise.hip +
+  # sail_trace.hip), or the first two force-included in front of the source that stands in for sail_trace.hip
   src=sail_kernels.hip; pre=""
-  case "$flags" in src=*) src=${flags%% *}; src=${src#src=}; flags=${flags#src=$src}; pre="-include csrc/sail_noise.hip"; esac
+  case "$flags" in src=*) src=${flags%% *}; src=${src#src=}; flags=${flags#src=$src}; pre="-include csrc/sail_noise.hip -include csrc/sail_denoise.hip"; esac
   $HIPCC $COMMON $flags -Icsrc $pre -c csrc/$src -o build/variants/trace_$name.o
   $HIPCC -shared -fPIC --offload-arch=gfx950 build/variants/trace_$name.o build/variants/sail_capi.o \
     build/variants/sail_hostmath.o build/variants/sail_jit.o build/variants/sail_jit_src.o -o lib/variants/libsail_hip_$name.so -ldl
