@@ -192,7 +192,9 @@ static inline float pow_s(float x, float y) {  // display gamma only: f64 exp/lo
   if (x == 0.0f) return (y > 0.0f) ? 0.0f : INFINITY;
   return (float)exp_d((double)y * log_d((double)x));
 }
-static inline float exp_s(float x) { return (float)exp_d((double)x); }
+// (a NaN argument yields the default NaN, as in pow_s: passed through the two conversions instead, a signalling NaN
+// comes back quieted or as it was, depending on the compiler; tests/test_sanitizers.py compares two compilers' bits)
+static inline float exp_s(float x) { if (x != x) return NAN; return (float)exp_d((double)x); }
 static inline float log_s(float x) { return (float)log_d((double)x); }
 
 // GLSL builtins with defined NaN behaviour

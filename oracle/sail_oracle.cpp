@@ -1554,6 +1554,10 @@ void oracle_math(int fn, const float* x, const float* y, float* out, int count) 
       case 11: out[i] = refm::div_s(x[i], y[i]); break;  // GLSL divide spec
       case 14: out[i] = refm::rcp_s(x[i]); break;        // its reciprocal
       case 12: out[i] = refm::fmin_s(refm::fmax_s(x[i], 0.0f), 1.0f); break;
+      case 13: out[i] = refm::exp_s(x[i]); break;
+      case 16: { const int v = refm::to_int(x[i]); memcpy(&out[i], &v, sizeof v); break; }  // the int's 32 bits
+      case 17: out[i] = refm::fract_s(x[i]); break;
+      case 18: out[i] = refm::fmin_s(refm::fmax_s(x[i], -1.0f), 1.0f); break;
       default: out[i] = 0.0f; break;
     }
   }

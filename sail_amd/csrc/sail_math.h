@@ -181,10 +181,14 @@ SM_D float fmin_(float a, float b) { return __builtin_fminf(a, b); }
 SM_D float fmax_(float a, float b) { return __builtin_fmaxf(a, b); }
 // clamp = max then min. With the bounds (0, 1) or (-1, 1) that is exactly one v_med3_f32 (which the compiler
 // may also fold into the producing instruction's output clamp modifier): equal for every f32 x, NaN and signed
-// zeros included (tools/med3_probe.hip, all 2^32 inputs on an MI355X, profiles/r02_med3_probe.json)
+// zeros included (tools/med3_probe.hip, all 2^32 inputs on an MI355X, profiles/r02_med3_probe.json) -- for a quiet
+// NaN. A signalling NaN handed to v_med3_f32 as it is comes out as hi, not lo (measured: its min3 quiets the NaN in
+// the first min and the second then returns hi), so x is canonicalized first, as the compiler does for the operands of
+// v_min_f32 / v_max_f32: clamp(any NaN) = lo. The result of an arithmetic instruction is canonical
+// already and costs nothing; only a value that comes straight from memory pays one instruction.
 SM_D float clamp_(float x, float lo, float hi) {
   if (__builtin_constant_p(lo) && __builtin_constant_p(hi) && (lo == 0.0f || lo == -1.0f) && hi == 1.0f)
-    return __builtin_amdgcn_fmed3f(x, lo, hi);
+    return __builtin_amdgcn_fmed3f(__builtin_canonicalizef(x), lo, hi);
   return fmin_(fmax_(x, lo), hi);
 }
 SM_D float fract_(float x) { return x - floorf(x); }

@@ -2598,6 +2598,10 @@ extern "C" __global__ void sail_math_kernel(int fn, const float* x, const float*
     case 14: r = rcp_rn(x[i]); break;
     case 15: r = sqrt01(x[i]); break;  // callers guarantee [0, 1] or NaN
     case 12: r = clamp_(x[i], 0.0f, 1.0f); break;
+    case 13: r = expf_(x[i]); break;
+    case 16: r = __int_as_float(to_int(x[i])); break;  // the int's 32 bits, compared as such
+    case 17: r = fract_(x[i]); break;
+    case 18: r = clamp_(x[i], -1.0f, 1.0f); break;
     default: break;
   }
   out[i] = r;

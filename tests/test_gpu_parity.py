@@ -66,6 +66,9 @@ def _args(fn, rng, n):
 
 @pytest.mark.parametrize("fn", list(range(13)) + [14])
 def test_math_spec_bit_exact(gpu, fn):
+    """the middle of each function's domain, 2^18 arguments each; the class and range edges (the 2^20 and 1e15 limits of
+    the sin/cos/tan reduction, rcp_rn's wave-uniform range guard, powf_'s class branches and subnormal results, and the
+    functions not called here: expf_, to_int, fract_, clamp_(x, -1, 1)) live in tests/test_gpu_math_edges.py"""
     rng = np.random.default_rng(1000 + fn)
     x, y = _args(fn, rng, 1 << 18)
     x = np.asarray(x).astype(np.float32)

@@ -195,6 +195,38 @@ def test_spec_math_accuracy(fn, ref, lo, hi, tol):
         assert (np.abs(got - want) <= tol * ulp).all()
 
 
+def test_pow_exp_spec_accuracy():
+    """pow_s / exp_s evaluate exp and log in f64 and round once to f32: within 1 ulp of the exact value over normal f32
+    results (the f64 evaluation's error is far below the final rounding's half ulp). The GPU copy is held to the same bits
+    by tests/test_gpu_math_edges.py; this keeps both from being wrong together."""
+    rng = np.random.default_rng(55)
+    n = 100000
+    x = (10.0 ** rng.uniform(-6, 3, n)).astype(np.float32)
+    y = rng.uniform(-8, 8, n).astype(np.float32)
+    e = rng.uniform(-87, 88, n).astype(np.float32)
+    for what, got, want in (("pow", oracle.math(5, x, y), np.power(x.astype(np.float64), y.astype(np.float64))),
+                            ("exp", oracle.math(13, e), np.exp(e.astype(np.float64)))):
+        normal = (want >= 2.0 ** -126) & (want <= 3.4028234663852886e38)
+        assert normal.sum() > 0.9 * n
+        ulp = np.spacing(want[normal].astype(np.float32)).astype(np.float64)
+        err = np.abs(got.astype(np.float64) - want)[normal] / ulp
+        print(f"{what}_s: max error {err.max():.3f} ulp over {int(normal.sum())} normal results")
+        assert (err <= 1.0).all(), what
+
+
+@pytest.mark.parametrize("fn,ref", [(0, np.sin), (1, np.cos)])
+def test_sin_cos_f64_reduction_accuracy(fn, ref):
+    """2^20 <= |x| <= 1e9, the f64 three-term reduction: the absolute bound stated below 2^20 holds on. (Beyond 1e9 the
+    reduction degrades -- sin(1e14) is off by 4e-4 -- and bit equality with the GPU is the only bar.)"""
+    rng = np.random.default_rng(60 + fn)
+    x = np.exp(rng.uniform(np.log(2.0 ** 20), np.log(1e9), 100000)).astype(np.float32)
+    x = np.clip(x, np.float32(2.0 ** 20), np.float32(1e9)) * np.where(rng.random(x.size) < 0.5, -1, 1).astype(np.float32)
+    assert (np.abs(x) >= 2.0 ** 20).all() and (np.abs(x) <= 1e9).all() and (x < 0).any() and (np.abs(x) > 5e8).any()
+    err = np.abs(oracle.math(fn, x).astype(np.float64) - ref(x.astype(np.float64)))
+    print(f"fn {fn}: max absolute error {err.max():.3e}")
+    assert err.max() <= 2.0 ** -22
+
+
 def test_division_spec_within_glsl_bound():
     """GLSL division a / b := a * RN(1/b) (ref_math.h div_s): within 1.5 ulp of the exact quotient over normal
     results, inside GLSL ES 3.00's 2.5 ulp bound; RN(1/b) itself is the correctly rounded reciprocal"""
