@@ -264,6 +264,94 @@ int sail_denoise_defaults(sail_denoise_params* p);
 int sail_denoise(sail_ctx* ctx, const sail_denoise_params* p, float* out_rgba, float* out_var, uint8_t* out_rgba8,
                  sail_denoise_info* info);
 
+/* ---- camera-motion reprojection: a G-buffer pass and a temporal resolve (no reference counterpart: the reference resets
+ * its accumulation on every camera move, src/core/renderer.js:57-60; the temporal part of SVGF, Schied et al. 2017, for a
+ * still scene under a moving camera) ----
+ * The context keeps, beside the accumulator, five W x H float4 maps and two views (P*MV with each double rounded to f32,
+ * row-major, and the eye): G_cur and G_prev (world position and object row of each pixel's first hit for the current and
+ * the previous view), Hist (rgb mean, w = effective sample count m: the committed output of the previous view), R (Hist
+ * seen from the current view) and Out (the resolved picture of the current view). They are allocated by the first call
+ * below that needs them. Every operation is an f32 IEEE operation in the order written; min(a, b) is a < b ? a : b.
+ *
+ * G-buffer of a view (mvp, eye), pixel (x, y), row 0 = bottom:
+ *   d0..d3 = the corner directions a sample of zero jitter gets: cornerDirs(sail_jitter_inverse(mvp, 0, 0, W, H), eye), i.e.
+ *            for corner c = (-1,-1), (-1,1), (1,-1), (1,1): q = inv * (cx, cy, 0, 1) summed left to right,
+ *            w = q.xyz * (1/q.w) - eye, len = sqrt((w.x*w.x + w.y*w.y) + w.z*w.z), d_c = w * (1/len)
+ *   s = (x + 0.5) / W;  t = (y + 0.5) / H
+ *   d = s + t <= 1 ? (d0 + (d2 - d0)*s) + (d1 - d0)*t : (d3 + (d1 - d3)*(1 - s)) + (d2 - d3)*(1 - t);  o = eye
+ *   (id, dist) = sail_pick of the ray (o, d): the first row with the smallest distance, (-1, 1e5) on a miss
+ *   G = (o + d * dist, (float)id), each component a product and a sum;  a miss stores (0, 0, 0, -1)
+ *
+ * Reproject, pixel p of the current view, with Mp = the previous view's matrix, eye_prev its eye:
+ *   (X, id) = G_cur[p];  id < 0 -> R[p] = 0
+ *   c_i = ((Mp[i][0]*X.x + Mp[i][1]*X.y) + Mp[i][2]*X.z) + Mp[i][3]      i = 0, 1, 3
+ *   !(c_3 > 0) -> R[p] = 0
+ *   u = ((c_0 / c_3) * 0.5 + 0.5) * W - 0.5;   v likewise with c_1 and H;   u or v not finite -> R[p] = 0
+ *   iu = floor(u), fu = u - iu;  iv, fv likewise
+ *   r = X - eye_prev;  r2 = (r.x*r.x + r.y*r.y) + r.z*r.z;  lim = (pos_tol*pos_tol) * r2
+ *   taps b = 0, 1 (outer), a = 0, 1:  q = (iu + a, iv + b),  w = (a ? fu : 1 - fu) * (b ? fv : 1 - fv)
+ *     counted only if q is inside the frame (else never loaded), w > 0, G_prev[q].w == (float)id, Hist[q].w > 0,
+ *     Hist[q].rgb all finite, and with e = X - G_prev[q].xyz:  (e.x*e.x + e.y*e.y) + e.z*e.z <= lim
+ *     acc += w * Hist[q].rgb;  wsum += w;  m = min(m, Hist[q].w)      (m starts at +inf)
+ *   wsum > 0 ? R[p] = (acc / wsum, m) : R[p] = 0
+ *
+ * Resolve, pointwise, with S the accumulator the context shows and n, c0 as in sail_denoise (SUM: n = S.w,
+ * c0 = n > 0 ? S.rgb / n : 0; MIX: n = f32 of the sample index, c0 = S.rgb):
+ *   m = R.w;  hist = m > 0;  cur = n > 0 and c0.rgb all finite
+ *   hist and cur:  ws = m + n;  o = ((m * R.rgb) + (n * c0)) / ws;  mo = min(ws, cap)
+ *   hist only:     o = R.rgb;  mo = m
+ *   otherwise:     o = c0;     mo = min(n, cap)
+ *   Out[p] = (o, mo)
+ * so the history counts as at most `cap` samples: after a move it carries the picture, and as the still frame converges
+ * its weight goes to cap / (cap + n) and the output to the plain mean. out_rgba8 is the display transform of o
+ * (sail_filter's kinds 0..2) quantised as the filter kernel does, alpha 255.
+ *
+ * State rules: sail_set_scene and sail_update_objects drop all of it (ids and positions are stale); sail_reset,
+ * sail_load_accum, sail_set_accum_mode and sail_set_partition keep it. Queued samples are launched first. SAIL_E_INVALID,
+ * before anything else, for a cap that is not finite or < 1, a pos_tol that is not finite or <= 0 and a display outside
+ * kinds 0..2; SAIL_E_STATE for a resolve without a begin, no scene, SAIL_ACCUM_COMPAT8 and a half-loaded checkpoint. A
+ * multi-device context reduces first and works on device 0's frame and scene, like sail_filter. Nothing any other call can
+ * see changes: accumulator, AOVs, noise mark, sample index, stats. */
+typedef struct sail_temporal_params {
+  float cap;        /* the history counts as at most this many samples: finite, >= 1  [32]    */
+  float pos_tol;    /* a tap's position may differ by this share of its distance      [0.05]  */
+  int display;      /* SAIL_FILTER_COLOR | GAMMA | TONEMAPPING, for out_rgba8         [COLOR] */
+  float gamma_c;    /*                                                                [2.2]   */
+} sail_temporal_params;
+typedef struct sail_temporal_info {
+  uint64_t k;               /* the context's sample index */
+  uint64_t hit_pixels;      /* pixels of the current view that hit the scene */
+  uint64_t history_pixels;  /* pixels of the current view that found a history (R.w > 0) */
+  uint64_t nonfinite;       /* resolve: pixels whose c0 is not finite (begin: 0) */
+  double kernel_ms, pass_ms[3];  /* HIP events: the call's passes; [0] G-buffer, [1] reproject, [2] resolve */
+} sail_temporal_info;
+enum sail_temporal_map { SAIL_TEMPORAL_G_CUR = 0, SAIL_TEMPORAL_G_PREV = 1, SAIL_TEMPORAL_HIST = 2, SAIL_TEMPORAL_R = 3,
+                         SAIL_TEMPORAL_OUT = 4 };
+/* host only: the bracketed defaults */
+int sail_temporal_defaults(sail_temporal_params* p);
+/* The G-buffer pass for a view, into a scratch map; a public id and depth pass. Each output may be NULL: rays6 (W H 6 f32:
+ * origin, direction), id (W H int32), t (W H f32), xyz (W H 3 f32). Changes no temporal state. */
+int sail_gbuffer(sail_ctx* ctx, const double mvp_rowmajor[16], const float eye[3], float* rays6, int32_t* id, float* t,
+                 float* xyz);
+/* "The camera is now here." Launches the queued samples and synchronises. If a view is already current it is committed:
+ * Hist <- Out, G_prev <- G_cur, view_prev <- view_cur (pointer swaps). Then G_cur is computed for the new view, R from the
+ * history (R = 0 when there is none) and Out <- R, so a view that is never resolved hands the history through unchanged.
+ * p == NULL: the defaults; info may be NULL. A singular mvp: SAIL_E_INVALID, nothing committed. */
+int sail_temporal_begin(sail_ctx* ctx, const double mvp_rowmajor[16], const float eye[3], const sail_temporal_params* p,
+                        sail_temporal_info* info);
+/* Launches the queue, synchronises, resolves the shown accumulator with R into Out and copies back what is asked: out_rgba
+ * (W H 4 f32: (o, mo)), out_rgba8 (W H 4 bytes), info; each may be NULL. Calling it again on the same view, after more
+ * samples, blends again from the same R. */
+int sail_temporal_resolve(sail_ctx* ctx, const sail_temporal_params* p, float* out_rgba, uint8_t* out_rgba8,
+                          sail_temporal_info* info);
+/* copy one of the five maps (sail_temporal_map) into out (W H 4 f32). G_CUR, R and OUT need a current view, G_PREV and HIST
+ * a committed one: SAIL_E_STATE otherwise */
+int sail_temporal_read(sail_ctx* ctx, int which, float* out);
+/* install hist (W H 4 f32) and g (W H 4 f32) with their view as the committed history; no view is current afterwards, so
+ * the next sail_temporal_begin reprojects from exactly this. For tests and for a host that keeps its own history. */
+int sail_temporal_load_history(sail_ctx* ctx, const float* hist, const float* g, const double mvp_prev_rowmajor[16],
+                               const float eye_prev[3]);
+
 /* ---- checkpoint / resume of a progressive render (no reference counterpart: the reference restarts its
  * accumulation on every camera or object change, src/core/renderer.js:57-60, src/scene/scene.js:65-68) ----
  * A context's accumulation is `parts` raw accumulators (1 for sail_create, one per device for sail_create_multi),

@@ -50,6 +50,8 @@ EXPORTS = (
     "sail_plan_reduce", "sail_plan_keep", "sail_plan_load_part",
     "sail_noise_mark", "sail_noise_estimate", "sail_plan_until", "sail_render_until",
     "sail_denoise_defaults", "sail_denoise",
+    "sail_temporal_defaults", "sail_gbuffer", "sail_temporal_begin", "sail_temporal_resolve", "sail_temporal_read",
+    "sail_temporal_load_history",
 )
 
 
@@ -98,6 +100,18 @@ class DenoiseInfo(ctypes.Structure):
     _fields_ = [("k", ctypes.c_uint64), ("k_mark", ctypes.c_uint64), ("nonfinite", ctypes.c_uint64),
                 ("iterations", ctypes.c_int), ("kernel_ms", ctypes.c_double), ("pass_ms", ctypes.c_double * 8)]
 
+
+class TemporalParams(ctypes.Structure):
+    _fields_ = [("cap", ctypes.c_float), ("pos_tol", ctypes.c_float), ("display", ctypes.c_int), ("gamma_c", ctypes.c_float)]
+
+
+class TemporalInfo(ctypes.Structure):
+    _fields_ = [("k", ctypes.c_uint64), ("hit_pixels", ctypes.c_uint64), ("history_pixels", ctypes.c_uint64),
+                ("nonfinite", ctypes.c_uint64), ("kernel_ms", ctypes.c_double), ("pass_ms", ctypes.c_double * 3)]
+
+
+# sail_temporal_read's maps
+TEMPORAL_G_CUR, TEMPORAL_G_PREV, TEMPORAL_HIST, TEMPORAL_R, TEMPORAL_OUT = 0, 1, 2, 3, 4
 
 _SHAPES = {"cube": 1, "sphere": 2, "rectangle": 3, "cone": 4, "cylinder": 5, "disk": 6,
            "hyperboloid": 7, "paraboloid": 8, "cornellbox": 9}
@@ -193,6 +207,13 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
         "sail_denoise_defaults": (ctypes.c_int, [ctypes.POINTER(DenoiseParams)]),
         "sail_denoise": (ctypes.c_int, [vp, ctypes.POINTER(DenoiseParams), f32p, f32p, ctypes.POINTER(ctypes.c_uint8),
                                         ctypes.POINTER(DenoiseInfo)]),
+        "sail_temporal_defaults": (ctypes.c_int, [ctypes.POINTER(TemporalParams)]),
+        "sail_gbuffer": (ctypes.c_int, [vp, f64p, f32p, f32p, ctypes.POINTER(ctypes.c_int32), f32p, f32p]),
+        "sail_temporal_begin": (ctypes.c_int, [vp, f64p, f32p, ctypes.POINTER(TemporalParams), ctypes.POINTER(TemporalInfo)]),
+        "sail_temporal_resolve": (ctypes.c_int, [vp, ctypes.POINTER(TemporalParams), f32p, ctypes.POINTER(ctypes.c_uint8),
+                                                 ctypes.POINTER(TemporalInfo)]),
+        "sail_temporal_read": (ctypes.c_int, [vp, ctypes.c_int, f32p]),
+        "sail_temporal_load_history": (ctypes.c_int, [vp, f32p, f32p, f64p, f32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -331,6 +352,32 @@ def denoise_defaults() -> dict:
         raise SailError(f"sail_denoise_defaults: {rc}")
     return {"iterations": p.iterations, "sigma_l": p.sigma_l, "sigma_x": p.sigma_x, "display": p.display,
             "gamma_c": p.gamma_c}
+
+
+def temporal_defaults() -> dict:
+    """The temporal resolve's default parameters (sail_temporal_defaults, host-only): cap, pos_tol, display, gamma_c."""
+    lib = load()
+    p = TemporalParams()
+    rc = lib.sail_temporal_defaults(ctypes.byref(p))
+    if rc:
+        raise SailError(f"sail_temporal_defaults: {rc}")
+    return {"cap": p.cap, "pos_tol": p.pos_tol, "display": p.display, "gamma_c": p.gamma_c}
+
+
+def _temporal_params(params: Optional[dict], who: str):
+    if params is None:
+        return None
+    d = temporal_defaults()
+    unknown = set(params) - set(d)
+    if unknown:
+        raise SailError(f"{who}: unknown parameters {sorted(unknown)}")
+    d.update(params)
+    return TemporalParams(float(d["cap"]), float(d["pos_tol"]), int(d["display"]), float(d["gamma_c"]))
+
+
+def _temporal_dict(i: TemporalInfo) -> dict:
+    return {"k": int(i.k), "hit_pixels": int(i.hit_pixels), "history_pixels": int(i.history_pixels),
+            "nonfinite": int(i.nonfinite), "kernel_ms": i.kernel_ms, "pass_ms": [i.pass_ms[j] for j in range(3)]}
 
 
 def prim_bounds(objects, n: int, tn: int) -> np.ndarray:
@@ -584,6 +631,69 @@ class Context:
         if want_u8:
             out["u8"] = u8
         return out
+
+    def gbuffer(self, mvp, eye, rays: bool = False) -> dict:
+        """The G-buffer pass for a view (sail_gbuffer): "id" (H, W) int32 object row of the first hit or -1, "t" (H, W)
+        its distance (1e5 on a miss), "xyz" (H, W, 3) its world position (0 on a miss), with `rays` "rays" (H, W, 6) the
+        pixels' origin and direction. Changes no temporal state."""
+        m = np.ascontiguousarray(np.asarray(mvp, dtype=np.float64).reshape(16))
+        e = _f32(eye)
+        r = np.zeros((self.H, self.W, 6), dtype=np.float32) if rays else None
+        idx = np.zeros((self.H, self.W), dtype=np.int32)
+        t = np.zeros((self.H, self.W), dtype=np.float32)
+        xyz = np.zeros((self.H, self.W, 3), dtype=np.float32)
+        self._check(self.lib.sail_gbuffer(self.h, _ptr(m, ctypes.c_double), _ptr(e), _ptr(r), _ptr(idx, ctypes.c_int32),
+                                          _ptr(t), _ptr(xyz)), "sail_gbuffer")
+        out = {"id": idx, "t": t, "xyz": xyz}
+        if rays:
+            out["rays"] = r
+        return out
+
+    def temporal_begin(self, mvp, eye, params: Optional[dict] = None) -> dict:
+        """The camera is now at this view (sail_temporal_begin): commits the view that was current, computes the new
+        view's G-buffer and reprojects the history into it. `params` overrides entries of temporal_defaults(). Returns
+        k, hit_pixels, history_pixels, nonfinite, kernel_ms and pass_ms (G-buffer, reproject, resolve)."""
+        m = np.ascontiguousarray(np.asarray(mvp, dtype=np.float64).reshape(16))
+        e = _f32(eye)
+        p = _temporal_params(params, "temporal_begin")
+        info = TemporalInfo()
+        self._check(self.lib.sail_temporal_begin(self.h, _ptr(m, ctypes.c_double), _ptr(e),
+                                                 ctypes.byref(p) if p is not None else None, ctypes.byref(info)),
+                    "sail_temporal_begin")
+        return _temporal_dict(info)
+
+    def temporal_resolve(self, params: Optional[dict] = None, want_u8: bool = False) -> dict:
+        """Blend the reprojected history with the samples of the current view (sail_temporal_resolve). Returns "rgba"
+        (H, W, 4) f32: the resolved colour and its effective sample count, with want_u8 "u8" (H, W, 4) uint8 (the
+        display transform), and the fields of temporal_begin."""
+        p = _temporal_params(params, "temporal_resolve")
+        info = TemporalInfo()
+        rgba = np.zeros((self.H, self.W, 4), dtype=np.float32)
+        u8 = np.zeros((self.H, self.W, 4), dtype=np.uint8) if want_u8 else None
+        self._check(self.lib.sail_temporal_resolve(self.h, ctypes.byref(p) if p is not None else None, _ptr(rgba),
+                                                   _ptr(u8, ctypes.c_uint8), ctypes.byref(info)), "sail_temporal_resolve")
+        out = _temporal_dict(info)
+        out["rgba"] = rgba
+        if want_u8:
+            out["u8"] = u8
+        return out
+
+    def temporal_read(self, which: int) -> np.ndarray:
+        """One of the five temporal maps (TEMPORAL_G_CUR .. TEMPORAL_OUT) as (H, W, 4) f32 (sail_temporal_read)."""
+        out = np.zeros((self.H, self.W, 4), dtype=np.float32)
+        self._check(self.lib.sail_temporal_read(self.h, int(which), _ptr(out)), "sail_temporal_read")
+        return out
+
+    def temporal_load_history(self, hist, g, mvp_prev, eye_prev):
+        """Install a history (H, W, 4: rgb mean, sample count), its G-buffer (H, W, 4: position, object row) and its
+        view as the committed one (sail_temporal_load_history)."""
+        h, gg = _f32(hist), _f32(g)
+        if h.shape != (self.H, self.W, 4) or gg.shape != (self.H, self.W, 4):
+            raise SailError(f"temporal_load_history: maps must have shape {(self.H, self.W, 4)}")
+        m = np.ascontiguousarray(np.asarray(mvp_prev, dtype=np.float64).reshape(16))
+        e = _f32(eye_prev)
+        self._check(self.lib.sail_temporal_load_history(self.h, _ptr(h), _ptr(gg), _ptr(m, ctypes.c_double), _ptr(e)),
+                    "sail_temporal_load_history")
 
     def filter_ms(self) -> float:
         v = ctypes.c_double()

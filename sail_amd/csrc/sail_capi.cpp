@@ -33,6 +33,11 @@ hipError_t sail_launch_noise(const SailNoiseArgs& A, hipStream_t s);
 #include "sail_denoise.h"
 hipError_t sail_launch_denoise_prepare(const SailDenoisePrepareArgs& A, hipStream_t s);
 hipError_t sail_launch_denoise_atrous(const SailDenoiseAtrousArgs& A, hipStream_t s);
+// sail_temporal.hip: the G-buffer, reproject and temporal resolve passes
+#include "sail_temporal.h"
+hipError_t sail_launch_gbuffer(const SailGbufferArgs& A, hipStream_t s);
+hipError_t sail_launch_reproject(const SailReprojectArgs& A, hipStream_t s);
+hipError_t sail_launch_temporal_resolve(const SailResolveArgs& A, hipStream_t s);
 
 namespace {
 
@@ -197,6 +202,15 @@ struct sail_ctx {
   // Denoiser (sail_denoise): one block of work buffers, allocated on first use: two (c, v) float4 maps, the guides as a
   // float4 and a float2 map, the variance map, the RGBA8 map and the per-tile non-finite counts
   void* denoiseWork = nullptr;
+  // Camera-motion reprojection (sail_temporal_*): one block, allocated on first use, holding the five float4 maps, the
+  // RGBA8 map and three counts per 16x16 tile; the map pointers are swapped when a view is committed. tpHaveCur: a view
+  // is current (G_cur, R and Out are its); tpHavePrev: a history is committed (G_prev, Hist and tpPrev are its).
+  // sail_set_scene and sail_update_objects drop both. On a multi-device context device 0's sub-context holds it.
+  void* tpWork = nullptr;
+  float4 *tpGcur = nullptr, *tpGprev = nullptr, *tpHist = nullptr, *tpR = nullptr, *tpOut = nullptr;
+  bool tpHaveCur = false, tpHavePrev = false;
+  struct TpView { float m[16]; float eye[3]; } tpCur{}, tpPrev{};
+  uint64_t tpHitPixels = 0;
   nccl_comm_t comm = nullptr;
   int commRanks = 0, commRank = 0;
   // Reduced frame (root of sail_reduce / device 0 of a multi-device context): the sum of every rank's
@@ -1205,7 +1219,7 @@ void sail_destroy(sail_ctx* c) {
   for (auto& pr : c->pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
   for (auto e : c->evPool) (void)hipEventDestroy(e);
   void* bufs[] = {c->accum, c->frame, c->frameN, c->frameP, c->aovN, c->aovP, c->filterOut, c->filterOut8, c->stage, c->segCounter, c->prims, c->tp, c->lt, c->lightObjRow, c->samples, c->wf,
-                  c->noiseMark, c->noiseOut, c->noisePix, c->denoiseWork};
+                  c->noiseMark, c->noiseOut, c->noisePix, c->denoiseWork, c->tpWork};
   for (void* b : bufs) if (b) (void)hipFree(b);
   if (c->samplesPinned) (void)hipHostFree(c->samplesPinned);
   if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1390,6 +1404,7 @@ int sail_set_scene(sail_ctx* c, const float* objects, int n, const float* texpar
   c->tpRows.assign(texparams, texparams + (size_t)tn * 16);
   c->n = n; c->tn = tn; c->ln = ln;
   c->haveScene = true;
+  c->tpHaveCur = c->tpHavePrev = false;  // the temporal maps' ids and positions are stale
   // Tracer.update links the scene's program (tracer.js:42-90): the plugin set's kernel starts building now, in the
   // background; the precompiled kernel of the set serves until it is loaded
   refreshJit(c);
@@ -1416,6 +1431,7 @@ int sail_update_objects(sail_ctx* c, const float* objects, int n) {
   if (int rc = uploadPrims(c, prims)) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->objectsRows.assign(objects, objects + (size_t)n * 18);
+  c->tpHaveCur = c->tpHavePrev = false;  // the temporal maps' ids and positions are stale
   refreshJit(c);  // a drag keeps the kernel; a changed shape type starts the new rows' kernel building
   return resetAccum(c);
 }
@@ -2002,6 +2018,267 @@ int sail_denoise(sail_ctx* c, const sail_denoise_params* params, float* out_rgba
     info->kernel_ms = total;
     for (int i = 0; i + 1 < nev; i++) info->pass_ms[i] = ms[i];
   }
+  return SAIL_OK;
+}
+
+// ---- camera-motion reprojection (include/sail_hip.h; the kernels are sail_temporal.hip) ---------------------------------------
+int sail_temporal_defaults(sail_temporal_params* p) {
+  if (!p) return SAIL_E_INVALID;
+  p->cap = 32.0f;
+  p->pos_tol = 0.05f;
+  p->display = SAIL_FILTER_COLOR;
+  p->gamma_c = 2.2f;
+  return SAIL_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+int temporalParams(sail_ctx* c, const char* who, const sail_temporal_params* params, sail_temporal_params* p) {
+  sail_temporal_defaults(p);
+  if (params) *p = *params;
+  if (!std::isfinite(p->cap) || p->cap < 1.0f || !std::isfinite(p->pos_tol) || !(p->pos_tol > 0.0f) ||
+      p->display < SAIL_FILTER_COLOR || p->display > SAIL_FILTER_TONEMAPPING)
+    return fail(c, SAIL_E_INVALID, "%s: bad parameters (cap %g finite and >= 1, pos_tol %g finite and > 0, display %d of 0..2)",
+                who, (double)p->cap, (double)p->pos_tol, p->display);
+  return SAIL_OK;
+}
+
+// what every temporal call refuses on one device's context
+int temporalState(sail_ctx* c, const char* who) {
+  if (!c->haveScene) return fail(c, SAIL_E_STATE, "%s: no scene (call sail_set_scene first)", who);
+  if (c->accumMode == SAIL_ACCUM_COMPAT8)
+    return fail(c, SAIL_E_STATE, "%s: SAIL_ACCUM_COMPAT8 stores 8-bit frames, which carry no sample count to blend with", who);
+  return SAIL_OK;
+}
+
+size_t temporalTiles(const sail_ctx* c) { return (size_t)((c->W + 15) / 16) * (size_t)((c->H + 15) / 16); }
+uint32_t* temporalOut8(const sail_ctx* c) { return (uint32_t*)((char*)c->tpWork + (size_t)c->W * c->H * 80); }
+uint32_t* temporalCounts(const sail_ctx* c) { return temporalOut8(c) + (size_t)c->W * c->H; }
+
+int ensureTemporal(sail_ctx* c) {
+  if (c->tpWork) return SAIL_OK;
+  const size_t np = (size_t)c->W * c->H;
+  // five float4 maps (16 B each) | rgba8 (4 B) per pixel, then three counts per tile
+  if (hipMalloc(&c->tpWork, np * 84 + temporalTiles(c) * 12) != hipSuccess) {
+    c->tpWork = nullptr;
+    return fail(c, SAIL_E_OOM, "temporal maps");
+  }
+  float4* base = (float4*)c->tpWork;
+  c->tpGcur = base; c->tpGprev = base + np; c->tpHist = base + 2 * np; c->tpR = base + 3 * np; c->tpOut = base + 4 * np;
+  return SAIL_OK;
+}
+
+// the G-buffer pass's arguments for a view: the corner directions of a sample without jitter
+int gbufferArgs(sail_ctx* c, const char* who, const double mvp[16], const float eye[3], SailGbufferArgs* A) {
+  float inv[16];
+  if (sail_jitter_inverse(mvp, 0.0, 0.0, c->W, c->H, inv) != SAIL_OK)
+    return fail(c, SAIL_E_INVALID, "%s: the camera matrix is singular", who);
+  memset(A, 0, sizeof *A);
+  A->prims = c->prims; A->n = c->n;
+  cornerDirs(inv, eye, A->d);
+  memcpy(A->eye, eye, sizeof A->eye);
+  A->W = c->W; A->H = c->H;
+  return SAIL_OK;
+}
+
+uint64_t sumTiles(const std::vector<uint32_t>& v, size_t from, size_t count) {
+  uint64_t s = 0;
+  for (size_t i = 0; i < count; i++) s += v[from + i];
+  return s;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sail_gbuffer(sail_ctx* c, const double mvp[16], const float eye[3], float* rays6, int32_t* id, float* t, float* xyz) {
+  if (!c) return SAIL_E_INVALID;
+  if (!mvp || !eye) return fail(c, SAIL_E_INVALID, "sail_gbuffer: mvp and eye are required");
+  if (!c->subs.empty()) return relay(c, sail_gbuffer(c->subs[0], mvp, eye, rays6, id, t, xyz), c->subs[0]);
+  if (!c->haveScene) return fail(c, SAIL_E_STATE, "sail_gbuffer: no scene (call sail_set_scene first)");
+  SailGbufferArgs A;
+  if (int rc = gbufferArgs(c, "sail_gbuffer", mvp, eye, &A)) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = sail_sync(c)) return rc;
+  const size_t np = (size_t)c->W * c->H;
+  void* work = nullptr;  // G (16 B) | rays (24 B) | t (4 B) per pixel
+  if (hipMalloc(&work, np * 44) != hipSuccess) return fail(c, SAIL_E_OOM, "G-buffer scratch");
+  A.G = (float4*)work;
+  A.rays = rays6 ? (float*)((char*)work + np * 16) : nullptr;
+  A.t = t ? (float*)((char*)work + np * 40) : nullptr;
+  std::vector<float> g((id || xyz) ? np * 4 : 0);
+  hipError_t e = sail_launch_gbuffer(A, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e == hipSuccess && !g.empty()) e = hipMemcpy(g.data(), A.G, np * 16, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && rays6) e = hipMemcpy(rays6, A.rays, np * 24, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && t) e = hipMemcpy(t, A.t, np * 4, hipMemcpyDeviceToHost);
+  (void)hipFree(work);
+  if (e != hipSuccess) return fail(c, SAIL_E_HIP, "sail_gbuffer: %s", hipGetErrorString(e));
+  for (size_t i = 0; i < np && !g.empty(); i++) {
+    if (id) id[i] = (int32_t)g[4 * i + 3];
+    if (xyz) { xyz[3 * i] = g[4 * i]; xyz[3 * i + 1] = g[4 * i + 1]; xyz[3 * i + 2] = g[4 * i + 2]; }
+  }
+  return SAIL_OK;
+}
+
+int sail_temporal_begin(sail_ctx* c, const double mvp[16], const float eye[3], const sail_temporal_params* params,
+                        sail_temporal_info* info) {
+  if (!c) return SAIL_E_INVALID;
+  sail_temporal_params p;
+  if (int rc = temporalParams(c, "sail_temporal_begin", params, &p)) return rc;
+  if (!mvp || !eye) return fail(c, SAIL_E_INVALID, "sail_temporal_begin: mvp and eye are required");
+  if (!c->subs.empty()) {  // device 0's reduced frame and scene, like sail_filter
+    if (int rc = loadIncomplete(c, "sail_temporal_begin")) return rc;
+    if (int rc = groupReduce(c)) return rc;
+    return relay(c, sail_temporal_begin(c->subs[0], mvp, eye, &p, info), c->subs[0]);
+  }
+  if (int rc = temporalState(c, "sail_temporal_begin")) return rc;
+  SailGbufferArgs A;
+  if (int rc = gbufferArgs(c, "sail_temporal_begin", mvp, eye, &A)) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = sail_sync(c)) return rc;
+  if (int rc = ensureTemporal(c)) return rc;
+  if (c->tpHaveCur) {  // commit the view that was current
+    std::swap(c->tpHist, c->tpOut);
+    std::swap(c->tpGprev, c->tpGcur);
+    c->tpPrev = c->tpCur;
+    c->tpHavePrev = true;
+    c->tpHaveCur = false;
+  }
+  const size_t nt = temporalTiles(c), np = (size_t)c->W * c->H;
+  uint32_t* cnt = temporalCounts(c);
+  A.G = c->tpGcur;
+  SailReprojectArgs B;
+  memset(&B, 0, sizeof B);
+  B.Gcur = c->tpGcur; B.Gprev = c->tpGprev; B.Hist = c->tpHist; B.R = c->tpR;
+  B.tileHit = cnt; B.tileHist = cnt + nt;
+  for (int j = 0; j < 4; j++) { B.Mp[0][j] = c->tpPrev.m[j]; B.Mp[1][j] = c->tpPrev.m[4 + j]; B.Mp[2][j] = c->tpPrev.m[12 + j]; }
+  memcpy(B.eyePrev, c->tpPrev.eye, sizeof B.eyePrev);
+  B.tol2 = p.pos_tol * p.pos_tol;
+  B.W = c->W; B.H = c->H;
+  B.haveHist = c->tpHavePrev;
+  hipEvent_t ev[3] = {};
+  for (int i = 0; i < 3; i++)
+    if (int rc = getEvent(c, &ev[i])) {
+      for (int j = 0; j < i; j++) c->evPool.push_back(ev[j]);
+      return rc;
+    }
+  hipError_t e = hipEventRecord(ev[0], c->stream);
+  if (e == hipSuccess) e = sail_launch_gbuffer(A, c->stream);
+  if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
+  if (e == hipSuccess) e = sail_launch_reproject(B, c->stream);
+  if (e == hipSuccess) e = hipEventRecord(ev[2], c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(c->tpOut, c->tpR, np * 16, hipMemcpyDeviceToDevice, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  float ms[2] = {};
+  for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]);
+  for (int i = 0; i < 3; i++) c->evPool.push_back(ev[i]);
+  std::vector<uint32_t> host(nt * 2);
+  if (e == hipSuccess) e = hipMemcpy(host.data(), cnt, nt * 8, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(c, SAIL_E_HIP, "sail_temporal_begin: %s", hipGetErrorString(e));
+  for (int i = 0; i < 16; i++) c->tpCur.m[i] = (float)mvp[i];
+  memcpy(c->tpCur.eye, eye, sizeof c->tpCur.eye);
+  c->tpHaveCur = true;
+  c->tpHitPixels = sumTiles(host, 0, nt);
+  if (info) {
+    memset(info, 0, sizeof *info);
+    info->k = c->k;
+    info->hit_pixels = c->tpHitPixels;
+    info->history_pixels = sumTiles(host, nt, nt);
+    info->kernel_ms = (double)ms[0] + (double)ms[1];
+    info->pass_ms[0] = ms[0]; info->pass_ms[1] = ms[1];
+  }
+  return SAIL_OK;
+}
+
+int sail_temporal_resolve(sail_ctx* c, const sail_temporal_params* params, float* out_rgba, uint8_t* out_rgba8,
+                          sail_temporal_info* info) {
+  if (!c) return SAIL_E_INVALID;
+  sail_temporal_params p;
+  if (int rc = temporalParams(c, "sail_temporal_resolve", params, &p)) return rc;
+  if (!c->subs.empty()) {
+    if (int rc = loadIncomplete(c, "sail_temporal_resolve")) return rc;
+    if (int rc = groupReduce(c)) return rc;
+    return relay(c, sail_temporal_resolve(c->subs[0], &p, out_rgba, out_rgba8, info), c->subs[0]);
+  }
+  if (int rc = temporalState(c, "sail_temporal_resolve")) return rc;
+  if (!c->tpHaveCur || !c->tpWork)
+    return fail(c, SAIL_E_STATE, "sail_temporal_resolve: no current view (sail_temporal_begin first; a new scene drops it)");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = sail_sync(c)) return rc;
+  const size_t nt = temporalTiles(c), np = (size_t)c->W * c->H;
+  uint32_t* cnt = temporalCounts(c);
+  SailResolveArgs A;
+  memset(&A, 0, sizeof A);
+  A.S = shownAccum(c); A.R = c->tpR; A.Out = c->tpOut;
+  A.out8 = out_rgba8 ? temporalOut8(c) : nullptr;
+  A.tileHist = cnt + nt; A.tileBad = cnt + 2 * nt;
+  A.W = c->W; A.H = c->H;
+  A.mix = c->accumMode == SAIL_ACCUM_MIX;
+  A.kf = (float)c->k;
+  A.cap = p.cap; A.display = p.display; A.gammaC = p.gamma_c;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (int rc = getEvent(c, &e0)) return rc;
+  if (int rc = getEvent(c, &e1)) { c->evPool.push_back(e0); return rc; }
+  float ms = 0.0f;
+  hipError_t e = hipEventRecord(e0, c->stream);
+  if (e == hipSuccess) e = sail_launch_temporal_resolve(A, c->stream);
+  if (e == hipSuccess) e = hipEventRecord(e1, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+  c->evPool.push_back(e0);
+  c->evPool.push_back(e1);
+  std::vector<uint32_t> host(nt * 2);
+  if (e == hipSuccess) e = hipMemcpy(host.data(), cnt + nt, nt * 8, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && out_rgba) e = hipMemcpy(out_rgba, c->tpOut, np * 16, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && out_rgba8) e = hipMemcpy(out_rgba8, A.out8, np * 4, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(c, SAIL_E_HIP, "sail_temporal_resolve: %s", hipGetErrorString(e));
+  if (info) {
+    memset(info, 0, sizeof *info);
+    info->k = c->k;
+    info->hit_pixels = c->tpHitPixels;
+    info->history_pixels = sumTiles(host, 0, nt);
+    info->nonfinite = sumTiles(host, nt, nt);
+    info->kernel_ms = ms;
+    info->pass_ms[2] = ms;
+  }
+  return SAIL_OK;
+}
+
+int sail_temporal_read(sail_ctx* c, int which, float* out) {
+  if (!c) return SAIL_E_INVALID;
+  if (!out || which < SAIL_TEMPORAL_G_CUR || which > SAIL_TEMPORAL_OUT)
+    return fail(c, SAIL_E_INVALID, "sail_temporal_read: map %d of 0..4 and an output are required", which);
+  if (!c->subs.empty()) return relay(c, sail_temporal_read(c->subs[0], which, out), c->subs[0]);
+  const bool prev = which == SAIL_TEMPORAL_G_PREV || which == SAIL_TEMPORAL_HIST;
+  if (!c->tpWork || !(prev ? c->tpHavePrev : c->tpHaveCur))
+    return fail(c, SAIL_E_STATE, "sail_temporal_read: map %d needs a %s view (a new scene drops both)", which,
+                prev ? "committed" : "current");
+  const float4* maps[5] = {c->tpGcur, c->tpGprev, c->tpHist, c->tpR, c->tpOut};
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(out, maps[which], (size_t)c->W * c->H * 16, hipMemcpyDeviceToHost));
+  return SAIL_OK;
+}
+
+int sail_temporal_load_history(sail_ctx* c, const float* hist, const float* g, const double mvp_prev[16],
+                               const float eye_prev[3]) {
+  if (!c) return SAIL_E_INVALID;
+  if (!hist || !g || !mvp_prev || !eye_prev)
+    return fail(c, SAIL_E_INVALID, "sail_temporal_load_history: hist, g, mvp_prev and eye_prev are required");
+  if (!c->subs.empty()) return relay(c, sail_temporal_load_history(c->subs[0], hist, g, mvp_prev, eye_prev), c->subs[0]);
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (int rc = ensureTemporal(c)) return rc;
+  const size_t bytes = (size_t)c->W * c->H * 16;
+  HIPCHK(c, hipMemcpy(c->tpHist, hist, bytes, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->tpGprev, g, bytes, hipMemcpyHostToDevice));
+  for (int i = 0; i < 16; i++) c->tpPrev.m[i] = (float)mvp_prev[i];
+  memcpy(c->tpPrev.eye, eye_prev, sizeof c->tpPrev.eye);
+  c->tpHavePrev = true;
+  c->tpHaveCur = false;
   return SAIL_OK;
 }
 

@@ -506,6 +506,135 @@ napi_value Denoise(napi_env env, napi_callback_info info) {
   NAPI_OK(napi_set_named_property(env, out, "info", inf));
   return out;
 }
+// ---- camera-motion reprojection (sail_gbuffer, sail_temporal_*) ----
+namespace {
+bool viewArgs(napi_env env, napi_value mvp, napi_value eye, double** m, float** e) {
+  size_t nm, ne;
+  if (!getArray(env, mvp, napi_float64_array, m, &nm) || !getArray(env, eye, napi_float32_array, e, &ne)) return false;
+  if (nm < 16 || ne < 3) { napi_throw_range_error(env, nullptr, "mvp needs 16 doubles and eye 3 floats"); return false; }
+  return true;
+}
+// cap, posTol, display, gamma from four values; undefined or null keeps sail_temporal_defaults' value
+bool temporalParams(napi_env env, const napi_value* a, sail_temporal_params* p) {
+  sail_temporal_defaults(p);
+  double v[4] = {p->cap, p->pos_tol, (double)p->display, p->gamma_c};
+  for (int i = 0; i < 4; i++) {
+    napi_valuetype vt;
+    napi_typeof(env, a[i], &vt);
+    if (vt == napi_undefined || vt == napi_null) continue;
+    if (!getDouble(env, a[i], &v[i])) return false;
+  }
+  if (v[2] != (double)(int)v[2]) { napi_throw_range_error(env, nullptr, "display must be an integer"); return false; }
+  p->cap = (float)v[0]; p->pos_tol = (float)v[1]; p->display = (int)v[2]; p->gamma_c = (float)v[3];
+  return true;
+}
+napi_value temporalObject(napi_env env, const sail_temporal_info& n) {
+  napi_value out, passes;
+  NAPI_OK(napi_create_object(env, &out));
+  napi_set_named_property(env, out, "k", num(env, (double)n.k));
+  napi_set_named_property(env, out, "hitPixels", num(env, (double)n.hit_pixels));
+  napi_set_named_property(env, out, "historyPixels", num(env, (double)n.history_pixels));
+  napi_set_named_property(env, out, "nonfinite", num(env, (double)n.nonfinite));
+  napi_set_named_property(env, out, "kernelMs", num(env, n.kernel_ms));
+  NAPI_OK(napi_create_array_with_length(env, 3, &passes));
+  for (int i = 0; i < 3; i++) napi_set_element(env, passes, (uint32_t)i, num(env, n.pass_ms[i]));
+  NAPI_OK(napi_set_named_property(env, out, "passMs", passes));
+  return out;
+}
+}  // namespace
+// (ctx, mvp f64[16] row-major, eye f32[3]) -> {id: Int32Array, t: Float32Array, xyz: Float32Array (3 per pixel)}
+napi_value Gbuffer(napi_env env, napi_callback_info info) {
+  napi_value a[3];
+  if (!args(env, info, 3, a)) return nullptr;
+  Handle* h;
+  double* m;
+  float* eye;
+  if (!getHandle(env, a[0], &h) || !viewArgs(env, a[1], a[2], &m, &eye)) return nullptr;
+  const size_t np = (size_t)h->W * h->H;
+  void *pi = nullptr, *pt = nullptr, *px = nullptr;
+  napi_value id = makeTyped(env, napi_int32_array, np, 4, &pi), t = makeTyped(env, napi_float32_array, np, 4, &pt),
+             xyz = makeTyped(env, napi_float32_array, np * 3, 4, &px);
+  const int rc = sail_gbuffer(h->ctx, m, eye, nullptr, (int32_t*)pi, (float*)pt, (float*)px);
+  if (rc) return throwSail(env, "sail_gbuffer", rc, h->ctx);
+  napi_value out;
+  NAPI_OK(napi_create_object(env, &out));
+  NAPI_OK(napi_set_named_property(env, out, "id", id));
+  NAPI_OK(napi_set_named_property(env, out, "t", t));
+  NAPI_OK(napi_set_named_property(env, out, "xyz", xyz));
+  return out;
+}
+// (ctx, mvp, eye, cap, posTol) -> {k, hitPixels, historyPixels, nonfinite, kernelMs, passMs}
+napi_value TemporalBegin(napi_env env, napi_callback_info info) {
+  napi_value a[5];
+  if (!args(env, info, 5, a)) return nullptr;
+  Handle* h;
+  double* m;
+  float* eye;
+  if (!getHandle(env, a[0], &h) || !viewArgs(env, a[1], a[2], &m, &eye)) return nullptr;
+  const napi_value none = undef(env);
+  const napi_value pv[4] = {a[3], a[4], none, none};
+  sail_temporal_params p;
+  if (!temporalParams(env, pv, &p)) return nullptr;
+  sail_temporal_info n;
+  const int rc = sail_temporal_begin(h->ctx, m, eye, &p, &n);
+  if (rc) return throwSail(env, "sail_temporal_begin", rc, h->ctx);
+  return temporalObject(env, n);
+}
+// (ctx, cap, posTol, display, gamma, wantF32) -> {rgba8, rgba?, info}
+napi_value TemporalResolve(napi_env env, napi_callback_info info) {
+  napi_value a[6];
+  if (!args(env, info, 6, a)) return nullptr;
+  Handle* h;
+  if (!getHandle(env, a[0], &h)) return nullptr;
+  sail_temporal_params p;
+  if (!temporalParams(env, a + 1, &p)) return nullptr;
+  bool wantF32 = false;
+  napi_get_value_bool(env, a[5], &wantF32);
+  const size_t np = (size_t)h->W * h->H * 4;
+  void *pf = nullptr, *p8 = nullptr;
+  napi_value u8 = makeTyped(env, napi_uint8_array, np, 1, &p8), f = nullptr;
+  if (wantF32) f = makeTyped(env, napi_float32_array, np, 4, &pf);
+  sail_temporal_info n;
+  const int rc = sail_temporal_resolve(h->ctx, &p, (float*)pf, (uint8_t*)p8, &n);
+  if (rc) return throwSail(env, "sail_temporal_resolve", rc, h->ctx);
+  napi_value out, inf = temporalObject(env, n);
+  if (!inf) return nullptr;
+  NAPI_OK(napi_create_object(env, &out));
+  NAPI_OK(napi_set_named_property(env, out, "rgba8", u8));
+  if (wantF32) NAPI_OK(napi_set_named_property(env, out, "rgba", f));
+  NAPI_OK(napi_set_named_property(env, out, "info", inf));
+  return out;
+}
+// (ctx, which 0..4) -> Float32Array (4 per pixel): G_cur, G_prev, Hist, R or Out
+napi_value TemporalRead(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  if (!args(env, info, 2, a)) return nullptr;
+  Handle* h;
+  int which = 0;
+  if (!getHandle(env, a[0], &h) || !getInt(env, a[1], &which)) return nullptr;
+  void* pf = nullptr;
+  napi_value f = makeTyped(env, napi_float32_array, (size_t)h->W * h->H * 4, 4, &pf);
+  const int rc = sail_temporal_read(h->ctx, which, (float*)pf);
+  if (rc) return throwSail(env, "sail_temporal_read", rc, h->ctx);
+  return f;
+}
+// (ctx, hist f32[W H 4], g f32[W H 4], mvpPrev, eyePrev)
+napi_value TemporalLoadHistory(napi_env env, napi_callback_info info) {
+  napi_value a[5];
+  if (!args(env, info, 5, a)) return nullptr;
+  Handle* h;
+  float *hist, *g, *eye;
+  double* m;
+  size_t nh, ng;
+  if (!getHandle(env, a[0], &h) || !getArray(env, a[1], napi_float32_array, &hist, &nh) ||
+      !getArray(env, a[2], napi_float32_array, &g, &ng) || !viewArgs(env, a[3], a[4], &m, &eye))
+    return nullptr;
+  const size_t need = (size_t)h->W * h->H * 4;
+  if (nh < need || ng < need) { napi_throw_range_error(env, nullptr, "hist and g need width * height * 4 floats"); return nullptr; }
+  const int rc = sail_temporal_load_history(h->ctx, hist, g, m, eye);
+  if (rc) return throwSail(env, "sail_temporal_load_history", rc, h->ctx);
+  return undef(env);
+}
 // (ctx, timeoutMs) -> whether the scene's run-time kernel is loaded (sail_kernel_ready; -1 waits for its build)
 napi_value KernelReady(napi_env env, napi_callback_info info) {
   napi_value a[2];
@@ -664,6 +793,11 @@ napi_value Init(napi_env env, napi_value exports) {
       {"noise", 0, Noise, 0, 0, 0, napi_enumerable, 0},
       {"renderUntil", 0, RenderUntil, 0, 0, 0, napi_enumerable, 0},
       {"denoise", 0, Denoise, 0, 0, 0, napi_enumerable, 0},
+      {"gbuffer", 0, Gbuffer, 0, 0, 0, napi_enumerable, 0},
+      {"temporalBegin", 0, TemporalBegin, 0, 0, 0, napi_enumerable, 0},
+      {"temporalResolve", 0, TemporalResolve, 0, 0, 0, napi_enumerable, 0},
+      {"temporalRead", 0, TemporalRead, 0, 0, 0, napi_enumerable, 0},
+      {"temporalLoadHistory", 0, TemporalLoadHistory, 0, 0, 0, napi_enumerable, 0},
       {"kernelReady", 0, KernelReady, 0, 0, 0, napi_enumerable, 0},
       {"kernelInfo", 0, KernelInfo, 0, 0, 0, napi_enumerable, 0},
       {"pick", 0, Pick, 0, 0, 0, napi_enumerable, 0},

@@ -12,7 +12,13 @@
 // one call; readPixels() / readAOV() / image() read the float frame back (the reference never reads back);
 // renderUntil(scene, {noise, minSpp, maxSpp}) renders until the device-side noise estimate is at most `noise`
 // (noiseMark() / noise() are its two halves: sail_noise_mark / sail_noise_estimate); denoise({...}) runs the
-// variance-guided a-trous denoiser over the frame, the mark and the AOV maps (sail_denoise).
+// variance-guided a-trous denoiser over the frame, the mark and the AOV maps (sail_denoise). Camera-motion reprojection:
+// gbuffer(scene) is the id / depth / position pass of the scene's view (sail_gbuffer); temporalBegin(scene) tells the
+// context that the camera is now at the scene's view and temporalResolve({display, gamma}) blends the history reprojected
+// into it with the samples rendered since (sail_temporal_begin / sail_temporal_resolve). With the option
+// temporal: true | {cap, posTol} (off by default) render / renderSamples / renderUntil call temporalBegin whenever they
+// restart the frame, and image() shows the resolve instead of the bare frame for the pointwise display filters, so an
+// orbit keeps the picture instead of dropping to one noisy sample.
 const native = require('./native');
 const { filterConfig } = require('./filter');
 
@@ -55,6 +61,10 @@ class Renderer {
       throw new Error("Renderer: partition 'samples' needs accumulation 'sum' (a running mean cannot be split by samples)");
     this.aov = opts.aov !== false;
     this.display = opts.display === undefined ? !!this.canvas : !!opts.display;
+    // camera-motion reprojection, off by default: true, or {cap, posTol} (left out: sail_temporal_defaults' 32 and 0.05)
+    this.temporal = opts.temporal ? Object.assign({}, opts.temporal === true ? {} : opts.temporal) : null;
+    if (this.temporal && this.accumulation === 'compat8')
+      throw new Error("Renderer: temporal needs accumulation 'sum' or 'mix' (8-bit frames carry no sample count)");
     this.lib = native.load();
     const flags = (this.aov ? 1 : 0) | 2;
     this.ctx = this.devices ? this.lib.createMulti(this.width, this.height, Int32Array.from(this.devices), flags)
@@ -69,6 +79,7 @@ class Renderer {
     this.filter = filterConfig({ name: 'color', params: {} });
     this.pixels = null;
     this.n = 0;
+    this._temporalView = false;  // a temporalBegin has made a view current since the last scene change
   }
 
   update(scene) {
@@ -79,20 +90,28 @@ class Renderer {
     this.lib.setScene(this.ctx, s.objects, s.n, s.texparams, s.tn, s.lights, s.ln, masksOf(scene.tracerConfig()));
     this.n = s.n;
     scene.sampleCount = 0;
+    this._temporalView = false;  // a new scene drops the temporal state
   }
 
   updateObjects(scene) {
     this.lib.updateObjects(this.ctx, scene.serializeObjects(), this.n);
+    this._temporalView = false;  // so do moved objects: a drag drops the history
   }
 
   _mvp(scene) { return rowMajor(scene.mat); }
+
+  // the frame restarts (the reference's textureWeight 0); with the temporal option the new view takes over the history
+  _restart(scene) {
+    this.lib.reset(this.ctx);
+    if (this.temporal) this.temporalBegin(scene);
+  }
 
   render(scene) {
     if (scene.moving) {
       scene.sampleCount = 0;
       this.updateObjects(scene);
     }
-    if (scene.sampleCount === 0) this.lib.reset(this.ctx);  // textureWeight 0: the frame restarts
+    if (scene.sampleCount === 0) this._restart(scene);  // textureWeight 0: the frame restarts
     const k = scene.sampleCount++;
     const mvp = this._mvp(scene);
     const eye = Float32Array.from(scene.eye.elements);
@@ -111,7 +130,7 @@ class Renderer {
   // many samples in one launch sequence, deterministic schedule k0 .. k0+spp-1
   renderSamples(scene, spp) {
     if (scene.moving) { scene.sampleCount = 0; this.updateObjects(scene); }
-    if (scene.sampleCount === 0) this.lib.reset(this.ctx);
+    if (scene.sampleCount === 0) this._restart(scene);
     const sch = this.lib.schedule(this._mvp(scene), this.width, this.height, scene.sampleCount, spp);
     this.lib.renderSchedule(this.ctx, sch.inv, sch.seeds, Float32Array.from(scene.eye.elements), this.maxBounces);
     scene.sampleCount += spp;
@@ -124,7 +143,7 @@ class Renderer {
   renderUntil(scene, { noise, minSpp = 16, maxSpp = 65536 } = {}) {
     if (typeof noise !== 'number' || Number.isNaN(noise)) throw new Error('Renderer.renderUntil: noise (the target) must be a number');
     if (scene.moving) { scene.sampleCount = 0; this.updateObjects(scene); }
-    if (scene.sampleCount === 0) this.lib.reset(this.ctx);
+    if (scene.sampleCount === 0) this._restart(scene);
     let r;
     try {
       r = this.lib.renderUntil(this.ctx, this._mvp(scene), Float32Array.from(scene.eye.elements), this.maxBounces,
@@ -160,10 +179,41 @@ class Renderer {
     return this.lib.denoise(this.ctx, iterations, sigmaL, sigmaX, kind, gamma, display !== undefined);
   }
 
-  // the display pass: pixelFilter over the accumulated frame -> RGBA8 (row 0 = bottom, GL order)
+  // The G-buffer pass of the scene's view (sail_gbuffer): {id: Int32Array (object row of each pixel's first hit, -1 = miss),
+  // t: Float32Array (its distance, 1e5 on a miss), xyz: Float32Array (its world position, 3 per pixel)}, row 0 = bottom.
+  gbuffer(scene) {
+    return this.lib.gbuffer(this.ctx, this._mvp(scene), Float32Array.from(scene.eye.elements));
+  }
+  // "The camera is now at the scene's view" (sail_temporal_begin): the view that was current is committed as the history,
+  // which is reprojected into the new view. Returns {k, hitPixels, historyPixels, nonfinite, kernelMs, passMs}.
+  temporalBegin(scene) {
+    const t = this.temporal || {};
+    this._temporalView = false;  // a begin that throws leaves no current view: image() then shows the bare frame
+    const info = this.lib.temporalBegin(this.ctx, this._mvp(scene), Float32Array.from(scene.eye.elements), t.cap, t.posTol);
+    this._temporalView = true;
+    return info;
+  }
+  // Blend the reprojected history with the samples of the current view (sail_temporal_resolve). display ('color' | 'gamma'
+  // | 'tonemapping', default 'color') and gamma choose the RGBA8 transform. Returns {rgba: Float32Array (colour and
+  // effective sample count), rgba8, info}. The frame itself is not changed.
+  temporalResolve({ display, gamma } = {}) {
+    const kinds = { color: 0, gamma: 1, tonemapping: 2 };
+    let kind;
+    if (display !== undefined) {
+      kind = typeof display === 'number' ? display : kinds[display];
+      if (kind === undefined) throw new Error(`Renderer.temporalResolve: unknown display '${display}' (color | gamma | tonemapping)`);
+    }
+    const t = this.temporal || {};
+    return this.lib.temporalResolve(this.ctx, t.cap, t.posTol, kind, gamma, true);
+  }
+
+  // the display pass: pixelFilter over the accumulated frame -> RGBA8 (row 0 = bottom, GL order); with the temporal option
+  // and a pointwise filter (color, gamma, tonemapping) the resolve's RGBA8 of the same transform
   image() {
     const f = this.filter;
     if (f.aov && !this.aov) throw new Error('this display filter reads the AOVs: create the Renderer with aov: true');
+    if (this.temporal && this._temporalView && f.kind <= 2)
+      return this.lib.temporalResolve(this.ctx, this.temporal.cap, this.temporal.posTol, f.kind, f.gamma, false).rgba8;
     return this.lib.filter(this.ctx, f.kind, f.weights, f.rx, f.ry, f.gamma).rgba8;
   }
 
