@@ -439,6 +439,17 @@ int sail_schedule(const double mvp_rowmajor[16], int width, int height, int k0, 
  * texParams row count the rows index), 6 floats min.xyz, max.xyz of the padded box, +-inf where a primitive has no
  * finite bound; a row whose category is not a shape gets an empty box (+inf, -inf). Host-only (no device). */
 int sail_prim_bounds(const float* objects, int n, int tn, float* out_minmax);
+/* Host only (no device): what the last bounce of the flat kernels' Cornell and all-plugin forms does with a hit on each
+ * row of a scene of at most 32 rows (sail_set_scene's arguments; the room form runs its last bounce like the others). A path's last bounce only adds radiance. Bit r of *quiet_rows: a hit on row r adds
+ * exactly (+0, +0, +0) x throughput whatever its hit record holds -- the row's emission words are +0.0f bit for bit
+ * and it is not a matte, or it is a Lambertian matte (sigma < EPSILON) of a constant colour (a Cornellbox's walls, a
+ * uniform texture) with kd x colour / pi finite, in a kernel without a light plugin -- so no record is built for it.
+ * *skip_sort = 1 when, besides, every other row that a ray can hit emits and its last bounce needs no BSDF sample:
+ * the last bounce's path sort is skipped as well. kernel_lights: nonzero when the kernel that runs has a light plugin
+ * compiled in (every kernel but the Cornell set's and a run-time kernel of a scene whose light mask is 0). Larger
+ * scenes get 0 and 0. */
+int sail_plan_last_bounce(const float* objects, int n, const float* texparams, int tn, const sail_plugins* plugins,
+                          int kernel_lights, uint32_t* quiet_rows, int* skip_sort);
 
 /* ---- multi-GPU (one process per GPU): image tiles / sample split + RCCL sum-reduce of the accumulators ---- */
 int sail_comm_unique_id(char id[128]);

@@ -47,7 +47,7 @@ EXPORTS = (
     "sail_prim_bounds", "sail_math_probe", "sail_pick", "sail_kernel_name", "sail_filter_ms",
     "sail_abi_version", "sail_accum_parts", "sail_save_accum", "sail_load_accum", "sail_jit_compile",
     "sail_get_kernel_info", "sail_kernel_ready", "sail_set_jit_cache", "sail_jit_prebuild",
-    "sail_plan_reduce", "sail_plan_keep", "sail_plan_load_part",
+    "sail_plan_reduce", "sail_plan_keep", "sail_plan_load_part", "sail_plan_last_bounce",
     "sail_noise_mark", "sail_noise_estimate", "sail_plan_until", "sail_render_until",
     "sail_denoise_defaults", "sail_denoise",
     "sail_temporal_defaults", "sail_gbuffer", "sail_temporal_begin", "sail_temporal_resolve", "sail_temporal_read",
@@ -178,6 +178,8 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
         "sail_partition_tiles": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                  ctypes.POINTER(ctypes.c_int), ctypes.c_int]),
         "sail_prim_bounds": (ctypes.c_int, [f32p, ctypes.c_int, ctypes.c_int, f32p]),
+        "sail_plan_last_bounce": (ctypes.c_int, [f32p, ctypes.c_int, f32p, ctypes.c_int, ctypes.POINTER(Plugins), ctypes.c_int,
+                                                 ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int)]),
         "sail_math_probe": (ctypes.c_int, [ctypes.c_int, f32p, f32p, f32p, ctypes.c_int]),
         "sail_abi_version": (ctypes.c_int, []),
         "sail_pick": (ctypes.c_int, [vp, f32p, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), f32p]),
@@ -392,6 +394,21 @@ def prim_bounds(objects, n: int, tn: int) -> np.ndarray:
     if rc:
         raise SailError(f"sail_prim_bounds: {rc}")
     return out[:n].reshape(n, 2, 3)
+
+
+def plan_last_bounce(sc: dict, kernel_lights: bool):
+    """(quiet row mask, skip_sort) of scene `sc` for a flat kernel with / without a light plugin compiled in
+    (sail_plan_last_bounce, host-only): the rows whose hits add exactly +0 at a path's last bounce, and whether that
+    bounce's path sort is skipped too."""
+    lib = load()
+    o, t = _f32(sc["objects"]), _f32(sc["texparams"])
+    pl = Plugins(*[int(m) for m in plugin_masks(sc["plugins"])])
+    quiet, skip = ctypes.c_uint32(0), ctypes.c_int(0)
+    rc = lib.sail_plan_last_bounce(_ptr(o), sc["n"], _ptr(t), sc["tn"], ctypes.byref(pl), int(bool(kernel_lights)),
+                                   ctypes.byref(quiet), ctypes.byref(skip))
+    if rc:
+        raise SailError(f"sail_plan_last_bounce: {rc}: {lib.sail_last_error(None).decode()}")
+    return int(quiet.value), int(skip.value)
 
 
 def math_probe(fn: int, x: np.ndarray, y: Optional[np.ndarray] = None) -> np.ndarray:

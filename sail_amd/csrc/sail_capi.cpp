@@ -144,6 +144,11 @@ struct sail_ctx {
   sail_plugins plugins{};
   bool haveScene = false;
   int shadowAnyHit = 0;
+  // the rows' last-bounce classes (lastBounceRows) for a kernel without ([0]) and with ([1]) a light plugin compiled in,
+  // re-derived whenever the rows are decoded (sail_set_scene, sail_update_objects: texParams and plugin masks change
+  // only with the former); launchTrace passes the pair of the kernel it launches
+  uint32_t lastQuietRows[2] = {0u, 0u};
+  int lastSkipSort[2] = {0, 0};
   std::vector<unsigned long long> typeMasksHost;  // staging for the per-chunk type masks (async copy source)
   int cullMinPrims = 8;  // scenes with at least this many primitives use the padded-box pre-cull
   int lastGroups = 1;         // the last trace launch: sample groups (sail_kernel_name)
@@ -682,6 +687,66 @@ void fillCats(std::vector<SailPrim>& prims, const float* texparams, int tn) {
     p.cats = (int32_t)(((uint32_t)(uint16_t)(int16_t)cat(p.matRow)) | ((uint32_t)(uint16_t)(int16_t)cat(p.texRow) << 16));
 }
 
+// What a path's last bounce can add at a hit on each row (SailTraceArgs.lastQuietRows / lastSkipSort), decided with
+// the kernel's own tests and f32 operations on the values it reads (sail_trace.hip shadeLast: emission, matCat,
+// matRow -> kd, sigma, the Cornellbox wall constants or the uniform texture's colour). `lights`: the kernel that will
+// run has a light plugin compiled in (shadeLast then declines every lit matte hit).
+//   quiet: the emission words are +0.0f bit for bit (the facing test can only zero them again), and the row is not a
+//     matte, or it is one whose light term is fma(f, 0, 0) with f = (kd * sc) * (1 / pi) finite for every colour sc the
+//     record can give it: +0. Its update is e + (+0) * throughput whatever the record says.
+//   record-only: shadeLast accepts every hit on the row, but the value depends on the record (an emitter's facing test,
+//     a non-finite f).
+//   full: shadeLast can decline (a light plugin, Oren-Nayar), or the matte's colour is not a per-scene constant.
+// Rows of more than 32-row scenes are not classified (the pre-cull kernels take none of this); a row no ray can hit
+// (type 0) has no class. skipSort: no full row, and every record-only row emits (a black one is a matte whose light
+// term is not +0: those keep the sort). Anything this cannot decide is full.
+void lastBounceRows(const std::vector<SailPrim>& prims, const float* tp, int tn, uint32_t matMask, bool lights,
+                    uint32_t* quietRows, int* skipSort) {
+  *quietRows = 0;
+  *skipSort = 0;
+  const int n = (int)prims.size();
+  if (n < 1 || n > 32 || tn < 1 || !tp) return;
+  constexpr float kEps = 1e-5f, kInvPI = 0.3183098861837907f;  // sail_trace.hip
+  bool skip = true, any = false;
+  for (int i = 0; i < n; i++) {
+    const SailPrim& p = prims[(size_t)i];
+    if (p.type == 0) continue;
+    any = true;
+    uint32_t eb[3];
+    memcpy(eb, p.em, sizeof eb);
+    const bool emPosZero = (eb[0] | eb[1] | eb[2]) == 0u;
+    const bool emBlack = p.em[0] == 0.0f && p.em[1] == 0.0f && p.em[2] == 0.0f;  // isBlack: -0 too, never NaN
+    const bool matte = (int)(short)(p.cats & 0xffff) == SAIL_MATTE;
+    bool matteOk = true;  // a lit matte hit on the row adds exactly +0
+    if (matte) {
+      const bool rowsOk = p.matRow >= 0 && p.matRow < tn && p.texRow >= 0 && p.texRow < tn;
+      if (lights || !rowsOk) {
+        matteOk = false;
+      } else if ((matMask >> SAIL_MATTE) & 1u) {  // material()'s matte branch; without the plugin f stays +0
+        const float kd = tp[(size_t)p.matRow * 16 + 1], sigma = tp[(size_t)p.matRow * 16 + 2];
+        float sc[4][3] = {{0.25f, 0.75f, 0.25f}, {0.25f, 0.25f, 0.75f}, {1.0f, 1.0f, 1.0f}, {0.0f, 0.0f, 0.0f}};
+        int ncol = 0;
+        if (p.type == SAIL_CORNELLBOX) {
+          ncol = 4;
+        } else if ((p.cats >> 16) == SAIL_TEX_UNIFORM) {
+          for (int k = 0; k < 3; k++) sc[0][k] = tp[(size_t)p.texRow * 16 + 1 + k];
+          ncol = 1;
+        }
+        matteOk = sigma < kEps && ncol > 0;
+        for (int q = 0; q < ncol; q++)
+          for (int k = 0; k < 3; k++) {
+            volatile float f = kd * sc[q][k];  // two roundings, as the kernel's (kd * sc) * kInvPI
+            f = f * kInvPI;
+            if (!std::isfinite((float)f)) matteOk = false;
+          }
+      }
+    }
+    if (emPosZero && matteOk) *quietRows |= 1u << i;
+    else if (!(matteOk && !emBlack)) skip = false;
+  }
+  *skipSort = (any && skip) ? 1 : 0;
+}
+
 void decodePrims(const float* objects, int n, int tn, uint32_t shapeMask, std::vector<SailPrim>& out, int* anyHitOk,
                  SceneBox* sbOut) {
   std::vector<PrimBox> raw((size_t)n);
@@ -823,6 +888,11 @@ int launchTrace(sail_ctx* c, const SailSample* hs, int count, int maxBounces) {
     // samples of each pixel in flight per workgroup (the run-time kernels' spec; the precompiled kernels hold one):
     // NS times the workgroups of one sample in flight, each NS times shorter
     const int ns = jit ? c->jitSpec.ns : 1;
+    {  // the last bounce's row classes for the light plugins compiled into the kernel that runs (shadeLast's kLights)
+      const bool kl = jit ? c->jitSpec.kl != 0u : A.kernelSet != SAIL_KSET_CORNELL;
+      A.lastQuietRows = A.cullPrims ? 0u : c->lastQuietRows[kl];
+      A.lastSkipSort = A.cullPrims ? 0 : c->lastSkipSort[kl];
+    }
     int G = 1;
     if (c->forceGroups > 0) {
       G = c->forceGroups;
@@ -1374,6 +1444,8 @@ int sail_set_scene(sail_ctx* c, const float* objects, int n, const float* texpar
   std::vector<SailPrim> prims;
   decodePrims(objects, n, tn, plugins->shape_mask, prims, &c->shadowAnyHit, &c->scene);
   fillCats(prims, texparams, tn);
+  for (int l = 0; l < 2; l++)
+    lastBounceRows(prims, texparams, tn, plugins->material_mask, l != 0, &c->lastQuietRows[l], &c->lastSkipSort[l]);
   c->primExtent = primExtent(prims);
   c->primTypes.clear();
   for (const SailPrim& q : prims) c->primTypes.push_back(q.type);
@@ -1424,6 +1496,9 @@ int sail_update_objects(sail_ctx* c, const float* objects, int n) {
   std::vector<SailPrim> prims;
   decodePrims(objects, n, c->tn, c->plugins.shape_mask, prims, &c->shadowAnyHit, &c->scene);
   fillCats(prims, c->tpRows.data(), c->tn);
+  for (int l = 0; l < 2; l++)
+    lastBounceRows(prims, c->tpRows.data(), c->tn, c->plugins.material_mask, l != 0, &c->lastQuietRows[l],
+                   &c->lastSkipSort[l]);
   c->primExtent = primExtent(prims);
   c->primTypes.clear();
   for (const SailPrim& q : prims) c->primTypes.push_back(q.type);  // a kernel compiled for the rows follows them
@@ -2489,6 +2564,19 @@ int sail_prim_bounds(const float* objects, int n, int tn, float* out) {
       out[6 * i + 3 + k] = p.type ? p.a[21 + k] : -INFINITY;
     }
   }
+  return SAIL_OK;
+}
+
+int sail_plan_last_bounce(const float* objects, int n, const float* texparams, int tn, const sail_plugins* plugins,
+                          int kernel_lights, uint32_t* quiet_rows, int* skip_sort) {
+  if (n < 0 || tn < 0 || (n > 0 && !objects) || (tn > 0 && !texparams) || !plugins || !quiet_rows || !skip_sort ||
+      (n > 0 && tn < 1))
+    return fail(nullptr, SAIL_E_INVALID, "sail_plan_last_bounce: bad arguments");
+  std::vector<SailPrim> prims;
+  int anyHit = 0;
+  decodePrims(objects, n, tn, plugins->shape_mask, prims, &anyHit, nullptr);
+  fillCats(prims, texparams, tn);
+  lastBounceRows(prims, texparams, tn, plugins->material_mask, kernel_lights != 0, quiet_rows, skip_sort);
   return SAIL_OK;
 }
 

@@ -81,6 +81,13 @@ struct SailTraceArgs {
   int groupHome;            // 1: group 0 accumulated its samples itself (SAIL_GROUP_HOME_FOR), the stage starts at groupSpp
   float* stage;             // three f32 planes per sample: stage[(3k + c) * stageStride + slot]
   long long stageStride;    // slots per sample = ownedTiles * 4096
+  // The last bounce of the Cornell and all-plugin forms (sail_capi.cpp lastBounceRows): bit r of lastQuietRows = a hit
+  // on row r adds exactly (+0, +0, +0) * throughput there, whatever its hit record says, so the path ends before the
+  // sort; lastSkipSort = 1 when no row's last bounce can need shadeBounce and every row that still builds a record
+  // emits, so the paths that are left are not sorted. Both 0 (scenes of more than 32 rows, the pre-cull kernels): the
+  // last bounce runs like any other. The room form reads neither.
+  uint32_t lastQuietRows;
+  int lastSkipSort;
 };
 
 // Wavefront split of the pre-cull path (study switch SAIL_DEBUG_WAVEFRONT): the path state of one sample of every

@@ -1926,6 +1926,25 @@ __device__ __forceinline__ void traceTileCompact(const SailTraceArgs& A) {
           key = 1 + mc * 10 + p.type;
         }
       }
+      // The last bounce (Cornell and all-plugin forms): only the path's radiance is read after it, and a hit on a
+      // quiet row (SailTraceArgs.lastQuietRows, classified by the host) adds exactly +0 * throughput whatever its hit
+      // record holds. Such a path ends here, on the lane that has carried it since the last gather (which also made the last
+      // store to its pixel's radiance): shadeLast's e + (emission + direct) * fpdf with both terms +0 -- the multiply and
+      // the add are made, so a non-finite throughput gives the same NaN -- and then it is dead to the sort, the hit
+      // record and the shading like a path that left the scene. Its segment is counted above. The lanes of the AOV
+      // sample keep their first-bounce record. Measured bit-identical (profiles/r07_last_quiet.jsonl): C2 +3.2 %,
+      // C5 +1.2 %; the room form is left as it was: its light plugins keep every matte row out of this, and with the
+      // test compiled in C3 lost 1.0 % (three runs each, spread 0.1 %).
+      const bool lastB = !CULL && !FAM && depth == A.maxBounces;  // uniform
+      if constexpr (!CULL && !FAM) {
+        if (lastB) __builtin_amdgcn_s_setprio(0);  // most waves gather no path below: none keeps a raised priority
+        if (lastB && alive && ((A.lastQuietRows >> (sw.bi & 31)) & 1u) != 0u &&
+            !(depth == 1 && aovs && k + pixel / kPX == A.spp - 1)) {
+          E_STORE(pixel, E_LOAD(pixel) + v3s(0.0f) * fpdf);
+          alive = false;
+          key = 0;
+        }
+      }
       PHASE_MARK(pc, 0);
       // ---- counting sort of the live paths by key (LDS atomics for the per-key rank, one wave scans)
       int rank = 0;
@@ -1953,7 +1972,10 @@ __device__ __forceinline__ void traceTileCompact(const SailTraceArgs& A) {
       // mostly hit one row already and none is dead yet, so each lane keeps its own pixel's path (C1 +1.1 %; the room
       // and pre-cull kernels keep the sort, where skipping it measured C3 -1.6 %, C4 -9.2 %:
       // profiles/r04_skip_sort1.jsonl)
-      const bool sortNow = kSort1 || depth > 1;
+      // lastSkipSort: every row that is not quiet is an emitter whose hit shadeLast accepts, so the few paths left
+      // after the quiet ones ended are not sorted: each lane keeps the path it holds. A sort skipped leaves the count
+      // buffers as the last sort cleared them and ph where it was, so the next sample's sorts alternate on as before.
+      const bool sortNow = (kSort1 || depth > 1) && !(lastB && A.lastSkipSort != 0);
       if (sortNow) {
       if constexpr (twoBar) {
       // every wave scans the counts itself (the start of a lane's key by a cross-lane read), so no barrier
