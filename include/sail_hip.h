@@ -133,7 +133,14 @@ enum sail_debug_option {
   SAIL_DEBUG_JIT_NS = 11,
   /* threads per workgroup of the run-time kernels: 128, 256, 512 or 1024 (the path sort's pool); 0 = the form's own
    * [0: 256 flat, 1,024 pre-cull] */
-  SAIL_DEBUG_JIT_NT = 12
+  SAIL_DEBUG_JIT_NT = 12,
+  /* the value kernel, a second tier on top of the scene's run-time kernel: a flat-form kernel compiled for the rows'
+   * values (the decoded rows and the texParams table as constants), asked for once the context has rendered `value`
+   * samples since its rows last changed (sail_set_scene, sail_update_objects, a switch or partition that changes the
+   * run-time kernel; not sail_reset or the camera). 0: asked for at once; < 0: never. A launch uses it when it is loaded
+   * and never waits for it; a change of the rows returns to the kernel above at the next launch. Same results [256: a
+   * policy value that keeps scenes in motion and few-sample renders from compiling, not a tuned one] */
+  SAIL_DEBUG_JIT_VALUES_AFTER = 13
 };
 int sail_set_debug(sail_ctx* ctx, int option, int value);
 
@@ -403,6 +410,8 @@ typedef struct sail_kernel_info {
   uint64_t build_id;      /* its build identity: FNV-1a 64 of the code object with the compiler's source-derived
                            * compilation-unit id masked (run-time kernels), or of the library image and the kernel's name
                            * (precompiled): profiles are matched to kernels by it */
+  /* the jit_* fields describe the best tier that is loaded -- the value kernel once it is (SAIL_DEBUG_JIT_VALUES_AFTER),
+   * else the scene's run-time kernel -- that is, what the next launch runs; name and build_id are the last launch's */
   int jit_state;          /* sail_kernel_jit_state of the scene's run-time kernel */
   int jit_from_cache;     /* its code object came from 0: hipRTC in this process, 1: the user's disk cache, 2: the
                            * cache shipped beside the library */
@@ -415,13 +424,32 @@ int sail_get_kernel_info(sail_ctx* ctx, sail_kernel_info* out);
  * its build (-1: until done); 0 while it is still building, when none applies, or when it failed */
 int sail_kernel_ready(sail_ctx* ctx, int timeout_ms, int* ready);
 /* process-wide user cache directory of run-time code objects: NULL = default ($XDG_CACHE_HOME or $HOME/.cache, then
- * sail_amd/jit), "" = no user cache */
+ * sail_amd/jit), "" = no user cache. The directory holds the run-time kernels' objects; the value kernels' objects
+ * (SAIL_DEBUG_JIT_VALUES_AFTER) are written to a directory beside it, the same path with "-values" appended (dir
+ * "/x/jit": "/x/jit-values"), which is created on demand and holds at most 32 objects, the oldest deleted first. The
+ * same rule names the value directory of sail_jit_prebuild's `dir` and of the cache shipped beside the library. */
 int sail_set_jit_cache(const char* dir);
 /* Host only (no device): build the run-time kernel a context with the default switches derives for this scene (the rows
  * of sail_set_scene) for `arch`, into the cache directory `dir` (the shipped cache when dir is <lib dir>/jit). *built
  * (may be NULL) = 1 when the scene gets a run-time kernel, 0 when it does not. */
 int sail_jit_prebuild(const float* objects, int n, const float* texparams, int tn, const float* lights, int ln,
                       const sail_plugins* plugins, const char* arch, const char* dir, int* built);
+/* The value kernel (SAIL_DEBUG_JIT_VALUES_AFTER): sail_jit_prebuild builds it too for every scene whose run-time kernel is
+ * the flat form compiled for rows with at most 32 texParams rows. Host only, nothing is compiled: *key = the disk caches'
+ * key of the value kernel a context with the default switches derives for this scene once it has settled (its object is
+ * <dir>-values/<key as 16 hex digits>.co, beside the cache directory <dir> of the types kernels; 0 when the scene gets none), and the source prefix it is compiled with -- the rows and
+ * the texParams table as 32-bit words, so that two scenes differing in one bit (+0 / -0, a NaN payload) are two kernels.
+ * *defs_len (may be NULL) = the prefix's size with its terminator; copied into defs when *defs_len on entry is enough. */
+int sail_jit_value_key(const float* objects, int n, const float* texparams, int tn, const sail_plugins* plugins,
+                       const char* arch, uint64_t* key, char* defs, size_t* defs_len);
+/* 1 when a context that rendered `settled` samples since its rows last changed asks for its value kernel under
+ * SAIL_DEBUG_JIT_VALUES_AFTER = after (0: at once, < 0: never), else 0 */
+int sail_plan_settle(uint64_t settled, int after);
+/* What the process keeps of value kernels: *code_objects in host memory, *modules loaded on devices. A value kernel is
+ * one per pose of a scene at rest, so both are released when the last context that holds one drops it (a change of its
+ * rows, another scene, sail_destroy): they are bounded by the live contexts, not by the poses seen. The objects stay in
+ * the disk caches. */
+int sail_jit_resident(int* code_objects, int* modules);
 
 /* ---- host math of the reference, so every host language gets identical uniforms ---- */
 /* Camera(eye, center, up) + makePerspective(fovy, aspect, near, far) (src/scene/camera.js:6-57):

@@ -32,6 +32,7 @@ DEBUG_JIT = 9
 DEBUG_JIT_WAIT = 10  # ms a launch waits for the scene's run-time kernel (-1: until built; the C ABI's default is 0)
 DEBUG_JIT_NT = 12  # threads per workgroup of the run-time kernels (0: the form's own)
 DEBUG_JIT_NS = 11  # samples of each pixel in flight per workgroup of the run-time kernels (0: the form's default)
+DEBUG_JIT_VALUES_AFTER = 13  # samples at rest before the kernel compiled for the rows' values is asked for (0: at once, < 0: never)
 KERNEL_JIT_NONE, KERNEL_JIT_PENDING, KERNEL_JIT_READY, KERNEL_JIT_FAILED = 0, 1, 2, 3
 JIT_MODE_FLAT, JIT_MODE_CULL, JIT_MODE_ROOM = 0, 1, 2  # sail_jit_compile kernel forms (include/sail_hip.h)
 # applied to every Context at creation (tests set entries with monkeypatch.setitem)
@@ -47,6 +48,7 @@ EXPORTS = (
     "sail_prim_bounds", "sail_math_probe", "sail_pick", "sail_kernel_name", "sail_filter_ms",
     "sail_abi_version", "sail_accum_parts", "sail_save_accum", "sail_load_accum", "sail_jit_compile",
     "sail_get_kernel_info", "sail_kernel_ready", "sail_set_jit_cache", "sail_jit_prebuild",
+    "sail_jit_value_key", "sail_plan_settle", "sail_jit_resident",
     "sail_plan_reduce", "sail_plan_keep", "sail_plan_load_part", "sail_plan_last_bounce",
     "sail_noise_mark", "sail_noise_estimate", "sail_plan_until", "sail_render_until",
     "sail_denoise_defaults", "sail_denoise",
@@ -195,6 +197,10 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
         "sail_set_jit_cache": (ctypes.c_int, [ctypes.c_char_p]),
         "sail_jit_prebuild": (ctypes.c_int, [f32p, ctypes.c_int, f32p, ctypes.c_int, f32p, ctypes.c_int, ctypes.POINTER(Plugins),
                                              ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]),
+        "sail_jit_value_key": (ctypes.c_int, [f32p, ctypes.c_int, f32p, ctypes.c_int, ctypes.POINTER(Plugins), ctypes.c_char_p,
+                                              ctypes.POINTER(ctypes.c_uint64), ctypes.c_char_p, ctypes.POINTER(ctypes.c_size_t)]),
+        "sail_plan_settle": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_int]),
+        "sail_jit_resident": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
         "sail_plan_reduce": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                             ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ReducePlan)]),
         "sail_plan_keep": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, f32p, f32p]),
@@ -456,6 +462,39 @@ def jit_prebuild(sc: dict, arch: str = "gfx950", cache_dir: Optional[str] = None
     if rc:
         raise SailError(f"sail_jit_prebuild: {rc}: {lib.sail_last_error(None).decode()}")
     return bool(built.value)
+
+
+def jit_value_key(sc: dict, arch: str = "gfx950"):
+    """Host-only, nothing is compiled: (key, source prefix) of the value kernel a default context derives for scene `sc`
+    once it has settled; its cache object is <cache dir>-values/<key>.co. (None, "") when the scene gets no value kernel."""
+    lib = load()
+    o, t = _f32(sc["objects"]), _f32(sc["texparams"])
+    pl = Plugins(*[int(m) for m in plugin_masks(sc["plugins"])])
+    key, size = ctypes.c_uint64(0), ctypes.c_size_t(0)
+    buf = None
+    for _ in range(2):  # the size, then the text
+        rc = lib.sail_jit_value_key(_ptr(o), sc["n"], _ptr(t), sc["tn"], ctypes.byref(pl), arch.encode(), ctypes.byref(key),
+                                    buf, ctypes.byref(size))
+        if rc:
+            raise SailError(f"sail_jit_value_key: {rc}: {lib.sail_last_error(None).decode()}")
+        if size.value == 0:
+            return None, ""
+        if buf is None:
+            buf = ctypes.create_string_buffer(size.value)
+    return f"{key.value:016x}", buf.value.decode()
+
+
+def jit_resident():
+    """(code objects in host memory, modules loaded on devices) of value kernels in this process"""
+    a, b = ctypes.c_int(0), ctypes.c_int(0)
+    load().sail_jit_resident(ctypes.byref(a), ctypes.byref(b))
+    return a.value, b.value
+
+
+def plan_settle(settled: int, after: int) -> bool:
+    """Whether a context that rendered `settled` samples since its rows last changed asks for its value kernel under
+    DEBUG_JIT_VALUES_AFTER = after"""
+    return bool(load().sail_plan_settle(int(settled), int(after)))
 
 
 def comm_unique_id() -> bytes:

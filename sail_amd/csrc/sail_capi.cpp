@@ -174,6 +174,18 @@ struct sail_ctx {
   int jitWait = 0;
   int jitNt = 0;  // SAIL_DEBUG_JIT_NT: threads per workgroup of the run-time kernels (0: the form's own)
   int jitNs = 0;  // SAIL_DEBUG_JIT_NS: samples in flight of the run-time kernels (0: the form's default, jitNsFor)
+  // The value kernel, a second tier on top of the scene's run-time kernel (refreshValues): the same spec with the rows'
+  // and the texParams table's words compiled in, asked for once `settled` samples were rendered since the rows last
+  // changed (sail_set_scene, sail_update_objects, a new types spec; not sail_reset or the camera). A launch uses it when
+  // it is loaded and never waits for it. jitValuesAfter (SAIL_DEBUG_JIT_VALUES_AFTER): 0 at once, < 0 never; 256 is a
+  // policy value, not tuned -- it only has to keep scenes in motion and few-sample renders from compiling.
+  int jitValuesAfter = 256;
+  uint64_t settled = 0;
+  std::vector<uint32_t> rowWords;  // the decoded rows as uploaded (uploadPrims), 32 words each
+  bool valHave = false;
+  SailJitSpec valSpec;
+  int valState = SAIL_KERNEL_JIT_NONE;
+  SailJitKernel valK;
   bool lastJit = false;  // the last trace launch ran a run-time compiled kernel (sail_kernel_name)
   int lastJitMode = 0;
   uint64_t lastBuildId = 0;  // the run-time kernel's build identity (sail_get_kernel_info)
@@ -366,6 +378,73 @@ bool jitSpecFor(const sail_ctx* c, SailJitSpec* out, int* mode) {
   *mode = m;
   return true;
 }
+// The rows changed, or the spec their value kernel was derived from: the hold on the value spec goes (a queued build of it
+// is skipped, a finished one stays in the caches for a scene that returns to this pose), launches run the types kernel
+// again, and the settle count restarts.
+void dropValues(sail_ctx* c) {
+  if (c->valHave) {
+    // the last hold unloads the module (sail_jit_hold): no launch of it may still be running on this context's stream
+    if (c->valState == SAIL_KERNEL_JIT_READY && c->stream) {
+      (void)hipSetDevice(c->device);
+      (void)hipStreamSynchronize(c->stream);
+    }
+    sail_jit_hold(c->device, c->valSpec, -1);
+  }
+  c->valHave = false;
+  c->valSpec = SailJitSpec{};
+  c->valState = SAIL_KERNEL_JIT_NONE;
+  c->valK = SailJitKernel{};
+  c->settled = 0;
+}
+// Whether the value kernel of a scene that rendered `settled` samples since its rows changed is asked for now
+// (sail_plan_settle; after: SAIL_DEBUG_JIT_VALUES_AFTER)
+bool settledFor(uint64_t settled, int after) { return after >= 0 && settled >= (uint64_t)after; }
+// The value spec of a types spec: the flat form compiled for rows, with a texParams table small enough to compile in.
+// Scenes of the Cornell plugin set only (cubes, spheres, the box; matte and mirror; no textures, no lights): the form
+// that was measured and that the parity tests run with constant rows. A flat-form kernel of a wider set (SAIL_DEBUG_JIT
+// without bit 8) would read its light sampler's geometry rows, textures and a full texParams table through the constant
+// tables too, which no test covers: it keeps its types kernel.
+bool valueSpecFor(const SailJitSpec& types, const std::vector<uint32_t>& rowWords, const float* tp, int tn, SailJitSpec* out) {
+  const bool cornellSet = (types.ks & ~SAIL_KSET_CORNELL_SHAPES) == 0 && (types.km & ~SAIL_KSET_CORNELL_MATS) == 0 &&
+                          (types.kt & ~SAIL_KSET_CORNELL_TEX) == 0 && types.kl == 0;
+  if (!cornellSet || types.mode != SAIL_JIT_MODE_FLAT || types.rows <= 0 || types.tn != 0 || tn < 0 || tn > kSailJitMaxFlatTp ||
+      rowWords.size() != (size_t)types.rows * 32 || (tn > 0 && !tp))
+    return false;
+  *out = types;
+  out->rowWords = rowWords;
+  out->tpWords.resize((size_t)tn * 16);
+  if (tn > 0) memcpy(out->tpWords.data(), tp, sizeof(float) * 16 * (size_t)tn);
+  return true;
+}
+// Ask for the scene's value kernel once it has settled (after every refreshJit, and between and after launches): the build
+// starts in the background, or the object loads here when a disk cache has it, as refreshJit does for the types kernel.
+void refreshValues(sail_ctx* c) {
+  if (!c->subs.empty() || c->valHave || !c->jitHave || !settledFor(c->settled, c->jitValuesAfter)) return;
+  SailJitSpec spec;
+  if (!valueSpecFor(c->jitSpec, c->rowWords, c->tpRows.data(), c->tn, &spec)) return;
+  sail_jit_hold(c->device, spec, +1);
+  c->valHave = true;
+  c->valSpec = spec;
+  c->valState = SAIL_KERNEL_JIT_PENDING;
+  std::string err;
+  const int r = sail_jit_kernels(c->device, spec, 0, &c->valK, &err);
+  if (r == 0) c->valState = SAIL_KERNEL_JIT_READY;
+  else if (r < 0) c->valState = SAIL_KERNEL_JIT_FAILED;  // the types kernel serves
+}
+// The loaded value kernel, waiting up to wait_ms for its build (launches pass 0: none waits for it)
+bool valueKernels(sail_ctx* c, int wait_ms, SailJitKernel* k, int* mode) {
+  if (!c->valHave || c->valState == SAIL_KERNEL_JIT_FAILED) return false;
+  if (c->valState != SAIL_KERNEL_JIT_READY) {
+    std::string err;
+    const int r = sail_jit_kernels(c->device, c->valSpec, wait_ms, &c->valK, &err);
+    if (r == 1) return false;
+    if (r < 0) { c->valState = SAIL_KERNEL_JIT_FAILED; return false; }
+    c->valState = SAIL_KERNEL_JIT_READY;
+  }
+  *k = c->valK;
+  *mode = c->jitMode;
+  return true;
+}
 // Re-derive the scene's run-time kernel after anything it depends on changed (scene, rows, switches). A new spec starts
 // its background build now (Tracer.update links the scene's program, tracer.js:42-90), so the caller never waits for it.
 void refreshJit(sail_ctx* c) {
@@ -376,6 +455,7 @@ void refreshJit(sail_ctx* c) {
   int mode = 0;
   const bool have = jitSpecFor(c, &spec, &mode);
   if (have == c->jitHave && (!have || sailJitSpecEqual(spec, c->jitSpec))) return;
+  dropValues(c);  // the value kernel is the old spec's
   // hold the new spec before dropping the old one: a build both share is never skipped in between
   if (have) sail_jit_hold(c->device, spec, +1);
   if (c->jitHave) sail_jit_hold(c->device, c->jitSpec, -1);
@@ -884,7 +964,8 @@ int launchTrace(sail_ctx* c, const SailSample* hs, int count, int maxBounces) {
     const bool wavefront = c->wavefront && A.kernelSet == SAIL_KSET_GENERIC && A.cullPrims;
     SailJitKernel jk;
     int jmode = 0;
-    const bool jit = !wavefront && jitKernels(c, c->jitWait, &jk, &jmode);
+    refreshValues(c);  // the settle count may have crossed its threshold with the launch before
+    const bool jit = !wavefront && (valueKernels(c, 0, &jk, &jmode) || jitKernels(c, c->jitWait, &jk, &jmode));
     // samples of each pixel in flight per workgroup (the run-time kernels' spec; the precompiled kernels hold one):
     // NS times the workgroups of one sample in flight, each NS times shorter
     const int ns = jit ? c->jitSpec.ns : 1;
@@ -980,7 +1061,9 @@ int launchTrace(sail_ctx* c, const SailSample* hs, int count, int maxBounces) {
     c->lastWavefront = wavefront;
     c->launches++;
     c->nominalSegments += (uint64_t)px * (uint64_t)nspp * (uint64_t)maxBounces;
+    c->settled += (uint64_t)nspp;
   }
+  refreshValues(c);
   return SAIL_OK;
 }
 
@@ -1184,10 +1267,17 @@ int sail_get_kernel_info(sail_ctx* c, sail_kernel_info* out) {
     int m;
     (void)jitKernels(c, 0, &k, &m);
   }
-  out->jit_state = c->jitState;
-  out->jit_build_id = c->jitState == SAIL_KERNEL_JIT_READY ? c->jitK.buildId : 0;
-  out->jit_compile_ms = c->jitK.compileMs;
-  out->jit_from_cache = c->jitK.fromCache;
+  {  // the same for the value kernel: once it is loaded it is the scene's run-time kernel (the next launch uses it)
+    SailJitKernel k;
+    int m;
+    if (c->valState == SAIL_KERNEL_JIT_PENDING) (void)valueKernels(c, 0, &k, &m);
+  }
+  const bool val = c->valHave && c->valState == SAIL_KERNEL_JIT_READY;
+  const SailJitKernel& jk = val ? c->valK : c->jitK;
+  out->jit_state = val ? SAIL_KERNEL_JIT_READY : c->jitState;
+  out->jit_build_id = (val || c->jitState == SAIL_KERNEL_JIT_READY) ? jk.buildId : 0;
+  out->jit_compile_ms = jk.compileMs;
+  out->jit_from_cache = jk.fromCache;
   snprintf(out->jit_error, sizeof out->jit_error, "%s", c->jitError.c_str());
   return SAIL_OK;
 }
@@ -1208,7 +1298,9 @@ int sail_kernel_ready(sail_ctx* c, int timeout_ms, int* ready) {
   if (!c->haveScene) return fail(c, SAIL_E_STATE, "sail_kernel_ready: no scene");
   SailJitKernel k;
   int m;
-  *ready = jitKernels(c, timeout_ms, &k, &m) ? 1 : 0;
+  // the best tier asked for so far: the value kernel once the scene has settled, else the types kernel
+  if (c->valHave && c->valState != SAIL_KERNEL_JIT_FAILED) *ready = valueKernels(c, timeout_ms, &k, &m) ? 1 : 0;
+  else *ready = jitKernels(c, timeout_ms, &k, &m) ? 1 : 0;
   return SAIL_OK;
 }
 
@@ -1283,6 +1375,7 @@ void sail_destroy(sail_ctx* c) {
     return;
   }
   if (c->device >= 0) (void)hipSetDevice(c->device);
+  dropValues(c);
   if (c->jitHave) sail_jit_hold(c->device, c->jitSpec, -1);  // its queued build, if any, is no longer needed
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->comm && g_rccl.commDestroy) g_rccl.commDestroy(c->comm);
@@ -1389,6 +1482,10 @@ int sail_set_debug(sail_ctx* c, int option, int value) {
       if (value < -1) return fail(c, SAIL_E_INVALID, "sail_set_debug: jit wait must be >= -1");
       c->jitWait = value;
       break;
+    case SAIL_DEBUG_JIT_VALUES_AFTER:
+      c->jitValuesAfter = value;
+      if (value < 0) { const uint64_t s = c->settled; dropValues(c); c->settled = s; }  // never: back to the types kernel
+      break;
     case SAIL_DEBUG_GROUP_ROUNDS:
       if (value <= 0) return fail(c, SAIL_E_INVALID, "sail_set_debug: group rounds must be > 0");
       c->flatGroupRounds = value;
@@ -1400,6 +1497,7 @@ int sail_set_debug(sail_ctx* c, int option, int value) {
     default: return fail(c, SAIL_E_INVALID, "sail_set_debug: unknown option %d", option);
   }
   refreshJit(c);  // the switches decide which run-time kernel (if any) the scene gets
+  refreshValues(c);
   return SAIL_OK;
 }
 
@@ -1417,6 +1515,8 @@ static int uploadPrims(sail_ctx* c, const std::vector<SailPrim>& prims) {
   for (int i = 0; i < n; i++)
     if (prims[i].type >= 0 && prims[i].type < 16) c->typeMasksHost[(size_t)(i / 64) * 16 + prims[i].type] |= 1ull << (i % 64);
   HIPCHK(c, hipMemcpyAsync(c->prims, prims.data(), sizeof(SailPrim) * n, hipMemcpyHostToDevice, c->stream));
+  c->rowWords.resize((size_t)n * 32);  // what a value kernel compiles in (refreshValues)
+  memcpy(c->rowWords.data(), prims.data(), sizeof(SailPrim) * (size_t)n);
   HIPCHK(c, hipMemcpyAsync(c->prims + n, c->typeMasksHost.data(), chunks * 16 * sizeof(unsigned long long),
                            hipMemcpyHostToDevice, c->stream));
   return SAIL_OK;
@@ -1479,7 +1579,9 @@ int sail_set_scene(sail_ctx* c, const float* objects, int n, const float* texpar
   c->tpHaveCur = c->tpHavePrev = false;  // the temporal maps' ids and positions are stale
   // Tracer.update links the scene's program (tracer.js:42-90): the plugin set's kernel starts building now, in the
   // background; the precompiled kernel of the set serves until it is loaded
+  dropValues(c);
   refreshJit(c);
+  refreshValues(c);
   return resetAccum(c);
 }
 
@@ -1507,7 +1609,9 @@ int sail_update_objects(sail_ctx* c, const float* objects, int n) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->objectsRows.assign(objects, objects + (size_t)n * 18);
   c->tpHaveCur = c->tpHavePrev = false;  // the temporal maps' ids and positions are stale
-  refreshJit(c);  // a drag keeps the kernel; a changed shape type starts the new rows' kernel building
+  dropValues(c);  // the rows' values moved: the value kernel goes, the settle count restarts
+  refreshJit(c);  // a drag keeps the types kernel; a changed shape type starts the new rows' kernel building
+  refreshValues(c);
   return resetAccum(c);
 }
 
@@ -1545,6 +1649,7 @@ int sail_set_partition(sail_ctx* c, int rank, int world, int mode) {
   HIPCHK(c, hipSetDevice(c->device));
   c->rank = rank; c->world = world; c->partMode = mode;
   refreshJit(c);  // the Cornell form's samples in flight follow the share of the frame (jitNsFor)
+  refreshValues(c);
   return resetAccum(c);
 }
 
@@ -2535,7 +2640,10 @@ int sail_jit_prebuild(const float* objects, int n, const float* texparams, int t
   std::vector<SailPrim> prims;
   int anyHit = 0;
   decodePrims(objects, n, tn, plugins->shape_mask, prims, &anyHit, nullptr);
+  fillCats(prims, texparams, tn);  // the rows as sail_set_scene uploads them: the value kernel compiles them in
   for (const SailPrim& q : prims) t.primTypes.push_back(q.type);
+  std::vector<uint32_t> rowWords((size_t)n * 32);
+  if (n > 0) memcpy(rowWords.data(), prims.data(), sizeof(SailPrim) * (size_t)n);
   SailJitSpec spec;
   int mode = 0;
   if (built) *built = 0;
@@ -2546,9 +2654,54 @@ int sail_jit_prebuild(const float* objects, int n, const float* texparams, int t
   for (int ns : {16, 1}) {
     if (cornell) spec.ns = ns;
     if (sail_jit_code_to_dir(arch, spec, dir, &err)) return fail(nullptr, SAIL_E_INVALID, "sail_jit_prebuild: %s", err.c_str());
+    // and the value kernel a context loads once the scene has settled, where the spec has one
+    SailJitSpec vspec;
+    if (valueSpecFor(spec, rowWords, texparams, tn, &vspec) && sail_jit_code_to_dir(arch, vspec, dir, &err))
+      return fail(nullptr, SAIL_E_INVALID, "sail_jit_prebuild: %s", err.c_str());
     if (!cornell) break;
   }
   if (built) *built = 1;
+  return SAIL_OK;
+}
+
+int sail_plan_settle(uint64_t settled, int after) { return settledFor(settled, after) ? 1 : 0; }
+
+int sail_jit_resident(int* code_objects, int* modules) {
+  if (!code_objects || !modules) return SAIL_E_INVALID;
+  sail_jit_resident_values(code_objects, modules);
+  return SAIL_OK;
+}
+
+int sail_jit_value_key(const float* objects, int n, const float* texparams, int tn, const sail_plugins* plugins,
+                       const char* arch, uint64_t* key, char* defs, size_t* defs_len) {
+  if (n < 1 || tn < 1 || !objects || !texparams || !plugins || !arch || !key)
+    return fail(nullptr, SAIL_E_INVALID, "sail_jit_value_key: bad arguments");
+  // as sail_jit_prebuild: the spec a context with the product's defaults derives, without a device
+  sail_ctx t;
+  t.plugins = *plugins;
+  t.n = n; t.tn = tn;
+  t.haveScene = true;
+  std::vector<SailPrim> prims;
+  int anyHit = 0;
+  decodePrims(objects, n, tn, plugins->shape_mask, prims, &anyHit, nullptr);
+  fillCats(prims, texparams, tn);
+  for (const SailPrim& q : prims) t.primTypes.push_back(q.type);
+  std::vector<uint32_t> rowWords((size_t)n * 32);
+  memcpy(rowWords.data(), prims.data(), sizeof(SailPrim) * (size_t)n);
+  SailJitSpec spec, vspec;
+  int mode = 0;
+  *key = 0;
+  if (!jitSpecFor(&t, &spec, &mode) || !valueSpecFor(spec, rowWords, texparams, tn, &vspec)) {
+    if (defs_len) *defs_len = 0;
+    return SAIL_OK;  // the scene gets no value kernel
+  }
+  std::string text, err;
+  if (sail_jit_key(arch, vspec, key, &text, &err)) return fail(nullptr, SAIL_E_INVALID, "sail_jit_value_key: %s", err.c_str());
+  if (defs_len) {
+    const size_t have = *defs_len;
+    *defs_len = text.size() + 1;
+    if (defs && have >= text.size() + 1) memcpy(defs, text.c_str(), text.size() + 1);
+  }
   return SAIL_OK;
 }
 

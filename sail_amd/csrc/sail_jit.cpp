@@ -21,6 +21,7 @@
 // (tests/test_jit_compile.py checks instruction identity after importing torch). A code object produced by another
 // compiler than the one this library was built with is refused (sameCompiler; the precompiled kernels serve).
 #include <ctype.h>
+#include <dirent.h>
 #include <dlfcn.h>
 #include <pthread.h>
 #include <errno.h>
@@ -55,19 +56,21 @@ int sailJitThreads(const SailJitSpec& s) { return s.nt ? s.nt : (s.mode == 1 ? 1
 bool sailJitSpecEqual(const SailJitSpec& a, const SailJitSpec& b) {
   const auto t = [](const SailJitSpec& x) {
     return std::tie(x.ks, x.km, x.kt, x.kl, x.mode, x.waves, x.rows, x.ldsFit, x.tn, x.ns, x.nt, x.types[0], x.types[1], x.types[2],
-                    x.types[3], x.types[4], x.types[5], x.types[6], x.types[7]);
+                    x.types[3], x.types[4], x.types[5], x.types[6], x.types[7], x.rowWords, x.tpWords);
   };
   return t(a) == t(b);
 }
 
 namespace {
 
+bool isValue(const SailJitSpec& s) { return !s.rowWords.empty(); }
+
 struct Key {
   SailJitSpec s;
   bool operator<(const Key& o) const {
     const auto t = [](const SailJitSpec& x) {
       return std::tie(x.ks, x.km, x.kt, x.kl, x.mode, x.waves, x.rows, x.ldsFit, x.tn, x.ns, x.nt, x.types[0], x.types[1], x.types[2],
-                      x.types[3], x.types[4], x.types[5], x.types[6], x.types[7]);
+                      x.types[3], x.types[4], x.types[5], x.types[6], x.types[7], x.rowWords, x.tpWords);
     };
     return t(s) < t(o.s);
   }
@@ -101,6 +104,19 @@ const char* const kOpts[] = {"-O3", "-std=c++17", "-ffp-contract=off", "-fno-fas
 std::string defsFor(const SailJitSpec& sp) {
   std::string types;
   for (int i = 0; i < sp.rows; i++) types += (i ? ", " : "") + std::to_string(sp.types[i]);
+  // a value kernel's rows and texParams table, as words (a float literal could not carry -0, NaN payloads or denormals
+  // bit for bit); in front, so that the text after them is the types kernel's
+  std::string vals;
+  if (!sp.rowWords.empty()) {
+    const auto list = [](const std::vector<uint32_t>& w) {
+      std::string s;
+      char b[16];
+      for (size_t i = 0; i < w.size(); i++) { snprintf(b, sizeof b, i ? ", 0x%08xu" : "0x%08xu", w[i]); s += b; }
+      return s.empty() ? std::string("0u") : s;
+    };
+    vals = "#define SAIL_JIT_ROWVALS 1\n#define SAIL_JIT_TPN " + std::to_string(sp.tpWords.size() / 16) +
+           "\n#define SAIL_JIT_ROW_WORDS " + list(sp.rowWords) + "\n#define SAIL_JIT_TP_WORDS " + list(sp.tpWords) + "\n";
+  }
   char defs[768];
   snprintf(defs, sizeof defs,
            "#define SAIL_JIT 1\n#define SAIL_JIT_WAVES %d\n#define SAIL_JIT_CULL %d\n#define SAIL_JIT_FAM %d\n"
@@ -110,7 +126,7 @@ std::string defsFor(const SailJitSpec& sp) {
            sp.waves, sp.mode == 1, sp.mode == 2, sp.ks, sp.km, sp.kt, sp.kl, sailJitThreads(sp), sp.rows,
            sp.rows ? types.c_str() : "0", sp.ldsFit, sp.tn, sp.ns);
   // the phase-timing build compiles its run-time kernels instrumented as well (their own g_sailPhase)
-  return sail_trace_phase_timing ? std::string("#define SAIL_PHASE_TIMING 1\n") + defs : std::string(defs);
+  return (sail_trace_phase_timing ? std::string("#define SAIL_PHASE_TIMING 1\n") : std::string()) + vals + defs;
 }
 
 // hipRTC entry points from the toolchain's library (SAIL_HIPRTC, else $ROCM_PATH or /opt/rocm, lib/libhiprtc.so.7)
@@ -203,9 +219,18 @@ uint64_t cacheKey(const std::string& arch, const Key& k) {
   return h;
 }
 constexpr char kMagic[8] = {'S', 'A', 'I', 'L', 'J', 'I', 'T', '1'};
-bool cacheRead(const std::string& dir, uint64_t key, std::vector<char>& code) {
-  if (dir.empty()) return false;
-  FILE* f = fopen((dir + "/" + hex16(key) + ".co").c_str(), "rb");
+// A cache directory holds the types kernels' objects, as it always has; the value kernels' objects live in a directory of
+// their own beside it, <dir>-values: one object per pose of a scene at rest, counted and pruned apart (pruneValues).
+std::string objName(uint64_t key) { return hex16(key) + ".co"; }
+std::string objDir(const std::string& dir, bool value) {
+  if (dir.empty() || !value) return dir;
+  const size_t e = dir.find_last_not_of('/');
+  return (e == std::string::npos ? dir : dir.substr(0, e + 1)) + "-values";
+}
+bool cacheRead(const std::string& base, uint64_t key, bool value, std::vector<char>& code) {
+  if (base.empty()) return false;
+  const std::string dir = objDir(base, value);
+  FILE* f = fopen((dir + "/" + objName(key)).c_str(), "rb");
   if (!f) return false;
   char magic[8];
   uint64_t hdr[3];  // key, payload size, payload hash
@@ -219,10 +244,30 @@ bool cacheRead(const std::string& dir, uint64_t key, std::vector<char>& code) {
   if (!ok) code.clear();
   return ok;
 }
-void cacheWrite(const std::string& dir, uint64_t key, const std::vector<char>& code) {
-  if (dir.empty() || code.empty()) return;
+// The user's cache holds at most kSailJitMaxValueObjects value-kernel objects: before one more is written, the oldest by
+// modification time go (an object another process is reading stays readable: it is unlinked, not truncated). dir: the
+// value objects' directory; types kernels' objects are in another and never touched.
+void pruneValues(const std::string& dir, const std::string& keep) {
+  DIR* d = opendir(dir.c_str());
+  if (!d) return;
+  std::vector<std::pair<std::pair<long long, long long>, std::string>> objs;  // ((mtime s, ns), name)
+  while (const dirent* e = readdir(d)) {
+    const std::string nm = e->d_name;
+    if (nm.size() != 19 || nm.compare(16, 3, ".co") != 0 || nm == keep) continue;
+    struct stat st;
+    if (stat((dir + "/" + nm).c_str(), &st) == 0) objs.push_back({{(long long)st.st_mtim.tv_sec, (long long)st.st_mtim.tv_nsec}, nm});
+  }
+  closedir(d);
+  std::sort(objs.begin(), objs.end());
+  for (size_t i = 0; i + (size_t)kSailJitMaxValueObjects <= objs.size(); i++) (void)unlink((dir + "/" + objs[i].second).c_str());
+}
+// prune: the user's cache (value objects are capped there, not in a directory a caller names or the shipped one)
+void cacheWrite(const std::string& base, uint64_t key, bool value, const std::vector<char>& code, bool prune = false) {
+  if (base.empty() || code.empty()) return;
+  const std::string dir = objDir(base, value);
   mkdirs(dir);
-  const std::string fin = dir + "/" + hex16(key) + ".co";
+  if (value && prune) pruneValues(dir, objName(key));
+  const std::string fin = dir + "/" + objName(key);
   const std::string tmp = fin + "." + std::to_string((long)getpid()) + "." +
                           std::to_string((unsigned long long)std::hash<std::thread::id>()(std::this_thread::get_id())) + ".tmp";
   FILE* f = fopen(tmp.c_str(), "wb");
@@ -293,6 +338,13 @@ bool validSpec(const SailJitSpec& sp, std::string* err) {
             (sp.ns == 1 || sp.ns == 4 || sp.ns == 16) &&
             (sp.nt == 0 || sp.nt == 128 || sp.nt == 256 || sp.nt == 512 || sp.nt == 1024) && sailJitThreads(sp) / sp.ns >= 16;
   for (int i = 0; ok && i < sp.rows; i++) ok = sp.types[i] >= 1 && sp.types[i] <= 9 && ((sp.ks >> sp.types[i]) & 1u);
+  // a value kernel: the flat form with rows and no LDS table copies, 32 words per row whose first is the row's type, and
+  // whole texParams rows
+  if (ok && (isValue(sp) || !sp.tpWords.empty())) {
+    ok = sp.mode == 0 && sp.rows > 0 && sp.tn == 0 && sp.rowWords.size() == (size_t)sp.rows * 32 &&
+         sp.tpWords.size() % 16 == 0 && sp.tpWords.size() <= (size_t)kSailJitMaxFlatTp * 16;
+    for (int i = 0; ok && i < sp.rows; i++) ok = sp.rowWords[(size_t)i * 32] == (uint32_t)sp.types[i];
+  }
   if (!ok) *err = "invalid kernel specialisation";
   return ok;
 }
@@ -362,10 +414,10 @@ void finish(Entry& e, std::vector<char>& code, const std::string& err, double ms
   e.cv.notify_all();
 }
 // A code object from the disk caches (the shipped one first), checked: 2 shipped, 1 user, 0 none
-int cacheLookup(uint64_t key, std::vector<char>& code) {
+int cacheLookup(uint64_t key, bool value, std::vector<char>& code) {
   std::string err;
-  if (cacheRead(shippedCacheDir(), key, code) && sameCompiler(code, err)) return 2;
-  if (cacheRead(userCacheDir(), key, code) && sameCompiler(code, err)) return 1;
+  if (cacheRead(shippedCacheDir(), key, value, code) && sameCompiler(code, err)) return 2;
+  if (cacheRead(userCacheDir(), key, value, code) && sameCompiler(code, err)) return 1;
   code.clear();
   return 0;
 }
@@ -380,8 +432,8 @@ void buildEntry(const std::shared_ptr<Entry>& e, const std::string& arch, const 
     if (compile(*R, arch, k, code, err) == 0 && sameCompiler(code, err)) {
       ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
       err.clear();
-      cacheWrite(userCacheDir(), key, code);
-      if (!extraDir.empty()) cacheWrite(extraDir, key, code);
+      cacheWrite(userCacheDir(), key, isValue(k.s), code, true);
+      if (!extraDir.empty()) cacheWrite(extraDir, key, isValue(k.s), code);
     } else {
       code.clear();
     }
@@ -443,6 +495,9 @@ void* buildWorker(void* arg) {
     }
     if (stillWanted(*j)) {
       buildEntry(j->e, j->arch, j->k, j->extraDir);
+      // a value kernel whose context moved on while it was being compiled: the object is in the disk caches, the copy
+      // in memory goes (releaseValue's rule)
+      if (isValue(j->k.s)) (void)stillWanted(*j);
       delete j;
     } else {
       dropJob(j, "build dropped: no context holds this kernel any more");
@@ -515,8 +570,8 @@ std::shared_ptr<Entry> request(const std::string& arch, const Key& k, bool pinne
   const uint64_t key = cacheKey(arch, k);
   if (getenv("SAIL_JIT_DEFS"))  // tooling (tools/isa.sh): the source prefix of this spec, to rebuild it with hipcc
     fprintf(stderr, "sail_jit %s %s\n%s", arch.c_str(), hex16(key).c_str(), defsFor(k.s).c_str());
-  if (const int from = cacheLookup(key, code)) {
-    if (!extraDir.empty()) cacheWrite(extraDir, key, code);
+  if (const int from = cacheLookup(key, isValue(k.s), code)) {
+    if (!extraDir.empty()) cacheWrite(extraDir, key, isValue(k.s), code);
     finish(*e, code, "", 0.0, from);
     return e;
   }
@@ -631,19 +686,79 @@ int sail_jit_code_to_dir(const char* arch, const SailJitSpec& spec, const char* 
   if (dir && *dir) {  // an entry made earlier in this process wrote only the user cache: write this directory too
     std::vector<char> have;
     const uint64_t key = cacheKey(arch, Key{spec});
-    if (!cacheRead(dir, key, have)) cacheWrite(dir, key, e->code);
+    if (!cacheRead(dir, key, isValue(spec), have)) cacheWrite(dir, key, isValue(spec), e->code);
   }
   return 0;
+}
+
+int sail_jit_key(const char* arch, const SailJitSpec& spec, uint64_t* key, std::string* defs, std::string* err) {
+  if (!validSpec(spec, err)) return -1;
+  *key = cacheKey(arch, Key{spec});
+  if (defs) *defs = defsFor(spec);
+  return 0;
+}
+
+// A value kernel is one per pose of a scene at rest, so what the process keeps of it is bounded by the contexts that hold
+// one, not by the poses seen: when the last hold on a value spec goes, its code object leaves g_code (one that is still
+// being built leaves when the worker is done with it) and its modules are unloaded on every device of that arch. The
+// object stays in the disk caches for a scene that returns to the pose. Types kernels (bounded by the plugin sets and
+// row types) stay for the life of the process, as before. The caller has synchronised the streams that ran the kernel.
+// Lock order: g_loadMutex, then g_mapMutex (the hold count is checked again under both: a context that took a new hold
+// meanwhile keeps the module, and one that takes it later finds none and loads afresh).
+void releaseValue(const std::string& arch, const Key& k) {
+  std::lock_guard<std::mutex> ll(g_loadMutex);
+  {
+    std::lock_guard<std::mutex> lk(g_mapMutex);
+    const auto h = g_holds.find({arch, k});
+    if (h != g_holds.end() && h->second > 0) return;
+    const auto it = g_code.find({arch, k});
+    if (it != g_code.end() && !it->second->pinned) {
+      std::lock_guard<std::mutex> le(it->second->m);
+      if (it->second->state != 0) g_code.erase(it);  // a running build erases its own (buildWorker)
+    }
+  }
+  int cur = 0;
+  const bool haveCur = hipGetDevice(&cur) == hipSuccess;
+  for (auto it = g_loaded.begin(); it != g_loaded.end();) {
+    bool same = !(it->first.second < k) && !(k < it->first.second);
+    if (same) {
+      std::lock_guard<std::mutex> la(g_archMutex);
+      const auto a = g_arch.find(it->first.first);
+      same = a != g_arch.end() && a->second == arch;
+    }
+    if (!same) { ++it; continue; }
+    if (hipSetDevice(it->first.first) == hipSuccess) (void)hipModuleUnload(it->second.mod);
+    it = g_loaded.erase(it);
+  }
+  if (haveCur) (void)hipSetDevice(cur);
 }
 
 void sail_jit_hold(int device, const SailJitSpec& spec, int delta) {
   std::string arch, err;
   if (deviceArch(device, arch, &err)) return;
-  std::lock_guard<std::mutex> lk(g_mapMutex);
-  const auto key = std::make_pair(arch, Key{spec});
-  int& h = g_holds[key];
-  h += delta;
-  if (h <= 0) g_holds.erase(key);
+  bool gone;
+  {
+    std::lock_guard<std::mutex> lk(g_mapMutex);
+    const auto key = std::make_pair(arch, Key{spec});
+    int& h = g_holds[key];
+    h += delta;
+    gone = h <= 0;
+    if (gone) g_holds.erase(key);
+  }
+  if (gone && isValue(spec)) releaseValue(arch, Key{spec});
+}
+
+void sail_jit_resident_values(int* code_objects, int* modules) {
+  {
+    std::lock_guard<std::mutex> lk(g_mapMutex);
+    int n = 0;
+    for (const auto& kv : g_code) n += isValue(kv.first.second.s) ? 1 : 0;
+    *code_objects = n;
+  }
+  std::lock_guard<std::mutex> ll(g_loadMutex);
+  int m = 0;
+  for (const auto& kv : g_loaded) m += isValue(kv.first.second.s) ? 1 : 0;
+  *modules = m;
 }
 
 void sail_jit_set_cache_dir(const char* dir) {

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
+#include <vector>
 
 constexpr int kSailJitMaxRows = 8;  // scenes of at most this many rows can be compiled for their rows (flat path)
 constexpr int kSailJitMaxFlatTp = 32;  // flat forms copy texParams tables of at most this many rows into LDS
@@ -16,6 +17,11 @@ struct SailJitSpec {
   int ns = 1;                               // samples of each pixel in flight per workgroup (1, 4, 16: traceTileCompact)
   int nt = 0;                               // threads per workgroup (128 .. 1,024); 0 = the form's own (1,024 pre-cull, 256)
   int types[kSailJitMaxRows] = {};
+  // A value kernel (flat form with rows, SAIL_JIT_ROWVALS in sail_trace.hip): the words of the decoded rows (rows x 32,
+  // the bytes of the SailPrim array the host uploads) and of the texParams table (16 per row, at most kSailJitMaxFlatTp
+  // rows; may be none). Both empty: the types kernel. Compared and keyed as words, never as floats: +0 / -0 and two NaN
+  // payloads are different kernels.
+  std::vector<uint32_t> rowWords, tpWords;
 };
 bool sailJitSpecEqual(const SailJitSpec& a, const SailJitSpec& b);
 int sailJitThreads(const SailJitSpec& s);  // threads per workgroup of the spec's kernels
@@ -35,12 +41,25 @@ int sail_jit_kernels(int device, const SailJitSpec& spec, int wait_ms, SailJitKe
 // A context's claim on the kernel of `spec` on `device` (delta +1 when it adopts the spec, -1 when it drops it): a queued
 // build of a spec no context holds any more is skipped by the build worker, so the scene's current kernel never waits
 // behind builds of specs that a newer scene, partition or switch replaced.
+// Dropping the last hold on a value spec (rowWords not empty) also unloads its modules and frees its code object in
+// memory (the object stays in the disk caches): the caller synchronises the streams that ran it first.
 void sail_jit_hold(int device, const SailJitSpec& spec, int delta);
 // host only: the code object for `arch`, built by the same path (sail_jit_compile, sail_jit_prebuild); blocks
 int sail_jit_code(const char* arch, const SailJitSpec& spec, void* code, size_t* bytes, std::string* err);
 // the on-disk code-object cache directory: nullptr = the default ($XDG_CACHE_HOME or $HOME/.cache, /sail_amd/jit),
 // "" = none (sail_set_jit_cache); `dir` of sail_jit_code / prebuild when it is not null
 void sail_jit_set_cache_dir(const char* dir);
+// The user's cache keeps at most this many value-kernel objects (a scene at rest in a new pose is a new object): writing
+// one more deletes the oldest by modification time. 32 is a choice, not a measurement. Value objects live in a directory
+// of their own beside each cache directory (<dir>-values), so types kernels are not counted and never deleted by this
+// rule; the cache shipped with the library is never pruned.
+constexpr int kSailJitMaxValueObjects = 32;
 int sail_jit_code_to_dir(const char* arch, const SailJitSpec& spec, const char* dir, std::string* err);
 // FNV-1a 64 of the library image plus a precompiled kernel's name: the build identity of a precompiled kernel
 uint64_t sail_precompiled_build_id(const char* kernel);
+// host only: the disk caches' key of `spec` for `arch` and, when defs is not null, the source prefix it is compiled with
+// (no compile; -1 for an invalid spec)
+int sail_jit_key(const char* arch, const SailJitSpec& spec, uint64_t* key, std::string* defs, std::string* err);
+// what the process keeps of value kernels: code objects in memory and loaded modules (all devices). Both fall back as
+// the last hold on a value spec is dropped (sail_jit_hold), so they are bounded by the contexts that hold one.
+void sail_jit_resident_values(int* code_objects, int* modules);

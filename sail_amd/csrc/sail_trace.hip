@@ -185,12 +185,42 @@ struct Ctx {
 // a wave-uniform primitive read becomes a per-lane vector load (VGPRs + TA cycles) instead of a scalar load.
 template <typename T> using ConstAS = const __attribute__((address_space(4))) T;
 template <typename T> D const T& constRow(const T* base, int i) { return *(const T*)((ConstAS<T>*)base + i); }
+// A flat kernel compiled at run time for a settled scene's row values (SAIL_JIT_ROWVALS, sail_jit.cpp; the host asks for
+// it once the rows have stood still for a while, sail_capi.cpp refreshValues) carries the decoded rows and the
+// texParams table as word lists in its source prefix: the bytes of the arrays the host uploads, bit for bit (-0, NaN
+// payloads, denormals). gfx950 has no scalar float ALU, so every wave-uniform float expression on row data (mn + 1e-4,
+// c - rad, rad * rad, rev ? -nd : nd) is a VALU instruction per wave and bounce, and the loaded rows live in SGPRs that
+// spill through v_writelane: with the rows constant, those expressions fold and the loads go. Same operations on the
+// same operands, so the frames are those of the types kernel (tests/test_gpu_jit_values.py).
+#if defined(SAIL_JIT) && defined(SAIL_JIT_ROWVALS) && SAIL_JIT_ROWVALS && SAIL_JIT_N > 0
+#define SAIL_ROWVALS 1
+template <class... T> constexpr int wordCount(T...) { return (int)sizeof...(T); }
+static_assert(sizeof(SailPrim) == 128, "a row is 32 words");
+static_assert(wordCount(SAIL_JIT_ROW_WORDS) == SAIL_JIT_N * 32, "32 words per row");
+constexpr int kTpC = SAIL_JIT_TPN;  // texParams rows compiled in (0: the scene has none)
+static_assert(wordCount(SAIL_JIT_TP_WORDS) == (kTpC > 0 ? kTpC * 16 : 1), "16 words per texParams row");
+struct PrimWordsC { uint32_t w[SAIL_JIT_N * 32]; };
+struct PrimTabC { SailPrim r[SAIL_JIT_N]; };
+struct TpWordsC { uint32_t w[kTpC > 0 ? kTpC * 16 : 1]; };
+struct TpTabC { float v[kTpC > 0 ? kTpC * 16 : 1]; };
+constexpr PrimWordsC kPrimW = {{SAIL_JIT_ROW_WORDS}};
+constexpr TpWordsC kTpW = {{SAIL_JIT_TP_WORDS}};
+constexpr PrimTabC kPrimTab = __builtin_bit_cast(PrimTabC, kPrimW);
+constexpr TpTabC kTpTab = __builtin_bit_cast(TpTabC, kTpW);
+#define PRIM(c, i) (kPrimTab.r[(i)])
+#else
+#define SAIL_ROWVALS 0
 #define PRIM(c, i) constRow<SailPrim>((c).prims, (i))
+#endif
 
 D V3 P3(const SailPrim& p, int k) { return v3(p.a[k], p.a[k + 1], p.a[k + 2]); }
 D float TP(const Ctx& c, int row, int col) {
+#if SAIL_ROWVALS
+  return kTpTab.v[row * 16 + col];
+#else
   if (c.tpCopy) return c.tpl[row * 16 + col];  // kernels with table copies in LDS (compile-time)
   return constRow<float>(c.tp, row * 16 + col);
+#endif
 }
 D V3 TP3(const Ctx& c, int row, int col) { return v3(TP(c, row, col), TP(c, row, col + 1), TP(c, row, col + 2)); }
 
@@ -1143,9 +1173,36 @@ D Hit hitRecord(const Ctx& c, const Ray& r, const Sweep& sw) {
   return h;
 }
 // wave-uniform winner: the same record with the row index in an SGPR (scalar row loads)
+#if SAIL_ROWVALS
+// Scenes of at most this many rows get one hit-record instance per row in a kernel compiled for their values (each
+// folds to one shape, one material category, constant operands); with more rows the per-row copies outgrow what they
+// save, and only the sweep, the key, the AOV and quiet-row reads take the constants (the one generic record then reads
+// its row from the constant table). Measured on C1 variants at 1080p, ms per 1,024-sample frame, types kernel /
+// generic record on constant rows / a record per row (profiles/r08_rowmax.jsonl): 3 rows 161.6 / 157.5 / 155.6,
+// 4 rows 174.7 / 169.2 / 173.2, 5 rows 178.1 / 171.4 / 173.7, 7 rows 202.2 / 193.8 / 205.1.
+constexpr int kRowRecordMax = 3;
+// the record of row I for the lanes whose winner it is: pick by the scalar row index (U) or per lane
+template <int I, bool U, bool RECOMP_HL, bool BOXU>
+D void hitRecordRows(const Ctx& c, const Ray& r, const Sweep& sw, int b0, Hit& h) {
+  if constexpr (I + 1 < kRows) {
+    if ((U ? b0 : sw.bi) != I) { hitRecordRows<I + 1, U, RECOMP_HL, BOXU>(c, r, sw, b0, h); return; }
+  }
+  Sweep su = sw;
+  su.bi = I;  // a winner is one of the kernel's rows (hitRecord's precondition): the last row needs no test
+  h = hitRecord<RECOMP_HL, BOXU>(c, r, su);
+}
+#endif
 template <bool RECOMP_HL = false, bool BOXU = false>
 D Hit hitRecordU(const Ctx& c, const Ray& r, const Sweep& sw) {
   const int b0 = __builtin_amdgcn_readfirstlane(sw.bi);
+#if SAIL_ROWVALS
+  if constexpr (kRows <= kRowRecordMax) {
+    Hit h;
+    if (__all(sw.bi == b0)) hitRecordRows<0, true, RECOMP_HL, BOXU>(c, r, sw, b0, h);
+    else hitRecordRows<0, false, RECOMP_HL, BOXU>(c, r, sw, b0, h);
+    return h;
+  }
+#endif
   if (__all(sw.bi == b0)) {
     Sweep su = sw;
     su.bi = b0;
@@ -1816,6 +1873,9 @@ __device__ __forceinline__ void traceTileCompact(const SailTraceArgs& A) {
   if constexpr (kFlatLds) {
     if (A.n != kRows || A.tn != kFlatTp) return;  // never launched so (sail_capi.cpp jitKernels); uniform
   }
+#if SAIL_ROWVALS
+  if (A.n != kRows || A.tn != kTpC) return;  // never launched so (sail_capi.cpp valueKernels); uniform
+#endif
   if constexpr (kLdsRows > 0) {
     if (kLdsFitAll || kFlatLds || A.n <= kLdsRows) {  // uniform
       const float4* src = reinterpret_cast<const float4*>(A.prims);

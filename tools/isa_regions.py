@@ -6,7 +6,8 @@ instruction attributed through its inline stack (llvm-symbolizer --inlining) to 
 classed: f32 arithmetic, transcendental, f64, int / bit, compare, move / select / lane, other VALU; SALU; LDS; memory.
 Static counts (instructions in the code), per part of the bounce -- the dynamic weights are the phase timers' shares
 (tools/phase_profile.py) and the PMC instruction mix (tools/pmc_mix.sh).
-Usage: python tools/isa_regions.py C1 [--kernel sail_trace_kernel_jit] [--json out.json]"""
+Usage: python tools/isa_regions.py C1 [--kernel sail_trace_kernel_jit] [--values] [--json out.json]
+--values: the value kernel of the scene (the rows' values compiled in, SAIL_JIT_ROWVALS) instead of the types kernel"""
 import collections
 import glob
 import json
@@ -30,7 +31,7 @@ SHADE = [("random2", "hash RNG"), ("material", "BSDF sample"), ("lightSample", "
          ("lightPrep", "light + shadow"), ("mkRay", "next ray"), ("localToWorld", "next ray")]
 
 
-def defines(scene):
+def defines(scene, values=False):
     """the #define prefix of the run-time kernel a default context derives for the frozen scene (NS = the full-frame
     shape), from sail_jit_prebuild with SAIL_JIT_DEFS set (the cache key is printed with it)"""
     code = ("import json, sys; sys.path.insert(0, %r); from sail_amd import capi; capi.set_jit_cache(''); "
@@ -39,7 +40,8 @@ def defines(scene):
     err = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, SAIL_JIT_DEFS="1"), capture_output=True,
                          text=True, check=True).stderr
     blocks = re.findall(r"sail_jit (\S+) ([0-9a-f]{16})\n((?:#define [^\n]*\n)+)", err)
-    arch, key, defs = blocks[0]  # the first spec prebuilt is the full-frame one
+    # the first spec prebuilt is the full-frame one, its value kernel (if the scene has one) the next
+    arch, key, defs = [b for b in blocks if ("SAIL_JIT_ROWVALS" in b[2]) == values][0]
     return key, [("-D%s=%s" % tuple(d[len("#define "):].split(" ", 1))) for d in defs.strip().split("\n")]
 
 
@@ -112,7 +114,7 @@ def part(names, line):
 def main():
     scene = sys.argv[1]
     kernel = sys.argv[sys.argv.index("--kernel") + 1] if "--kernel" in sys.argv else None
-    key, defs = defines(scene)
+    key, defs = defines(scene, "--values" in sys.argv)
     if kernel is None:
         kernel = "sail_trace_kernel_cull_jit" if "-DSAIL_JIT_CULL=1" in defs else "sail_trace_kernel_jit"
     td = tempfile.mkdtemp()
@@ -121,7 +123,8 @@ def main():
     subprocess.run([LLVM + "/clang-offload-bundler", "--unbundle", "--type=o", "--input=" + td + "/t.o",
                     "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + td + "/t.co"], check=True)
     ins = instructions(td + "/t.co", kernel)
-    shipped = os.path.join(ROOT, "sail_amd", "lib", "jit", key + ".co")
+    # value kernels' objects live beside the cache directory, in jit-values
+    shipped = os.path.join(ROOT, "sail_amd", "lib", "jit-values" if "--values" in sys.argv else "jit", key + ".co")
     same = None
     if os.path.exists(shipped):
         open(td + "/s.co", "wb").write(open(shipped, "rb").read()[32:])  # SAILJIT1 header: magic + 3 words

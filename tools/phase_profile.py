@@ -40,6 +40,7 @@ def main():
         dbg = {int(k): int(v) for k, v in (o.split("=") for o in os.environ.get("PHASE_DEBUG", "").split(",") if o)}
         ctx = capi.Context(W, H, debug=dbg)
         ctx.set_scene_dict(sc)
+        ctx.kernel_ready(-1)  # the best tier asked for: PHASE_DEBUG=13=0 profiles the value kernel, 13=-1 the types kernel
         lib.sail_phase_read(buf, 1)
         ctx.render_schedule(inv, seeds, sc["eye"], B)
         ctx.sync()
