@@ -359,6 +359,97 @@ int sail_temporal_read(sail_ctx* ctx, int which, float* out);
 int sail_temporal_load_history(sail_ctx* ctx, const float* hist, const float* g, const double mvp_prev_rowmajor[16],
                                const float eye_prev[3]);
 
+/* ---- filtering the reprojected frame: temporal luminance moments and the a-trous passes over Out (no reference
+ * counterpart; the variance estimation of SVGF, Schied et al. 2017, between its temporal accumulation and its filter) ----
+ * Opt-in state of the temporal context: three more W x H float4 maps, Mhist (the committed moments of the previous view),
+ * MR (Mhist seen from the current view) and Mout (the moments of the current view). A texel is (mu1, mu2, mm, 0): the first
+ * and second moment of the luminance and the moments' own effective sample count. sail_temporal_moments(ctx, 1) allocates
+ * them zeroed, sail_temporal_moments(ctx, 0) and sail_destroy free them. A context that never switches them on allocates
+ * nothing and runs no extra pass: the calls above behave, bit for bit and pass for pass, as without this section; with
+ * tracking on their colour outputs are the same bits too. Every operation is an f32 IEEE operation in the order written,
+ * no contraction; min(a, b) = a < b ? a : b and max(a, b) = a > b ? a : b with the operands in the order written (so a
+ * NaN first operand gives the second); lum(c) = ((c.r + c.g) + c.b) / 3.
+ *
+ * With tracking on, sail_temporal_begin also commits Mhist <- Mout (a pointer swap, with the others) and, after the
+ * G-buffer pass, runs the moment reproject and copies Mout <- MR; sail_temporal_resolve also runs the moment resolve;
+ * sail_set_scene and sail_update_objects zero the three maps (tracking stays on); the calls that keep the temporal state
+ * keep them; sail_temporal_load_history zeroes Mhist.
+ *
+ * Moment reproject, pixel p of the current view: X, id, c_i, u, v, iu, fu, iv, fv, lim and the early-outs exactly as the
+ * colour reproject (the R[p] = 0 cases give MR[p] = 0):
+ *   taps b = 0, 1 (outer), a = 0, 1:  q, w as the colour reproject
+ *     counted only if q is inside the frame (else never loaded), w > 0, G_prev[q].w == (float)id, with e = X - G_prev[q].xyz:
+ *     (e.x*e.x + e.y*e.y) + e.z*e.z <= lim, Mhist[q].z > 0, Mhist[q].x and .y finite          (Hist is not read)
+ *     a1 += w * Mhist[q].x;  a2 += w * Mhist[q].y;  wsum += w;  m = min(m, Mhist[q].z)     (m starts at +inf)
+ *   MR[p] = wsum > 0 ? (a1 / wsum, a2 / wsum, m, 0) : 0
+ * Moment resolve, pointwise, n and c0 as sail_temporal_resolve:
+ *   l = lum(c0);  cur = n > 0 and c0.rgb all finite;  mh = MR.z;  hist = mh > 0
+ *   hist and cur:  ws = mh + n;  mu1 = ((mh * MR.x) + (n * l)) / ws;  mu2 = ((mh * MR.y) + (n * (l*l))) / ws;
+ *                  Mout = (mu1, mu2, min(ws, cap), 0)
+ *   hist only:     Mout = MR          cur only:  Mout = (l, l*l, min(n, cap), 0)          neither:  Mout = 0
+ *
+ * sail_temporal_filter: a variance from the moments, then sail_denoise's a-trous passes over Out. Inputs: Out (o, mo) and
+ * Mout of the current view, the AOVs N and X (SAIL_FLAG_AOV), and n of the shown accumulator (SUM: per pixel S.w; MIX: f32
+ * of the sample index):
+ *   c = Out.rgb;  nd = 2 * N.xyz - 1;  x = X.xyz                          (the guides exactly as sail_denoise)
+ *   nn = n > 0 ? n : 1
+ *   vt = (max(Mout.y - Mout.x * Mout.x, 0) * nn) / Mout.z                 -- temporal: variance of the mean
+ *   spatial, 7x7: dy = -3..3 (outer), dx = -3..3, q = p + (dx, dy) inside the frame (else never loaded);
+ *     sx0 = (sigma_x * 2) * (sigma_x * 2)
+ *     centre tap: w = 1
+ *     else: d = max((nd_p.x*nd_q.x + nd_p.y*nd_q.y) + nd_p.z*nd_q.z, 0); six times d = d*d
+ *           t = x_p - x_q;  dx2 = (t.x*t.x + t.y*t.y) + t.z*t.z;  wx = 1 / (1 + dx2 / sx0);  w = d * wx
+ *     the tap counts only if w > 0 and c_q.rgb are all finite:  lq = lum(c_q);  a1 += w*lq;  a2 += w*(lq*lq);  ws += w
+ *   vs = ws > 0 ? max(a2/ws - (a1/ws)*(a1/ws), 0) : 0
+ *   v0 = (Mout.z >= min_hist and vt is finite) ? vt : vs        -- counted in temporal_pixels / spatial_pixels
+ *   v = the 3x3 prefilter of v0, then (c, v), nd, x and every a-trous pass: exactly sail_denoise's text above
+ * `* nn` makes vt the variance of the mean when every frame of the history carried the same number of samples; with one
+ * sample per frame, the interactive case, it is the plain (mu2 - mu1*mu1) / mm. With unequal frame sizes it is only a
+ * steering estimate. nonfinite counts the pixels whose c is not finite: they stay as they are and feed nobody, as in
+ * sail_denoise. The outputs are sail_denoise's.
+ *
+ * State rules of sail_temporal_filter: SAIL_E_INVALID, before anything else, for iterations outside 1..6, a sigma that is
+ * not finite and > 0, a min_hist that is not finite or < 1 and a display outside kinds 0..2. Then queued samples are
+ * launched and the stream synchronised. SAIL_E_STATE: tracking off; no current view, or one not resolved since the
+ * accumulator last restarted (sail_reset, sail_load_accum, sail_set_accum_mode and sail_set_partition keep the maps, but
+ * Out and Mout then belong to the accumulator before: resolve again first); sample index 0 (the AOVs would belong to
+ * another view); no SAIL_FLAG_AOV; SAIL_ACCUM_COMPAT8; a half-loaded checkpoint. A
+ * multi-device context reduces first and works on device 0's maps. Nothing any other call can see changes: Out, Hist, the
+ * moment maps, accumulator, AOVs, mark, sample index and stats all stay; the unfiltered Out stays the history. */
+typedef struct sail_tfilter_params {
+  int iterations;   /* a-trous passes with step 1, 2, 4, ...: 1..6                          [4]   */
+  float sigma_l;    /* luminance edge stop, in standard deviations of the mean              [4.0] */
+  float sigma_x;    /* position edge stop per pixel of step                                 [0.2] */
+  float min_hist;   /* moments younger than this many samples use the spatial estimate: finite, >= 1  [4] */
+  int display;      /* SAIL_FILTER_COLOR | GAMMA | TONEMAPPING, for out_rgba8               [COLOR] */
+  float gamma_c;    /*                                                                      [2.2] */
+} sail_tfilter_params;
+typedef struct sail_tfilter_info {
+  uint64_t k;                 /* the context's sample index */
+  uint64_t temporal_pixels;   /* pixels whose v0 is vt */
+  uint64_t spatial_pixels;    /* pixels whose v0 is vs; the two add up to W * H */
+  uint64_t nonfinite;         /* pixels whose c is not finite */
+  int iterations;
+  double kernel_ms, pass_ms[8];    /* HIP events: total; [0] = prepare, [1..] = each a-trous pass */
+} sail_tfilter_info;
+enum sail_temporal_moment_map { SAIL_TEMPORAL_M_HIST = 0, SAIL_TEMPORAL_M_R = 1, SAIL_TEMPORAL_M_OUT = 2 };
+/* on = 1: allocate the three moment maps, zeroed (nothing happens if tracking is already on); on = 0: free them. Another
+ * value: SAIL_E_INVALID. A multi-device context keeps them on device 0, with the other temporal maps. */
+int sail_temporal_moments(sail_ctx* ctx, int on);
+/* install mom (W H 4 f32) as Mhist. Valid only when a history is committed and no view is current, i.e. right after
+ * sail_temporal_load_history; otherwise, and with tracking off, SAIL_E_STATE. */
+int sail_temporal_load_moments(sail_ctx* ctx, const float* mom);
+/* copy one of the three moment maps (sail_temporal_moment_map) into out (W H 4 f32). M_R and M_OUT need a current view,
+ * M_HIST a committed one, as sail_temporal_read: SAIL_E_STATE otherwise and with tracking off; SAIL_E_INVALID for another
+ * `which`. */
+int sail_temporal_read_moments(sail_ctx* ctx, int which, float* out);
+/* host only: the bracketed defaults */
+int sail_temporal_filter_defaults(sail_tfilter_params* p);
+/* p == NULL: the defaults. out_rgba (W H 4 f32: the filtered picture, w = 1, row 0 = bottom), out_var (W H f32: the filtered
+ * variance), out_rgba8 (W H 4 bytes) and info may each be NULL. */
+int sail_temporal_filter(sail_ctx* ctx, const sail_tfilter_params* p, float* out_rgba, float* out_var, uint8_t* out_rgba8,
+                         sail_tfilter_info* info);
+
 /* ---- checkpoint / resume of a progressive render (no reference counterpart: the reference restarts its
  * accumulation on every camera or object change, src/core/renderer.js:57-60, src/scene/scene.js:65-68) ----
  * A context's accumulation is `parts` raw accumulators (1 for sail_create, one per device for sail_create_multi),

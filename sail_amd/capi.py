@@ -54,6 +54,8 @@ EXPORTS = (
     "sail_denoise_defaults", "sail_denoise",
     "sail_temporal_defaults", "sail_gbuffer", "sail_temporal_begin", "sail_temporal_resolve", "sail_temporal_read",
     "sail_temporal_load_history",
+    "sail_temporal_moments", "sail_temporal_load_moments", "sail_temporal_read_moments",
+    "sail_temporal_filter_defaults", "sail_temporal_filter",
 )
 
 
@@ -114,6 +116,20 @@ class TemporalInfo(ctypes.Structure):
 
 # sail_temporal_read's maps
 TEMPORAL_G_CUR, TEMPORAL_G_PREV, TEMPORAL_HIST, TEMPORAL_R, TEMPORAL_OUT = 0, 1, 2, 3, 4
+# sail_temporal_read_moments' maps
+TEMPORAL_M_HIST, TEMPORAL_M_R, TEMPORAL_M_OUT = 0, 1, 2
+
+
+class TfilterParams(ctypes.Structure):
+    _fields_ = [("iterations", ctypes.c_int), ("sigma_l", ctypes.c_float), ("sigma_x", ctypes.c_float),
+                ("min_hist", ctypes.c_float), ("display", ctypes.c_int), ("gamma_c", ctypes.c_float)]
+
+
+class TfilterInfo(ctypes.Structure):
+    _fields_ = [("k", ctypes.c_uint64), ("temporal_pixels", ctypes.c_uint64), ("spatial_pixels", ctypes.c_uint64),
+                ("nonfinite", ctypes.c_uint64), ("iterations", ctypes.c_int), ("kernel_ms", ctypes.c_double),
+                ("pass_ms", ctypes.c_double * 8)]
+
 
 _SHAPES = {"cube": 1, "sphere": 2, "rectangle": 3, "cone": 4, "cylinder": 5, "disk": 6,
            "hyperboloid": 7, "paraboloid": 8, "cornellbox": 9}
@@ -222,6 +238,12 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
                                                  ctypes.POINTER(TemporalInfo)]),
         "sail_temporal_read": (ctypes.c_int, [vp, ctypes.c_int, f32p]),
         "sail_temporal_load_history": (ctypes.c_int, [vp, f32p, f32p, f64p, f32p]),
+        "sail_temporal_moments": (ctypes.c_int, [vp, ctypes.c_int]),
+        "sail_temporal_load_moments": (ctypes.c_int, [vp, f32p]),
+        "sail_temporal_read_moments": (ctypes.c_int, [vp, ctypes.c_int, f32p]),
+        "sail_temporal_filter_defaults": (ctypes.c_int, [ctypes.POINTER(TfilterParams)]),
+        "sail_temporal_filter": (ctypes.c_int, [vp, ctypes.POINTER(TfilterParams), f32p, f32p,
+                                                ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(TfilterInfo)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -370,6 +392,18 @@ def temporal_defaults() -> dict:
     if rc:
         raise SailError(f"sail_temporal_defaults: {rc}")
     return {"cap": p.cap, "pos_tol": p.pos_tol, "display": p.display, "gamma_c": p.gamma_c}
+
+
+def temporal_filter_defaults() -> dict:
+    """sail_temporal_filter's default parameters (sail_temporal_filter_defaults, host-only): iterations, sigma_l, sigma_x,
+    min_hist, display, gamma_c."""
+    lib = load()
+    p = TfilterParams()
+    rc = lib.sail_temporal_filter_defaults(ctypes.byref(p))
+    if rc:
+        raise SailError(f"sail_temporal_filter_defaults: {rc}")
+    return {"iterations": p.iterations, "sigma_l": p.sigma_l, "sigma_x": p.sigma_x, "min_hist": p.min_hist,
+            "display": p.display, "gamma_c": p.gamma_c}
 
 
 def _temporal_params(params: Optional[dict], who: str):
@@ -750,6 +784,57 @@ class Context:
         e = _f32(eye_prev)
         self._check(self.lib.sail_temporal_load_history(self.h, _ptr(h), _ptr(gg), _ptr(m, ctypes.c_double), _ptr(e)),
                     "sail_temporal_load_history")
+
+    def temporal_moments(self, on: bool = True):
+        """Switch the tracking of the luminance moments on (three more maps, zeroed) or off (freed)
+        (sail_temporal_moments)."""
+        self._check(self.lib.sail_temporal_moments(self.h, int(on)), "sail_temporal_moments")
+
+    def temporal_load_moments(self, mom):
+        """Install moments (H, W, 4: mu1, mu2, mm, 0) as those of the committed history, right after
+        temporal_load_history (sail_temporal_load_moments)."""
+        m = _f32(mom)
+        if m.shape != (self.H, self.W, 4):
+            raise SailError(f"temporal_load_moments: the map must have shape {(self.H, self.W, 4)}")
+        self._check(self.lib.sail_temporal_load_moments(self.h, _ptr(m)), "sail_temporal_load_moments")
+
+    def temporal_read_moments(self, which: int) -> np.ndarray:
+        """One of the three moment maps (TEMPORAL_M_HIST, TEMPORAL_M_R, TEMPORAL_M_OUT) as (H, W, 4) f32
+        (sail_temporal_read_moments)."""
+        out = np.zeros((self.H, self.W, 4), dtype=np.float32)
+        self._check(self.lib.sail_temporal_read_moments(self.h, int(which), _ptr(out)), "sail_temporal_read_moments")
+        return out
+
+    def temporal_filter(self, params: Optional[dict] = None, want_var: bool = False, want_u8: bool = False) -> dict:
+        """The a-trous passes over the resolved picture of the current view, steered by the variance of the tracked
+        moments (sail_temporal_filter). `params` overrides entries of temporal_filter_defaults(). Returns "rgba"
+        (H, W, 4) f32, with want_var "var" (H, W) f32, with want_u8 "u8" (H, W, 4) uint8 (the display transform), and k,
+        temporal_pixels, spatial_pixels, nonfinite, iterations, kernel_ms and pass_ms (prepare, then each a-trous pass)."""
+        p = None
+        if params is not None:
+            d = temporal_filter_defaults()
+            unknown = set(params) - set(d)
+            if unknown:
+                raise SailError(f"temporal_filter: unknown parameters {sorted(unknown)}")
+            d.update(params)
+            p = TfilterParams(int(d["iterations"]), float(d["sigma_l"]), float(d["sigma_x"]), float(d["min_hist"]),
+                              int(d["display"]), float(d["gamma_c"]))
+        info = TfilterInfo()
+        rgba = np.zeros((self.H, self.W, 4), dtype=np.float32)
+        var = np.zeros((self.H, self.W), dtype=np.float32) if want_var else None
+        u8 = np.zeros((self.H, self.W, 4), dtype=np.uint8) if want_u8 else None
+        self._check(self.lib.sail_temporal_filter(self.h, ctypes.byref(p) if p is not None else None, _ptr(rgba),
+                                                  _ptr(var), _ptr(u8, ctypes.c_uint8), ctypes.byref(info)),
+                    "sail_temporal_filter")
+        out = {"rgba": rgba, "k": int(info.k), "temporal_pixels": int(info.temporal_pixels),
+               "spatial_pixels": int(info.spatial_pixels), "nonfinite": int(info.nonfinite),
+               "iterations": info.iterations, "kernel_ms": info.kernel_ms,
+               "pass_ms": [info.pass_ms[i] for i in range(info.iterations + 1)]}
+        if want_var:
+            out["var"] = var
+        if want_u8:
+            out["u8"] = u8
+        return out
 
     def filter_ms(self) -> float:
         v = ctypes.c_double()

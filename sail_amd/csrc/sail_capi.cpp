@@ -38,6 +38,11 @@ hipError_t sail_launch_denoise_atrous(const SailDenoiseAtrousArgs& A, hipStream_
 hipError_t sail_launch_gbuffer(const SailGbufferArgs& A, hipStream_t s);
 hipError_t sail_launch_reproject(const SailReprojectArgs& A, hipStream_t s);
 hipError_t sail_launch_temporal_resolve(const SailResolveArgs& A, hipStream_t s);
+// sail_tfilter.hip: the moment reproject and resolve passes and the temporal filter's prepare pass
+#include "sail_tfilter.h"
+hipError_t sail_launch_moment_reproject(const SailMomentReprojectArgs& A, hipStream_t s);
+hipError_t sail_launch_moment_resolve(const SailMomentResolveArgs& A, hipStream_t s);
+hipError_t sail_launch_tfilter_prepare(const SailTfilterPrepareArgs& A, hipStream_t s);
 
 namespace {
 
@@ -228,6 +233,12 @@ struct sail_ctx {
   bool tpHaveCur = false, tpHavePrev = false;
   struct TpView { float m[16]; float eye[3]; } tpCur{}, tpPrev{};
   uint64_t tpHitPixels = 0;
+  // Moment tracking (sail_temporal_moments): one block of three float4 maps (mu1, mu2, mm, 0) and a count per tile,
+  // allocated when tracking is switched on and freed when it is switched off; the pointers are swapped with the colour
+  // maps'. tpResolved: the current view has been resolved (sail_temporal_filter needs its Out and Mout).
+  void* tpMom = nullptr;
+  float4 *tpMhist = nullptr, *tpMR = nullptr, *tpMout = nullptr;
+  bool tpResolved = false;
   nccl_comm_t comm = nullptr;
   int commRanks = 0, commRank = 0;
   // Reduced frame (root of sail_reduce / device 0 of a multi-device context): the sum of every rank's
@@ -552,6 +563,7 @@ int resetAccum(sail_ctx* c) {
   c->reduced = false;
   c->queued.clear();  // queued one-sample frames belong to the accumulation being discarded
   c->noiseHave = false;  // so does the noise estimate's mark (sail_load_accum puts it back: it continues a render)
+  c->tpResolved = false;  // Out no longer belongs to this accumulator: sail_temporal_filter wants a resolve of the new one
   const size_t bytes = (size_t)c->W * c->H * sizeof(float4);
   HIPCHK(c, hipMemsetAsync(c->accum, 0, bytes, c->stream));
   if (c->aovN) HIPCHK(c, hipMemsetAsync(c->aovN, 0, bytes, c->stream));
@@ -1092,6 +1104,89 @@ const float4* shownAccum(const sail_ctx* c) { return c->reduced ? c->frame : c->
 const float4* shownAovN(const sail_ctx* c) { return c->reduced && c->frameN ? c->frameN : c->aovN; }
 const float4* shownAovP(const sail_ctx* c) { return c->reduced && c->frameP ? c->frameP : c->aovP; }
 
+// the a-trous passes' work buffers (sail_denoise and sail_temporal_filter share them), allocated on first use:
+// cvA | cvB | g0 (16 B each) | g1 (8 B) | var (4 B) | rgba8 (4 B) per pixel, then a count per 16x16 tile
+int ensureDenoiseWork(sail_ctx* c) {
+  if (c->denoiseWork) return SAIL_OK;
+  const size_t nt = (size_t)((c->W + 15) / 16) * (size_t)((c->H + 15) / 16), np = (size_t)c->W * c->H;
+  if (hipMalloc(&c->denoiseWork, np * 64 + nt * 4) != hipSuccess) {
+    c->denoiseWork = nullptr;
+    return fail(c, SAIL_E_OOM, "denoise work buffers");
+  }
+  return SAIL_OK;
+}
+
+struct DenoiseWork {
+  float4* cv[2];
+  float4* g0;
+  float2* g1;
+  float* var;
+  uint32_t* u8;
+  uint32_t* bad;
+};
+DenoiseWork denoiseWork(const sail_ctx* c) {
+  const size_t np = (size_t)c->W * c->H;
+  char* base = (char*)c->denoiseWork;
+  return {{(float4*)base, (float4*)(base + np * 16)}, (float4*)(base + np * 32), (float2*)(base + np * 48),
+          (float*)(base + np * 56), (uint32_t*)(base + np * 60), (uint32_t*)(base + np * 64)};
+}
+
+// What sail_denoise and sail_temporal_filter share: `prepare` launches the pass that fills (cv[0], g0, g1) and the
+// per-tile counts, then the a-trous passes run with steps 1, 2, 4, ..., an event round every pass (ms[0] = prepare,
+// ms[1..] = the passes); the stream is synchronised and the outputs that are asked for are copied back.
+template <class Prepare>
+hipError_t runAtrous(sail_ctx* c, const DenoiseWork& w, Prepare prepare, int iterations, float sigma_l, float sigma_x,
+                     int display, float gamma_c, float* out_rgba, float* out_var, uint8_t* out_rgba8, float ms[8],
+                     float* total, int* rc) {
+  const size_t np = (size_t)c->W * c->H;
+  const int nev = iterations + 2;  // before the prepare pass, then after every pass
+  hipEvent_t ev[8] = {};
+  *rc = SAIL_OK;
+  for (int i = 0; i < nev; i++)
+    if ((*rc = getEvent(c, &ev[i]))) {
+      for (int j = 0; j < i; j++) c->evPool.push_back(ev[j]);
+      return hipSuccess;
+    }
+  hipError_t e = hipEventRecord(ev[0], c->stream);
+  if (e == hipSuccess) e = prepare();
+  if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
+  int cur = 0;
+  for (int it = 0; it < iterations && e == hipSuccess; it++) {
+    const bool last = it == iterations - 1;
+    SailDenoiseAtrousArgs B;
+    memset(&B, 0, sizeof B);
+    B.src = w.cv[cur];
+    B.dst = (last && !out_rgba) ? nullptr : w.cv[cur ^ 1];
+    B.g0 = w.g0; B.g1 = w.g1;
+    B.outVar = (last && out_var) ? w.var : nullptr;
+    B.out8 = (last && out_rgba8) ? w.u8 : nullptr;
+    B.W = c->W; B.H = c->H;
+    B.step = 1 << it;
+    B.last = last;
+    B.sl2 = sigma_l * sigma_l;
+    const float sx = sigma_x * (float)B.step;
+    B.sxs = sx * sx;
+    B.display = display; B.gammaC = gamma_c;
+    e = sail_launch_denoise_atrous(B, c->stream);
+    if (e == hipSuccess) e = hipEventRecord(ev[it + 2], c->stream);
+    cur ^= 1;
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  for (int i = 0; i + 1 < nev && e == hipSuccess; i++) e = hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]);
+  if (e == hipSuccess) e = hipEventElapsedTime(total, ev[0], ev[nev - 1]);
+  for (int i = 0; i < nev; i++) c->evPool.push_back(ev[i]);
+  if (e == hipSuccess && out_rgba) e = hipMemcpy(out_rgba, w.cv[cur], np * 16, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && out_var) e = hipMemcpy(out_var, w.var, np * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && out_rgba8) e = hipMemcpy(out_rgba8, w.u8, np * 4, hipMemcpyDeviceToHost);
+  return e;
+}
+
+// the three moment maps of a context that tracks them (sail_temporal_moments), zeroed on its stream
+hipError_t zeroMoments(sail_ctx* c) {
+  if (!c->tpMom) return hipSuccess;
+  return hipMemsetAsync(c->tpMom, 0, (size_t)c->W * c->H * 48, c->stream);
+}
+
 // asynchronous RCCL errors (ncclCommGetAsyncError): a failed collective surfaces here, not at enqueue time
 int commCheck(sail_ctx* c, nccl_comm_t comm) {
   if (!comm || !g_rccl.commGetAsyncError) return SAIL_OK;
@@ -1382,7 +1477,7 @@ void sail_destroy(sail_ctx* c) {
   for (auto& pr : c->pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
   for (auto e : c->evPool) (void)hipEventDestroy(e);
   void* bufs[] = {c->accum, c->frame, c->frameN, c->frameP, c->aovN, c->aovP, c->filterOut, c->filterOut8, c->stage, c->segCounter, c->prims, c->tp, c->lt, c->lightObjRow, c->samples, c->wf,
-                  c->noiseMark, c->noiseOut, c->noisePix, c->denoiseWork, c->tpWork};
+                  c->noiseMark, c->noiseOut, c->noisePix, c->denoiseWork, c->tpWork, c->tpMom};
   for (void* b : bufs) if (b) (void)hipFree(b);
   if (c->samplesPinned) (void)hipHostFree(c->samplesPinned);
   if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1576,7 +1671,8 @@ int sail_set_scene(sail_ctx* c, const float* objects, int n, const float* texpar
   c->tpRows.assign(texparams, texparams + (size_t)tn * 16);
   c->n = n; c->tn = tn; c->ln = ln;
   c->haveScene = true;
-  c->tpHaveCur = c->tpHavePrev = false;  // the temporal maps' ids and positions are stale
+  c->tpHaveCur = c->tpHavePrev = c->tpResolved = false;  // the temporal maps' ids and positions are stale
+  HIPCHK(c, zeroMoments(c));
   // Tracer.update links the scene's program (tracer.js:42-90): the plugin set's kernel starts building now, in the
   // background; the precompiled kernel of the set serves until it is loaded
   dropValues(c);
@@ -1608,7 +1704,8 @@ int sail_update_objects(sail_ctx* c, const float* objects, int n) {
   if (int rc = uploadPrims(c, prims)) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->objectsRows.assign(objects, objects + (size_t)n * 18);
-  c->tpHaveCur = c->tpHavePrev = false;  // the temporal maps' ids and positions are stale
+  c->tpHaveCur = c->tpHavePrev = c->tpResolved = false;  // the temporal maps' ids and positions are stale
+  HIPCHK(c, zeroMoments(c));
   dropValues(c);  // the rows' values moved: the value kernel goes, the settle count restarts
   refreshJit(c);  // a drag keeps the types kernel; a changed shape type starts the new rows' kernel building
   refreshValues(c);
@@ -2126,68 +2223,23 @@ int sail_denoise(sail_ctx* c, const sail_denoise_params* params, float* out_rgba
   if (c->k <= c->noiseK)
     return fail(c, SAIL_E_STATE, "sail_denoise: no sample since the mark (k = %llu, marked at %llu)",
                 (unsigned long long)c->k, (unsigned long long)c->noiseK);
-  const int tx = (c->W + 15) / 16, ty = (c->H + 15) / 16;
-  const size_t nt = (size_t)tx * ty, np = (size_t)c->W * c->H;
-  // cvA | cvB | g0 (16 B each) | g1 (8 B) | var (4 B) | rgba8 (4 B) per pixel, then a count per tile
-  if (!c->denoiseWork && hipMalloc(&c->denoiseWork, np * 64 + nt * 4) != hipSuccess) {
-    c->denoiseWork = nullptr;
-    return fail(c, SAIL_E_OOM, "denoise work buffers");
-  }
-  char* base = (char*)c->denoiseWork;
-  float4* cv[2] = {(float4*)base, (float4*)(base + np * 16)};
-  float4* g0 = (float4*)(base + np * 32);
-  float2* g1 = (float2*)(base + np * 48);
-  float* dVar = (float*)(base + np * 56);
-  uint32_t* d8 = (uint32_t*)(base + np * 60);
-  uint32_t* dBad = (uint32_t*)(base + np * 64);
+  const size_t nt = (size_t)((c->W + 15) / 16) * (size_t)((c->H + 15) / 16);
+  if (int rc = ensureDenoiseWork(c)) return rc;
+  const DenoiseWork w = denoiseWork(c);
   SailDenoisePrepareArgs A;
   memset(&A, 0, sizeof A);
   A.S = shownAccum(c); A.P = c->noiseMark; A.N = shownAovN(c); A.X = shownAovP(c);
-  A.cv = cv[0]; A.g0 = g0; A.g1 = g1; A.tileBad = dBad;
+  A.cv = w.cv[0]; A.g0 = w.g0; A.g1 = w.g1; A.tileBad = w.bad;
   A.W = c->W; A.H = c->H;
   A.mix = c->accumMode == SAIL_ACCUM_MIX;
   A.kf = (float)c->k; A.hf = (float)c->noiseK;
-  const int nev = p.iterations + 2;  // before the prepare pass, then after every pass
-  hipEvent_t ev[8] = {};
-  for (int i = 0; i < nev; i++)
-    if (int rc = getEvent(c, &ev[i])) {
-      for (int j = 0; j < i; j++) c->evPool.push_back(ev[j]);
-      return rc;
-    }
-  hipError_t e = hipEventRecord(ev[0], c->stream);
-  if (e == hipSuccess) e = sail_launch_denoise_prepare(A, c->stream);
-  if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
-  int cur = 0;
-  for (int it = 0; it < p.iterations && e == hipSuccess; it++) {
-    const bool last = it == p.iterations - 1;
-    SailDenoiseAtrousArgs B;
-    memset(&B, 0, sizeof B);
-    B.src = cv[cur];
-    B.dst = (last && !out_rgba) ? nullptr : cv[cur ^ 1];
-    B.g0 = g0; B.g1 = g1;
-    B.outVar = (last && out_var) ? dVar : nullptr;
-    B.out8 = (last && out_rgba8) ? d8 : nullptr;
-    B.W = c->W; B.H = c->H;
-    B.step = 1 << it;
-    B.last = last;
-    B.sl2 = p.sigma_l * p.sigma_l;
-    const float sx = p.sigma_x * (float)B.step;
-    B.sxs = sx * sx;
-    B.display = p.display; B.gammaC = p.gamma_c;
-    e = sail_launch_denoise_atrous(B, c->stream);
-    if (e == hipSuccess) e = hipEventRecord(ev[it + 2], c->stream);
-    cur ^= 1;
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   float ms[8] = {}, total = 0.0f;
-  for (int i = 0; i + 1 < nev && e == hipSuccess; i++) e = hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]);
-  if (e == hipSuccess) e = hipEventElapsedTime(&total, ev[0], ev[nev - 1]);
-  for (int i = 0; i < nev; i++) c->evPool.push_back(ev[i]);
+  int rc = SAIL_OK;
+  hipError_t e = runAtrous(c, w, [&] { return sail_launch_denoise_prepare(A, c->stream); }, p.iterations, p.sigma_l,
+                           p.sigma_x, p.display, p.gamma_c, out_rgba, out_var, out_rgba8, ms, &total, &rc);
+  if (rc) return rc;
   std::vector<uint32_t> bad(nt);
-  if (e == hipSuccess) e = hipMemcpy(bad.data(), dBad, nt * 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && out_rgba) e = hipMemcpy(out_rgba, cv[cur], np * 16, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && out_var) e = hipMemcpy(out_var, dVar, np * 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && out_rgba8) e = hipMemcpy(out_rgba8, d8, np * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(bad.data(), w.bad, nt * 4, hipMemcpyDeviceToHost);
   if (e != hipSuccess) return fail(c, SAIL_E_HIP, "sail_denoise: %s", hipGetErrorString(e));
   if (info) {
     memset(info, 0, sizeof *info);
@@ -2196,7 +2248,7 @@ int sail_denoise(sail_ctx* c, const sail_denoise_params* params, float* out_rgba
     for (uint32_t b : bad) info->nonfinite += b;
     info->iterations = p.iterations;
     info->kernel_ms = total;
-    for (int i = 0; i + 1 < nev; i++) info->pass_ms[i] = ms[i];
+    for (int i = 0; i <= p.iterations; i++) info->pass_ms[i] = ms[i];
   }
   return SAIL_OK;
 }
@@ -2323,6 +2375,7 @@ int sail_temporal_begin(sail_ctx* c, const double mvp[16], const float eye[3], c
   if (c->tpHaveCur) {  // commit the view that was current
     std::swap(c->tpHist, c->tpOut);
     std::swap(c->tpGprev, c->tpGcur);
+    if (c->tpMom) std::swap(c->tpMhist, c->tpMout);
     c->tpPrev = c->tpCur;
     c->tpHavePrev = true;
     c->tpHaveCur = false;
@@ -2339,8 +2392,17 @@ int sail_temporal_begin(sail_ctx* c, const double mvp[16], const float eye[3], c
   B.tol2 = p.pos_tol * p.pos_tol;
   B.W = c->W; B.H = c->H;
   B.haveHist = c->tpHavePrev;
-  hipEvent_t ev[3] = {};
-  for (int i = 0; i < 3; i++)
+  c->tpResolved = false;
+  // moment tracking: the same gather over Mhist, timed with the reproject pass
+  const int nev = c->tpMom ? 4 : 3;
+  SailMomentReprojectArgs M;
+  memset(&M, 0, sizeof M);
+  M.Gcur = c->tpGcur; M.Gprev = c->tpGprev; M.Mhist = c->tpMhist; M.MR = c->tpMR;
+  memcpy(M.Mp, B.Mp, sizeof M.Mp);
+  memcpy(M.eyePrev, B.eyePrev, sizeof M.eyePrev);
+  M.tol2 = B.tol2; M.W = c->W; M.H = c->H; M.haveHist = B.haveHist;
+  hipEvent_t ev[4] = {};
+  for (int i = 0; i < nev; i++)
     if (int rc = getEvent(c, &ev[i])) {
       for (int j = 0; j < i; j++) c->evPool.push_back(ev[j]);
       return rc;
@@ -2350,11 +2412,17 @@ int sail_temporal_begin(sail_ctx* c, const double mvp[16], const float eye[3], c
   if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
   if (e == hipSuccess) e = sail_launch_reproject(B, c->stream);
   if (e == hipSuccess) e = hipEventRecord(ev[2], c->stream);
+  if (c->tpMom) {
+    if (e == hipSuccess) e = sail_launch_moment_reproject(M, c->stream);
+    if (e == hipSuccess) e = hipEventRecord(ev[3], c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->tpMout, c->tpMR, np * 16, hipMemcpyDeviceToDevice, c->stream);
+  }
   if (e == hipSuccess) e = hipMemcpyAsync(c->tpOut, c->tpR, np * 16, hipMemcpyDeviceToDevice, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  float ms[2] = {};
-  for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]);
-  for (int i = 0; i < 3; i++) c->evPool.push_back(ev[i]);
+  float ms[3] = {};
+  for (int i = 0; i + 1 < nev && e == hipSuccess; i++) e = hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]);
+  for (int i = 0; i < nev; i++) c->evPool.push_back(ev[i]);
+  ms[1] += ms[2];  // the moment reproject, when it ran
   std::vector<uint32_t> host(nt * 2);
   if (e == hipSuccess) e = hipMemcpy(host.data(), cnt, nt * 8, hipMemcpyDeviceToHost);
   if (e != hipSuccess) return fail(c, SAIL_E_HIP, "sail_temporal_begin: %s", hipGetErrorString(e));
@@ -2405,6 +2473,13 @@ int sail_temporal_resolve(sail_ctx* c, const sail_temporal_params* params, float
   float ms = 0.0f;
   hipError_t e = hipEventRecord(e0, c->stream);
   if (e == hipSuccess) e = sail_launch_temporal_resolve(A, c->stream);
+  if (c->tpMom && e == hipSuccess) {  // moment tracking: blended like the colour, timed with it
+    SailMomentResolveArgs M;
+    memset(&M, 0, sizeof M);
+    M.S = A.S; M.MR = c->tpMR; M.Mout = c->tpMout;
+    M.W = c->W; M.H = c->H; M.mix = A.mix; M.kf = A.kf; M.cap = A.cap;
+    e = sail_launch_moment_resolve(M, c->stream);
+  }
   if (e == hipSuccess) e = hipEventRecord(e1, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
@@ -2415,6 +2490,7 @@ int sail_temporal_resolve(sail_ctx* c, const sail_temporal_params* params, float
   if (e == hipSuccess && out_rgba) e = hipMemcpy(out_rgba, c->tpOut, np * 16, hipMemcpyDeviceToHost);
   if (e == hipSuccess && out_rgba8) e = hipMemcpy(out_rgba8, A.out8, np * 4, hipMemcpyDeviceToHost);
   if (e != hipSuccess) return fail(c, SAIL_E_HIP, "sail_temporal_resolve: %s", hipGetErrorString(e));
+  c->tpResolved = true;
   if (info) {
     memset(info, 0, sizeof *info);
     info->k = c->k;
@@ -2459,6 +2535,149 @@ int sail_temporal_load_history(sail_ctx* c, const float* hist, const float* g, c
   memcpy(c->tpPrev.eye, eye_prev, sizeof c->tpPrev.eye);
   c->tpHavePrev = true;
   c->tpHaveCur = false;
+  c->tpResolved = false;
+  if (c->tpMom) {  // the loaded history carries no moments
+    HIPCHK(c, hipMemsetAsync(c->tpMhist, 0, bytes, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return SAIL_OK;
+}
+
+// ---- moment tracking and the temporal filter (include/sail_hip.h; the kernels are sail_tfilter.hip) ---------------------------
+int sail_temporal_moments(sail_ctx* c, int on) {
+  // the arguments first, so that they can be checked without a device (a NULL context's message: sail_last_error(NULL))
+  if (on != 0 && on != 1) return fail(c, SAIL_E_INVALID, "sail_temporal_moments: on must be 0 or 1, not %d", on);
+  if (!c) return fail(c, SAIL_E_INVALID, "sail_temporal_moments: a context is required");
+  if (!c->subs.empty()) return relay(c, sail_temporal_moments(c->subs[0], on), c->subs[0]);
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (!on) {
+    if (c->tpMom) HIPCHK(c, hipFree(c->tpMom));
+    c->tpMom = nullptr;
+    c->tpMhist = c->tpMR = c->tpMout = nullptr;
+    return SAIL_OK;
+  }
+  if (c->tpMom) return SAIL_OK;
+  const size_t np = (size_t)c->W * c->H;
+  // three float4 maps (16 B each) per pixel, then the filter's count of temporal pixels per tile
+  if (hipMalloc(&c->tpMom, np * 48 + temporalTiles(c) * 4) != hipSuccess) {
+    c->tpMom = nullptr;
+    return fail(c, SAIL_E_OOM, "moment maps");
+  }
+  float4* base = (float4*)c->tpMom;
+  c->tpMhist = base; c->tpMR = base + np; c->tpMout = base + 2 * np;
+  HIPCHK(c, zeroMoments(c));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SAIL_OK;
+}
+
+int sail_temporal_load_moments(sail_ctx* c, const float* mom) {
+  if (!c) return SAIL_E_INVALID;
+  if (!mom) return fail(c, SAIL_E_INVALID, "sail_temporal_load_moments: mom is required");
+  if (!c->subs.empty()) return relay(c, sail_temporal_load_moments(c->subs[0], mom), c->subs[0]);
+  if (!c->tpMom)
+    return fail(c, SAIL_E_STATE, "sail_temporal_load_moments: moment tracking is off (sail_temporal_moments first)");
+  if (!c->tpHavePrev || c->tpHaveCur)
+    return fail(c, SAIL_E_STATE, "sail_temporal_load_moments: needs a committed history and no current view (right after sail_temporal_load_history)");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(c->tpMhist, mom, (size_t)c->W * c->H * 16, hipMemcpyHostToDevice));
+  return SAIL_OK;
+}
+
+int sail_temporal_read_moments(sail_ctx* c, int which, float* out) {
+  if (!out || which < SAIL_TEMPORAL_M_HIST || which > SAIL_TEMPORAL_M_OUT)
+    return fail(c, SAIL_E_INVALID, "sail_temporal_read_moments: map %d of 0..2 and an output are required", which);
+  if (!c) return fail(c, SAIL_E_INVALID, "sail_temporal_read_moments: a context is required");
+  if (!c->subs.empty()) return relay(c, sail_temporal_read_moments(c->subs[0], which, out), c->subs[0]);
+  if (!c->tpMom)
+    return fail(c, SAIL_E_STATE, "sail_temporal_read_moments: moment tracking is off (sail_temporal_moments first)");
+  const bool prev = which == SAIL_TEMPORAL_M_HIST;
+  if (!c->tpWork || !(prev ? c->tpHavePrev : c->tpHaveCur))
+    return fail(c, SAIL_E_STATE, "sail_temporal_read_moments: map %d needs a %s view (a new scene drops both)", which,
+                prev ? "committed" : "current");
+  const float4* maps[3] = {c->tpMhist, c->tpMR, c->tpMout};
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(out, maps[which], (size_t)c->W * c->H * 16, hipMemcpyDeviceToHost));
+  return SAIL_OK;
+}
+
+int sail_temporal_filter_defaults(sail_tfilter_params* p) {
+  if (!p) return SAIL_E_INVALID;
+  p->iterations = 4;
+  p->sigma_l = 4.0f;
+  p->sigma_x = 0.2f;
+  p->min_hist = 4.0f;
+  p->display = SAIL_FILTER_COLOR;
+  p->gamma_c = 2.2f;
+  return SAIL_OK;
+}
+
+int sail_temporal_filter(sail_ctx* c, const sail_tfilter_params* params, float* out_rgba, float* out_var,
+                         uint8_t* out_rgba8, sail_tfilter_info* info) {
+  // the parameters first, so that they can be checked without a device (a NULL context's message: sail_last_error(NULL))
+  sail_tfilter_params p;
+  sail_temporal_filter_defaults(&p);
+  if (params) p = *params;
+  if (p.iterations < 1 || p.iterations > 6 || !(p.sigma_l > 0.0f) || !std::isfinite(p.sigma_l) || !(p.sigma_x > 0.0f) ||
+      !std::isfinite(p.sigma_x) || !std::isfinite(p.min_hist) || p.min_hist < 1.0f || p.display < SAIL_FILTER_COLOR ||
+      p.display > SAIL_FILTER_TONEMAPPING)
+    return fail(c, SAIL_E_INVALID, "sail_temporal_filter: bad parameters (iterations %d of 1..6, sigma_l %g and sigma_x %g finite and > 0, min_hist %g finite and >= 1, display %d of 0..2)",
+                p.iterations, (double)p.sigma_l, (double)p.sigma_x, (double)p.min_hist, p.display);
+  if (!c) return fail(c, SAIL_E_INVALID, "sail_temporal_filter: a context is required");
+  if (!c->subs.empty()) {  // device 0's reduced frame, AOV and temporal maps, like sail_denoise
+    if (int rc = loadIncomplete(c, "sail_temporal_filter")) return rc;
+    if (int rc = groupReduce(c)) return rc;
+    return relay(c, sail_temporal_filter(c->subs[0], &p, out_rgba, out_var, out_rgba8, info), c->subs[0]);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = sail_sync(c)) return rc;
+  if (!c->tpMom)
+    return fail(c, SAIL_E_STATE, "sail_temporal_filter: moment tracking is off (sail_temporal_moments first)");
+  if (!c->aovN || !c->aovP)
+    return fail(c, SAIL_E_STATE, "sail_temporal_filter: reads the normal and position AOVs (create with SAIL_FLAG_AOV)");
+  if (c->accumMode == SAIL_ACCUM_COMPAT8)
+    return fail(c, SAIL_E_STATE, "sail_temporal_filter: SAIL_ACCUM_COMPAT8 stores 8-bit frames, which carry no sample count to blend with");
+  if (!c->tpHaveCur || !c->tpWork)
+    return fail(c, SAIL_E_STATE, "sail_temporal_filter: no current view (sail_temporal_begin first; a new scene drops it)");
+  if (!c->tpResolved)
+    return fail(c, SAIL_E_STATE, "sail_temporal_filter: the current view is not resolved (sail_temporal_resolve first)");
+  if (c->k == 0)
+    return fail(c, SAIL_E_STATE, "sail_temporal_filter: no sample of the current view (k = 0: the AOVs belong to another view)");
+  const size_t nt = temporalTiles(c), np = (size_t)c->W * c->H;
+  if (int rc = ensureDenoiseWork(c)) return rc;
+  const DenoiseWork w = denoiseWork(c);  // sail_denoise's work buffers; the count of temporal pixels sits behind the moments
+  uint32_t* dTmp = (uint32_t*)((char*)c->tpMom + np * 48);
+  SailTfilterPrepareArgs A;
+  memset(&A, 0, sizeof A);
+  A.Out = c->tpOut; A.Mout = c->tpMout; A.S = shownAccum(c); A.N = shownAovN(c); A.X = shownAovP(c);
+  A.cv = w.cv[0]; A.g0 = w.g0; A.g1 = w.g1; A.tileBad = w.bad; A.tileTemporal = dTmp;
+  A.W = c->W; A.H = c->H;
+  A.mix = c->accumMode == SAIL_ACCUM_MIX;
+  A.kf = (float)c->k;
+  A.minHist = p.min_hist;
+  const float sx2 = p.sigma_x * 2.0f;
+  A.sx0 = sx2 * sx2;
+  float ms[8] = {}, total = 0.0f;
+  int rc = SAIL_OK;
+  hipError_t e = runAtrous(c, w, [&] { return sail_launch_tfilter_prepare(A, c->stream); }, p.iterations, p.sigma_l,
+                           p.sigma_x, p.display, p.gamma_c, out_rgba, out_var, out_rgba8, ms, &total, &rc);
+  if (rc) return rc;
+  std::vector<uint32_t> bad(nt), tmp(nt);
+  if (e == hipSuccess) e = hipMemcpy(bad.data(), w.bad, nt * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(tmp.data(), dTmp, nt * 4, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(c, SAIL_E_HIP, "sail_temporal_filter: %s", hipGetErrorString(e));
+  if (info) {
+    memset(info, 0, sizeof *info);
+    info->k = c->k;
+    info->temporal_pixels = sumTiles(tmp, 0, nt);
+    info->spatial_pixels = (uint64_t)np - info->temporal_pixels;
+    info->nonfinite = sumTiles(bad, 0, nt);
+    info->iterations = p.iterations;
+    info->kernel_ms = total;
+    for (int i = 0; i <= p.iterations; i++) info->pass_ms[i] = ms[i];
+  }
   return SAIL_OK;
 }
 

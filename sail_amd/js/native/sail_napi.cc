@@ -635,6 +635,113 @@ napi_value TemporalLoadHistory(napi_env env, napi_callback_info info) {
   if (rc) return throwSail(env, "sail_temporal_load_history", rc, h->ctx);
   return undef(env);
 }
+// ---- moment tracking and the temporal filter (sail_temporal_moments, sail_temporal_filter) ----
+// (ctx, on)
+napi_value TemporalMoments(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  if (!args(env, info, 2, a)) return nullptr;
+  Handle* h;
+  bool on = false;
+  if (!getHandle(env, a[0], &h)) return nullptr;
+  if (napi_get_value_bool(env, a[1], &on) != napi_ok) {  // anything but a boolean must not silently mean "off"
+    napi_throw_type_error(env, nullptr, "temporalMoments: on must be a boolean");
+    return nullptr;
+  }
+  const int rc = sail_temporal_moments(h->ctx, on ? 1 : 0);
+  if (rc) return throwSail(env, "sail_temporal_moments", rc, h->ctx);
+  return undef(env);
+}
+// (ctx, mom f32[W H 4])
+napi_value TemporalLoadMoments(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  if (!args(env, info, 2, a)) return nullptr;
+  Handle* h;
+  float* mom;
+  size_t nm;
+  if (!getHandle(env, a[0], &h) || !getArray(env, a[1], napi_float32_array, &mom, &nm)) return nullptr;
+  if (nm < (size_t)h->W * h->H * 4) { napi_throw_range_error(env, nullptr, "mom needs width * height * 4 floats"); return nullptr; }
+  const int rc = sail_temporal_load_moments(h->ctx, mom);
+  if (rc) return throwSail(env, "sail_temporal_load_moments", rc, h->ctx);
+  return undef(env);
+}
+// (ctx, which 0..2) -> Float32Array (4 per pixel): Mhist, MR or Mout
+napi_value TemporalReadMoments(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  if (!args(env, info, 2, a)) return nullptr;
+  Handle* h;
+  int which = 0;
+  if (!getHandle(env, a[0], &h) || !getInt(env, a[1], &which)) return nullptr;
+  void* pf = nullptr;
+  napi_value f = makeTyped(env, napi_float32_array, (size_t)h->W * h->H * 4, 4, &pf);
+  const int rc = sail_temporal_read_moments(h->ctx, which, (float*)pf);
+  if (rc) return throwSail(env, "sail_temporal_read_moments", rc, h->ctx);
+  return f;
+}
+// () -> {iterations, sigmaL, sigmaX, minHist, display, gamma}: sail_temporal_filter_defaults (host only)
+napi_value TemporalFilterDefaults(napi_env env, napi_callback_info info) {
+  (void)info;
+  sail_tfilter_params p;
+  sail_temporal_filter_defaults(&p);
+  napi_value out;
+  NAPI_OK(napi_create_object(env, &out));
+  napi_set_named_property(env, out, "iterations", num(env, p.iterations));
+  napi_set_named_property(env, out, "sigmaL", num(env, p.sigma_l));
+  napi_set_named_property(env, out, "sigmaX", num(env, p.sigma_x));
+  napi_set_named_property(env, out, "minHist", num(env, p.min_hist));
+  napi_set_named_property(env, out, "display", num(env, p.display));
+  napi_set_named_property(env, out, "gamma", num(env, p.gamma_c));
+  return out;
+}
+// (ctx, iterations, sigmaL, sigmaX, minHist, display, gamma, wantU8) -> {rgba, rgba8?, info}; a parameter that is
+// undefined or null keeps sail_temporal_filter_defaults' value
+napi_value TemporalFilter(napi_env env, napi_callback_info info) {
+  napi_value a[8];
+  if (!args(env, info, 8, a)) return nullptr;
+  Handle* h;
+  if (!getHandle(env, a[0], &h)) return nullptr;
+  sail_tfilter_params p;
+  sail_temporal_filter_defaults(&p);
+  double v[6] = {(double)p.iterations, p.sigma_l, p.sigma_x, p.min_hist, (double)p.display, p.gamma_c};
+  for (int i = 0; i < 6; i++) {
+    napi_valuetype vt;
+    napi_typeof(env, a[1 + i], &vt);
+    if (vt == napi_undefined || vt == napi_null) continue;
+    if (!getDouble(env, a[1 + i], &v[i])) return nullptr;
+  }
+  // the range first: converting a double outside int's range is undefined
+  const auto small = [](double x) { return x >= -1e6 && x <= 1e6 && x == (double)(int)x; };
+  if (!small(v[0]) || !small(v[4])) {
+    napi_throw_range_error(env, nullptr, "iterations and display must be integers");
+    return nullptr;
+  }
+  p.iterations = (int)v[0]; p.sigma_l = (float)v[1]; p.sigma_x = (float)v[2]; p.min_hist = (float)v[3];
+  p.display = (int)v[4]; p.gamma_c = (float)v[5];
+  bool wantU8 = false;
+  napi_get_value_bool(env, a[7], &wantU8);
+  const size_t np = (size_t)h->W * h->H * 4;
+  void *pf = nullptr, *p8 = nullptr;
+  napi_value f = makeTyped(env, napi_float32_array, np, 4, &pf), u8 = nullptr;
+  if (wantU8) u8 = makeTyped(env, napi_uint8_array, np, 1, &p8);
+  sail_tfilter_info n;
+  const int rc = sail_temporal_filter(h->ctx, &p, (float*)pf, nullptr, (uint8_t*)p8, &n);
+  if (rc) return throwSail(env, "sail_temporal_filter", rc, h->ctx);
+  napi_value out, inf, passes;
+  NAPI_OK(napi_create_object(env, &out));
+  NAPI_OK(napi_create_object(env, &inf));
+  napi_set_named_property(env, inf, "k", num(env, (double)n.k));
+  napi_set_named_property(env, inf, "temporalPixels", num(env, (double)n.temporal_pixels));
+  napi_set_named_property(env, inf, "spatialPixels", num(env, (double)n.spatial_pixels));
+  napi_set_named_property(env, inf, "nonfinite", num(env, (double)n.nonfinite));
+  napi_set_named_property(env, inf, "iterations", num(env, n.iterations));
+  napi_set_named_property(env, inf, "kernelMs", num(env, n.kernel_ms));
+  NAPI_OK(napi_create_array_with_length(env, (size_t)n.iterations + 1, &passes));
+  for (int i = 0; i <= n.iterations; i++) napi_set_element(env, passes, (uint32_t)i, num(env, n.pass_ms[i]));
+  NAPI_OK(napi_set_named_property(env, inf, "passMs", passes));
+  NAPI_OK(napi_set_named_property(env, out, "rgba", f));
+  if (wantU8) NAPI_OK(napi_set_named_property(env, out, "rgba8", u8));
+  NAPI_OK(napi_set_named_property(env, out, "info", inf));
+  return out;
+}
 // (ctx, timeoutMs) -> whether the scene's run-time kernel is loaded (sail_kernel_ready; -1 waits for its build)
 napi_value KernelReady(napi_env env, napi_callback_info info) {
   napi_value a[2];
@@ -798,6 +905,11 @@ napi_value Init(napi_env env, napi_value exports) {
       {"temporalResolve", 0, TemporalResolve, 0, 0, 0, napi_enumerable, 0},
       {"temporalRead", 0, TemporalRead, 0, 0, 0, napi_enumerable, 0},
       {"temporalLoadHistory", 0, TemporalLoadHistory, 0, 0, 0, napi_enumerable, 0},
+      {"temporalMoments", 0, TemporalMoments, 0, 0, 0, napi_enumerable, 0},
+      {"temporalLoadMoments", 0, TemporalLoadMoments, 0, 0, 0, napi_enumerable, 0},
+      {"temporalReadMoments", 0, TemporalReadMoments, 0, 0, 0, napi_enumerable, 0},
+      {"temporalFilterDefaults", 0, TemporalFilterDefaults, 0, 0, 0, napi_enumerable, 0},
+      {"temporalFilter", 0, TemporalFilter, 0, 0, 0, napi_enumerable, 0},
       {"kernelReady", 0, KernelReady, 0, 0, 0, napi_enumerable, 0},
       {"kernelInfo", 0, KernelInfo, 0, 0, 0, napi_enumerable, 0},
       {"pick", 0, Pick, 0, 0, 0, napi_enumerable, 0},

@@ -18,7 +18,8 @@
 // into it with the samples rendered since (sail_temporal_begin / sail_temporal_resolve). With the option
 // temporal: true | {cap, posTol} (off by default) render / renderSamples / renderUntil call temporalBegin whenever they
 // restart the frame, and image() shows the resolve instead of the bare frame for the pointwise display filters, so an
-// orbit keeps the picture instead of dropping to one noisy sample.
+// orbit keeps the picture instead of dropping to one noisy sample. With temporal: {moments: true} the luminance moments are
+// tracked as well and temporalFilter({...}) runs the a-trous passes over the resolved picture (sail_temporal_filter).
 const native = require('./native');
 const { filterConfig } = require('./filter');
 
@@ -61,7 +62,8 @@ class Renderer {
       throw new Error("Renderer: partition 'samples' needs accumulation 'sum' (a running mean cannot be split by samples)");
     this.aov = opts.aov !== false;
     this.display = opts.display === undefined ? !!this.canvas : !!opts.display;
-    // camera-motion reprojection, off by default: true, or {cap, posTol} (left out: sail_temporal_defaults' 32 and 0.05)
+    // camera-motion reprojection, off by default: true, or {cap, posTol, moments} (left out: sail_temporal_defaults' 32 and
+    // 0.05, no moment tracking)
     this.temporal = opts.temporal ? Object.assign({}, opts.temporal === true ? {} : opts.temporal) : null;
     if (this.temporal && this.accumulation === 'compat8')
       throw new Error("Renderer: temporal needs accumulation 'sum' or 'mix' (8-bit frames carry no sample count)");
@@ -75,6 +77,8 @@ class Renderer {
     // milliseconds: renderer.js:45-52); until it is loaded render() uses the precompiled kernel of the scene's plugin
     // set, with identical frames. waitKernel (ms, -1 = until built) makes each launch wait for it instead [0].
     if (opts.waitKernel !== undefined) this.lib.setDebug(this.ctx, 10, opts.waitKernel);
+    // temporal: {moments: true} tracks the luminance moments beside the colour history, for temporalFilter()
+    if (this.temporal && this.temporal.moments) this.lib.temporalMoments(this.ctx, true);
     this.timeStart = Date.now();
     this.filter = filterConfig({ name: 'color', params: {} });
     this.pixels = null;
@@ -205,6 +209,24 @@ class Renderer {
     }
     const t = this.temporal || {};
     return this.lib.temporalResolve(this.ctx, t.cap, t.posTol, kind, gamma, true);
+  }
+  // The a-trous passes over the resolved picture of the current view, steered by the variance of the tracked luminance
+  // moments (sail_temporal_filter): needs the option temporal: {moments: true}, aov: true, and a temporalResolve of the
+  // current view. Options left out keep the library's defaults (4 passes, sigmaL 4, sigmaX 0.2, minHist 4, display
+  // 'color', gamma 2.2); display asks for rgba8 as well. Returns {rgba: Float32Array (row 0 = bottom), rgba8?, info: {k,
+  // temporalPixels, spatialPixels, nonfinite, iterations, kernelMs, passMs}}. Neither the frame nor the history changes.
+  temporalFilter({ iterations, sigmaL, sigmaX, minHist, display, gamma } = {}) {
+    if (!this.aov)
+      throw new Error('Renderer.temporalFilter reads the normal and position AOVs: create the Renderer with aov: true');
+    if (!(this.temporal && this.temporal.moments))
+      throw new Error('Renderer.temporalFilter needs the tracked moments: create the Renderer with temporal: {moments: true}');
+    const kinds = { color: 0, gamma: 1, tonemapping: 2 };
+    let kind;
+    if (display !== undefined) {
+      kind = typeof display === 'number' ? display : kinds[display];
+      if (kind === undefined) throw new Error(`Renderer.temporalFilter: unknown display '${display}' (color | gamma | tonemapping)`);
+    }
+    return this.lib.temporalFilter(this.ctx, iterations, sigmaL, sigmaX, minHist, kind, gamma, display !== undefined);
   }
 
   // the display pass: pixelFilter over the accumulated frame -> RGBA8 (row 0 = bottom, GL order); with the temporal option
