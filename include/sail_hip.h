@@ -450,6 +450,47 @@ int sail_temporal_filter_defaults(sail_tfilter_params* p);
 int sail_temporal_filter(sail_ctx* ctx, const sail_tfilter_params* p, float* out_rgba, float* out_var, uint8_t* out_rgba8,
                          sail_tfilter_info* info);
 
+/* ---- keeping the temporal history across an object drag (no reference counterpart: the reference restarts its
+ * accumulation on every drag step, src/scene/scene.js:65-68; every drag there is a pure translation of one object,
+ * scene.js:143-261, which the host knows exactly) ----
+ * sail_move_objects is sail_update_objects without the loss of the temporal state: it decodes and uploads the rows, runs
+ * the last-bounce plan, restarts the settle count and the accumulator (the noise mark goes) exactly as sail_update_objects,
+ * but leaves the current view, the committed history and the moment maps alone. If a view is current or a history is
+ * committed, the context also keeps, for the next sail_temporal_begin, a pending table D of n rows of 3 floats (+0 at first)
+ * and a pending cap mc (+inf at first):
+ *   D[r] = D[r] + motion[r]   per component, in f32, in call order (motion == NULL: every component +0)
+ *   mc = min(mc, hist_cap)    when hist_cap != 0
+ * and pending becomes 1. With no temporal state at all the call is exactly sail_update_objects: nothing is pending and the
+ * next begin finds no history. For sail_temporal_filter's "resolved since the accumulator last restarted" rule it is an
+ * accumulator restart.
+ *
+ * sail_temporal_begin with pending == 1 commits as always, computes G_cur from the new rows, then reprojects with motion:
+ * a pixel whose first hit is on row id shows a surface point that sat at Xp = X - D[id] in the previous frame, so
+ *   (X, id) = G_cur[p];  id < 0 -> R[p] = 0
+ *   d = D[(int)id];  Xp = X - d                                            (per component)
+ *   c_i, u, v, iu, fu, iv, fv exactly as the reproject above with Xp in the place of X;  r = Xp - eye_prev;  lim as there
+ *   taps as there, with e = Xp - G_prev[q].xyz                             (the id test still compares with (float)id)
+ *   wsum > 0 ? R[p] = (acc / wsum, min(m, mc)) : R[p] = 0
+ * and the moment reproject, with tracking on, uses the same Xp and stores MR.z = min(m, mc). The id and position tests
+ * reject what the move uncovered: a pixel whose row did not move but which a moved row used to hide projects onto that
+ * row's texels and finds no history. mc is there because a move changes the shading everywhere (shadows, reflections,
+ * bounce light): clamping the count of a history that crosses a move lets the new samples take over faster; it applies to
+ * every pixel. After a successful begin D is +0, mc is +inf and pending is 0; a begin that fails keeps them.
+ * sail_set_scene, sail_update_objects and sail_temporal_load_history clear them; sail_reset, sail_load_accum,
+ * sail_set_accum_mode and sail_set_partition keep them. With pending == 0 a begin launches the kernels above with the
+ * arguments above: no table, no extra load, the same bits.
+ *
+ * Validation, before anything changes (a refused call leaves rows, accumulator and temporal state as they were):
+ * SAIL_E_STATE without a scene; SAIL_E_INVALID for an n that is not the scene's or objects == NULL, as sail_update_objects,
+ * for a motion component that is not finite and for a hist_cap that is neither 0 nor finite and >= 1. A multi-device
+ * context fans the rows out as sail_update_objects does; the pending state lives with the temporal maps on device 0. */
+/* sail_update_objects that keeps the temporal state. motion: n x 3 f32, the translation of each row since the rows the
+ * context holds now (NULL: all +0). hist_cap: 0 = none, else finite and >= 1. */
+int sail_move_objects(sail_ctx* ctx, const float* objects, int n, const float* motion, float hist_cap);
+/* what is pending for the next sail_temporal_begin: motion (n x 3, may be NULL), *hist_cap (+inf when none), *pending (1
+ * after a sail_move_objects that found temporal state, until the next successful begin); each may be NULL */
+int sail_temporal_pending_motion(sail_ctx* ctx, float* motion, float* hist_cap, int* pending);
+
 /* ---- checkpoint / resume of a progressive render (no reference counterpart: the reference restarts its
  * accumulation on every camera or object change, src/core/renderer.js:57-60, src/scene/scene.js:65-68) ----
  * A context's accumulation is `parts` raw accumulators (1 for sail_create, one per device for sail_create_multi),

@@ -56,6 +56,7 @@ EXPORTS = (
     "sail_temporal_load_history",
     "sail_temporal_moments", "sail_temporal_load_moments", "sail_temporal_read_moments",
     "sail_temporal_filter_defaults", "sail_temporal_filter",
+    "sail_move_objects", "sail_temporal_pending_motion",
 )
 
 
@@ -244,6 +245,8 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
         "sail_temporal_filter_defaults": (ctypes.c_int, [ctypes.POINTER(TfilterParams)]),
         "sail_temporal_filter": (ctypes.c_int, [vp, ctypes.POINTER(TfilterParams), f32p, f32p,
                                                 ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(TfilterInfo)]),
+        "sail_move_objects": (ctypes.c_int, [vp, f32p, ctypes.c_int, f32p, ctypes.c_float]),
+        "sail_temporal_pending_motion": (ctypes.c_int, [vp, f32p, f32p, ctypes.POINTER(ctypes.c_int)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -590,6 +593,7 @@ class Context:
         pl = Plugins(*[int(m) for m in masks])
         self._check(self.lib.sail_set_scene(self.h, _ptr(o), n, _ptr(t), tn, _ptr(l), ln, ctypes.byref(pl)),
                     "sail_set_scene")
+        self._n = int(n)
 
     def set_scene_dict(self, sc: dict):
         self.set_scene(sc["objects"], sc["n"], sc["texparams"], sc["tn"], sc["lights"], sc["ln"],
@@ -784,6 +788,32 @@ class Context:
         e = _f32(eye_prev)
         self._check(self.lib.sail_temporal_load_history(self.h, _ptr(h), _ptr(gg), _ptr(m, ctypes.c_double), _ptr(e)),
                     "sail_temporal_load_history")
+
+    def move_objects(self, objects, motion=None, hist_cap: float = 0.0):
+        """New object rows that keep the temporal state (sail_move_objects). `motion` is (n, 3) f32, each row's
+        translation since the rows the context holds now (None: no row moved); `hist_cap` 0 for none, else the count a
+        history that crosses the move is clamped to. The next temporal_begin reprojects with the motion."""
+        o = _f32(objects)
+        if o.size % 18:
+            raise SailError("move_objects: object rows have 18 floats each")
+        n = o.size // 18
+        m = None
+        if motion is not None:
+            m = _f32(motion)
+            if m.size != n * 3:
+                raise SailError(f"move_objects: motion must have shape {(n, 3)}")
+        self._check(self.lib.sail_move_objects(self.h, _ptr(o), n, _ptr(m), float(hist_cap)), "sail_move_objects")
+
+    def temporal_pending_motion(self) -> dict:
+        """What is pending for the next temporal_begin (sail_temporal_pending_motion): "motion" (n, 3) f32 for the n rows
+        of the scene set through this object, "hist_cap" (inf when none) and "pending"."""
+        n = getattr(self, "_n", 0)
+        motion = np.zeros((n, 3), dtype=np.float32)
+        cap = ctypes.c_float()
+        pending = ctypes.c_int()
+        self._check(self.lib.sail_temporal_pending_motion(self.h, _ptr(motion) if n else _ptr(None), ctypes.byref(cap),
+                                                          ctypes.byref(pending)), "sail_temporal_pending_motion")
+        return {"motion": motion, "hist_cap": float(cap.value), "pending": int(pending.value)}
 
     def temporal_moments(self, on: bool = True):
         """Switch the tracking of the luminance moments on (three more maps, zeroed) or off (freed)

@@ -37,10 +37,12 @@ hipError_t sail_launch_denoise_atrous(const SailDenoiseAtrousArgs& A, hipStream_
 #include "sail_temporal.h"
 hipError_t sail_launch_gbuffer(const SailGbufferArgs& A, hipStream_t s);
 hipError_t sail_launch_reproject(const SailReprojectArgs& A, hipStream_t s);
+hipError_t sail_launch_reproject_moved(const SailReprojectMovedArgs& A, hipStream_t s);
 hipError_t sail_launch_temporal_resolve(const SailResolveArgs& A, hipStream_t s);
 // sail_tfilter.hip: the moment reproject and resolve passes and the temporal filter's prepare pass
 #include "sail_tfilter.h"
 hipError_t sail_launch_moment_reproject(const SailMomentReprojectArgs& A, hipStream_t s);
+hipError_t sail_launch_moment_reproject_moved(const SailMomentReprojectMovedArgs& A, hipStream_t s);
 hipError_t sail_launch_moment_resolve(const SailMomentResolveArgs& A, hipStream_t s);
 hipError_t sail_launch_tfilter_prepare(const SailTfilterPrepareArgs& A, hipStream_t s);
 
@@ -227,7 +229,8 @@ struct sail_ctx {
   // Camera-motion reprojection (sail_temporal_*): one block, allocated on first use, holding the five float4 maps, the
   // RGBA8 map and three counts per 16x16 tile; the map pointers are swapped when a view is committed. tpHaveCur: a view
   // is current (G_cur, R and Out are its); tpHavePrev: a history is committed (G_prev, Hist and tpPrev are its).
-  // sail_set_scene and sail_update_objects drop both. On a multi-device context device 0's sub-context holds it.
+  // sail_set_scene and sail_update_objects drop both (sail_move_objects keeps them). On a multi-device context device
+  // 0's sub-context holds it.
   void* tpWork = nullptr;
   float4 *tpGcur = nullptr, *tpGprev = nullptr, *tpHist = nullptr, *tpR = nullptr, *tpOut = nullptr;
   bool tpHaveCur = false, tpHavePrev = false;
@@ -239,6 +242,15 @@ struct sail_ctx {
   void* tpMom = nullptr;
   float4 *tpMhist = nullptr, *tpMR = nullptr, *tpMout = nullptr;
   bool tpResolved = false;
+  // Object motion pending for the next sail_temporal_begin (sail_move_objects): tpMotion is the table D, n rows of
+  // (d.xyz, 0), the sum of the moves since the last begin; tpMotionCap is mc (+inf: none). tpMotionDev is D's device copy,
+  // allocated on first use and uploaded by the begin that consumes it. sail_set_scene, sail_update_objects and
+  // sail_temporal_load_history clear the pending state; on a multi-device context device 0's sub-context holds it.
+  bool tpMotionPending = false;
+  std::vector<float> tpMotion;
+  float tpMotionCap = INFINITY;
+  float4* tpMotionDev = nullptr;
+  int tpMotionDevRows = 0;
   nccl_comm_t comm = nullptr;
   int commRanks = 0, commRank = 0;
   // Reduced frame (root of sail_reduce / device 0 of a multi-device context): the sum of every rank's
@@ -1187,6 +1199,13 @@ hipError_t zeroMoments(sail_ctx* c) {
   return hipMemsetAsync(c->tpMom, 0, (size_t)c->W * c->H * 48, c->stream);
 }
 
+// nothing is pending for the next sail_temporal_begin any more (sail_move_objects)
+void clearMotion(sail_ctx* c) {
+  c->tpMotionPending = false;
+  c->tpMotion.clear();
+  c->tpMotionCap = INFINITY;
+}
+
 // asynchronous RCCL errors (ncclCommGetAsyncError): a failed collective surfaces here, not at enqueue time
 int commCheck(sail_ctx* c, nccl_comm_t comm) {
   if (!comm || !g_rccl.commGetAsyncError) return SAIL_OK;
@@ -1477,7 +1496,7 @@ void sail_destroy(sail_ctx* c) {
   for (auto& pr : c->pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
   for (auto e : c->evPool) (void)hipEventDestroy(e);
   void* bufs[] = {c->accum, c->frame, c->frameN, c->frameP, c->aovN, c->aovP, c->filterOut, c->filterOut8, c->stage, c->segCounter, c->prims, c->tp, c->lt, c->lightObjRow, c->samples, c->wf,
-                  c->noiseMark, c->noiseOut, c->noisePix, c->denoiseWork, c->tpWork, c->tpMom};
+                  c->noiseMark, c->noiseOut, c->noisePix, c->denoiseWork, c->tpWork, c->tpMom, c->tpMotionDev};
   for (void* b : bufs) if (b) (void)hipFree(b);
   if (c->samplesPinned) (void)hipHostFree(c->samplesPinned);
   if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1672,6 +1691,7 @@ int sail_set_scene(sail_ctx* c, const float* objects, int n, const float* texpar
   c->n = n; c->tn = tn; c->ln = ln;
   c->haveScene = true;
   c->tpHaveCur = c->tpHavePrev = c->tpResolved = false;  // the temporal maps' ids and positions are stale
+  clearMotion(c);
   HIPCHK(c, zeroMoments(c));
   // Tracer.update links the scene's program (tracer.js:42-90): the plugin set's kernel starts building now, in the
   // background; the precompiled kernel of the set serves until it is loaded
@@ -1681,15 +1701,9 @@ int sail_set_scene(sail_ctx* c, const float* objects, int n, const float* texpar
   return resetAccum(c);
 }
 
-int sail_update_objects(sail_ctx* c, const float* objects, int n) {
-  if (c && !c->subs.empty()) {
-    for (sail_ctx* s : c->subs) if (int rc = sail_update_objects(s, objects, n)) return relay(c, rc, s);
-    c->dirty = false;
-    c->loadMissing = 0;
-    return SAIL_OK;
-  }
-  if (!c || !c->haveScene) return c ? fail(c, SAIL_E_STATE, "sail_update_objects before sail_set_scene") : SAIL_E_INVALID;
-  if (n != c->n || !objects) return fail(c, SAIL_E_INVALID, "sail_update_objects: n must stay %d", c->n);
+// New rows for a single-device context whose arguments have been checked: sail_update_objects (the temporal state goes,
+// its ids and positions are stale) and sail_move_objects (it stays: the caller records how the rows moved)
+static int updateRows(sail_ctx* c, const float* objects, int n, bool keepTemporal) {
   HIPCHK(c, hipSetDevice(c->device));
   std::vector<SailPrim> prims;
   decodePrims(objects, n, c->tn, c->plugins.shape_mask, prims, &c->shadowAnyHit, &c->scene);
@@ -1704,12 +1718,71 @@ int sail_update_objects(sail_ctx* c, const float* objects, int n) {
   if (int rc = uploadPrims(c, prims)) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->objectsRows.assign(objects, objects + (size_t)n * 18);
-  c->tpHaveCur = c->tpHavePrev = c->tpResolved = false;  // the temporal maps' ids and positions are stale
-  HIPCHK(c, zeroMoments(c));
+  if (!keepTemporal) {
+    c->tpHaveCur = c->tpHavePrev = c->tpResolved = false;  // the temporal maps' ids and positions are stale
+    clearMotion(c);
+    HIPCHK(c, zeroMoments(c));
+  }
   dropValues(c);  // the rows' values moved: the value kernel goes, the settle count restarts
   refreshJit(c);  // a drag keeps the types kernel; a changed shape type starts the new rows' kernel building
   refreshValues(c);
   return resetAccum(c);
+}
+
+int sail_update_objects(sail_ctx* c, const float* objects, int n) {
+  if (c && !c->subs.empty()) {
+    for (sail_ctx* s : c->subs) if (int rc = sail_update_objects(s, objects, n)) return relay(c, rc, s);
+    c->dirty = false;
+    c->loadMissing = 0;
+    return SAIL_OK;
+  }
+  if (!c || !c->haveScene) return c ? fail(c, SAIL_E_STATE, "sail_update_objects before sail_set_scene") : SAIL_E_INVALID;
+  if (n != c->n || !objects) return fail(c, SAIL_E_INVALID, "sail_update_objects: n must stay %d", c->n);
+  return updateRows(c, objects, n, false);
+}
+
+int sail_move_objects(sail_ctx* c, const float* objects, int n, const float* motion, float hist_cap) {
+  if (!c) return SAIL_E_INVALID;
+  // everything is checked before anything changes: a refused call leaves rows, accumulator and temporal state alone
+  if (!c->haveScene) return fail(c, SAIL_E_STATE, "sail_move_objects before sail_set_scene");
+  if (n != c->n || !objects) return fail(c, SAIL_E_INVALID, "sail_move_objects: n must stay %d", c->n);
+  for (size_t i = 0; motion && i < (size_t)n * 3; i++)
+    if (!std::isfinite(motion[i]))
+      return fail(c, SAIL_E_INVALID, "sail_move_objects: the motion of row %d is not finite", (int)(i / 3));
+  if (!(hist_cap == 0.0f || (std::isfinite(hist_cap) && hist_cap >= 1.0f)))
+    return fail(c, SAIL_E_INVALID, "sail_move_objects: hist_cap %g must be 0 (none) or finite and >= 1", (double)hist_cap);
+  if (!c->subs.empty()) {  // the temporal maps, and with them what is pending, live on device 0
+    for (size_t i = 0; i < c->subs.size(); i++) {
+      sail_ctx* s = c->subs[i];
+      if (int rc = i == 0 ? sail_move_objects(s, objects, n, motion, hist_cap) : sail_update_objects(s, objects, n))
+        return relay(c, rc, s);
+    }
+    c->dirty = false;
+    c->loadMissing = 0;
+    return SAIL_OK;
+  }
+  const bool temporal = c->tpHaveCur || c->tpHavePrev;
+  if (int rc = updateRows(c, objects, n, temporal)) return rc;
+  if (!temporal) return SAIL_OK;  // no temporal state: exactly sail_update_objects, nothing is pending
+  if (!c->tpMotionPending) {
+    c->tpMotion.assign((size_t)n * 4, 0.0f);
+    c->tpMotionCap = INFINITY;
+    c->tpMotionPending = true;
+  }
+  for (int r = 0; motion && r < n; r++)
+    for (int j = 0; j < 3; j++) c->tpMotion[(size_t)r * 4 + j] = c->tpMotion[(size_t)r * 4 + j] + motion[r * 3 + j];
+  if (hist_cap != 0.0f) c->tpMotionCap = hist_cap < c->tpMotionCap ? hist_cap : c->tpMotionCap;
+  return SAIL_OK;
+}
+
+int sail_temporal_pending_motion(sail_ctx* c, float* motion, float* hist_cap, int* pending) {
+  if (!c) return SAIL_E_INVALID;
+  if (!c->subs.empty()) return relay(c, sail_temporal_pending_motion(c->subs[0], motion, hist_cap, pending), c->subs[0]);
+  for (int r = 0; motion && r < c->n; r++)
+    for (int j = 0; j < 3; j++) motion[r * 3 + j] = c->tpMotionPending ? c->tpMotion[(size_t)r * 4 + j] : 0.0f;
+  if (hist_cap) *hist_cap = c->tpMotionPending ? c->tpMotionCap : INFINITY;
+  if (pending) *pending = c->tpMotionPending ? 1 : 0;
+  return SAIL_OK;
 }
 
 int sail_set_accum_mode(sail_ctx* c, int mode) {
@@ -2372,6 +2445,18 @@ int sail_temporal_begin(sail_ctx* c, const double mvp[16], const float eye[3], c
   HIPCHK(c, hipSetDevice(c->device));
   if (int rc = sail_sync(c)) return rc;
   if (int rc = ensureTemporal(c)) return rc;
+  const bool moved = c->tpMotionPending;
+  if (moved && c->tpMotionDevRows < (c->n > 0 ? c->n : 1)) {  // before anything is committed: a begin that fails keeps it all
+    if (c->tpMotionDev) HIPCHK(c, hipFree(c->tpMotionDev));
+    c->tpMotionDev = nullptr;
+    c->tpMotionDevRows = 0;
+    const int rows = c->n > 0 ? c->n : 1;
+    if (hipMalloc(&c->tpMotionDev, sizeof(float4) * (size_t)rows) != hipSuccess) {
+      c->tpMotionDev = nullptr;
+      return fail(c, SAIL_E_OOM, "object motion table");
+    }
+    c->tpMotionDevRows = rows;
+  }
   if (c->tpHaveCur) {  // commit the view that was current
     std::swap(c->tpHist, c->tpOut);
     std::swap(c->tpGprev, c->tpGcur);
@@ -2401,19 +2486,27 @@ int sail_temporal_begin(sail_ctx* c, const double mvp[16], const float eye[3], c
   memcpy(M.Mp, B.Mp, sizeof M.Mp);
   memcpy(M.eyePrev, B.eyePrev, sizeof M.eyePrev);
   M.tol2 = B.tol2; M.W = c->W; M.H = c->H; M.haveHist = B.haveHist;
+  // an object motion is pending (sail_move_objects): the motion kernels, with the table uploaded ahead of them
+  SailReprojectMovedArgs BM;
+  SailMomentReprojectMovedArgs MM;
+  BM.base = B; BM.motion = c->tpMotionDev; BM.n = c->n; BM.mc = c->tpMotionCap;
+  MM.base = M; MM.motion = c->tpMotionDev; MM.n = c->n; MM.mc = c->tpMotionCap;
   hipEvent_t ev[4] = {};
   for (int i = 0; i < nev; i++)
     if (int rc = getEvent(c, &ev[i])) {
       for (int j = 0; j < i; j++) c->evPool.push_back(ev[j]);
       return rc;
     }
-  hipError_t e = hipEventRecord(ev[0], c->stream);
+  hipError_t e = hipSuccess;
+  if (moved && c->n > 0)
+    e = hipMemcpyAsync(c->tpMotionDev, c->tpMotion.data(), sizeof(float4) * (size_t)c->n, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipEventRecord(ev[0], c->stream);
   if (e == hipSuccess) e = sail_launch_gbuffer(A, c->stream);
   if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
-  if (e == hipSuccess) e = sail_launch_reproject(B, c->stream);
+  if (e == hipSuccess) e = moved ? sail_launch_reproject_moved(BM, c->stream) : sail_launch_reproject(B, c->stream);
   if (e == hipSuccess) e = hipEventRecord(ev[2], c->stream);
   if (c->tpMom) {
-    if (e == hipSuccess) e = sail_launch_moment_reproject(M, c->stream);
+    if (e == hipSuccess) e = moved ? sail_launch_moment_reproject_moved(MM, c->stream) : sail_launch_moment_reproject(M, c->stream);
     if (e == hipSuccess) e = hipEventRecord(ev[3], c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(c->tpMout, c->tpMR, np * 16, hipMemcpyDeviceToDevice, c->stream);
   }
@@ -2429,6 +2522,7 @@ int sail_temporal_begin(sail_ctx* c, const double mvp[16], const float eye[3], c
   for (int i = 0; i < 16; i++) c->tpCur.m[i] = (float)mvp[i];
   memcpy(c->tpCur.eye, eye, sizeof c->tpCur.eye);
   c->tpHaveCur = true;
+  clearMotion(c);  // consumed: the next begin is today's unless the rows move again
   c->tpHitPixels = sumTiles(host, 0, nt);
   if (info) {
     memset(info, 0, sizeof *info);
@@ -2536,6 +2630,7 @@ int sail_temporal_load_history(sail_ctx* c, const float* hist, const float* g, c
   c->tpHavePrev = true;
   c->tpHaveCur = false;
   c->tpResolved = false;
+  clearMotion(c);  // a loaded history belongs to the rows as they are now
   if (c->tpMom) {  // the loaded history carries no moments
     HIPCHK(c, hipMemsetAsync(c->tpMhist, 0, bytes, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -30,6 +30,14 @@ struct SailReprojectArgs {
   int haveHist;           // 0: no committed history, R = 0 everywhere (Gprev and Hist are not read)
 };
 
+// sail_reproject_moved_kernel: the reproject pass of a begin with an object motion pending (sail_move_objects)
+struct SailReprojectMovedArgs {
+  SailReprojectArgs base;
+  const float4* motion;   // n rows of (d.xyz, 0): each row's translation since G_prev, read per lane by G_cur's id
+  int n;
+  float mc;               // the count of a history that crosses the move is at most this (+inf: no cap)
+};
+
 struct SailResolveArgs {
   const float4* S;        // the accumulator the context shows
   const float4* R;

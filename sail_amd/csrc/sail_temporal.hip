@@ -19,6 +19,9 @@
 //  * reproject: a data-dependent gather of up to four float4 pairs (G_prev, Hist) per pixel, 16-byte loads, straight
 //    from L2 / HBM: neighbouring pixels of the new view land on neighbouring texels of the old one, so a wave's taps
 //    share cache lines. Taps outside the frame are never loaded. No LDS staging;
+//  * reproject with an object motion pending (sail_move_objects; sail_reproject_moved_kernel, DESIGN.md §5,
+//    "sail_reproject_moved_kernel"): the same body, which first takes the pixel's row translation from a table of n float4
+//    (one more 16-byte load by the id of G_cur; the table stays in L1/L2) and looks up X - d instead of X;
 //  * resolve: pointwise, one float4 of S and of R in, one float4 and one RGBA8 word out;
 //  * the counts are wave ballots, summed across the four waves through LDS in a fixed order and per tile on the host;
 //  * lanes outside ragged tiles load nothing and store nothing;
@@ -88,7 +91,11 @@ extern "C" __global__ void __launch_bounds__(256) sail_gbuffer_kernel(SailGbuffe
   if (A.t) A.t[pix] = best;
 }
 
-extern "C" __global__ void __launch_bounds__(256) sail_reproject_kernel(SailReprojectArgs A) {
+// The reproject pass. MOVED = false is sail_reproject_kernel as it always was: motion, n and mc are not read. MOVED = true is the
+// pass after sail_move_objects: the point the pixel shows sat at Xp = X - D[id] in the previous frame, and the count that
+// crosses the move is at most mc.
+template <bool MOVED>
+__device__ __forceinline__ void tpReproject(const SailReprojectArgs& A, const float4* motion, int n, float mc) {
   __shared__ uint32_t sHit[4], sHist[4];
   const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
   bool hit = false, found = false;
@@ -98,16 +105,24 @@ extern "C" __global__ void __launch_bounds__(256) sail_reproject_kernel(SailRepr
     float4 out = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     hit = !(g.w < 0.0f);
     if (hit && A.haveHist) {
-      const float c0 = ((A.Mp[0][0] * g.x + A.Mp[0][1] * g.y) + A.Mp[0][2] * g.z) + A.Mp[0][3];
-      const float c1 = ((A.Mp[1][0] * g.x + A.Mp[1][1] * g.y) + A.Mp[1][2] * g.z) + A.Mp[1][3];
-      const float c3 = ((A.Mp[2][0] * g.x + A.Mp[2][1] * g.y) + A.Mp[2][2] * g.z) + A.Mp[2][3];
+      float px = g.x, py = g.y, pz = g.z;
+      if (MOVED) {
+        const int id = (int)g.w;
+        if ((uint32_t)id < (uint32_t)n) {  // G_cur comes from the rows the table was sized for; a row beyond it is never loaded
+          const float4 d = motion[id];
+          px = g.x - d.x; py = g.y - d.y; pz = g.z - d.z;
+        }
+      }
+      const float c0 = ((A.Mp[0][0] * px + A.Mp[0][1] * py) + A.Mp[0][2] * pz) + A.Mp[0][3];
+      const float c1 = ((A.Mp[1][0] * px + A.Mp[1][1] * py) + A.Mp[1][2] * pz) + A.Mp[1][3];
+      const float c3 = ((A.Mp[2][0] * px + A.Mp[2][1] * py) + A.Mp[2][2] * pz) + A.Mp[2][3];
       if (c3 > 0.0f) {
         const float u = ((c0 / c3) * 0.5f + 0.5f) * (float)A.W - 0.5f;
         const float v = ((c1 / c3) * 0.5f + 0.5f) * (float)A.H - 0.5f;
         if (tpFinite(u) && tpFinite(v)) {
           const float iu = __builtin_floorf(u), iv = __builtin_floorf(v);
           const float fu = u - iu, fv = v - iv;
-          const float rx = g.x - A.eyePrev[0], ry = g.y - A.eyePrev[1], rz = g.z - A.eyePrev[2];
+          const float rx = px - A.eyePrev[0], ry = py - A.eyePrev[1], rz = pz - A.eyePrev[2];
           const float r2 = (rx * rx + ry * ry) + rz * rz;
           const float lim = A.tol2 * r2;
           float ar = 0.0f, ag = 0.0f, ab = 0.0f, wsum = 0.0f, m = __builtin_inff();
@@ -123,7 +138,7 @@ extern "C" __global__ void __launch_bounds__(256) sail_reproject_kernel(SailRepr
               const size_t q = (size_t)(int)qyf * A.W + (int)qxf;
               const float4 gq = A.Gprev[q];
               if (!(gq.w == g.w)) continue;
-              const float ex = g.x - gq.x, ey = g.y - gq.y, ez = g.z - gq.z;
+              const float ex = px - gq.x, ey = py - gq.y, ez = pz - gq.z;
               if (!((ex * ex + ey * ey) + ez * ez <= lim)) continue;
               const float4 h = A.Hist[q];
               if (!(h.w > 0.0f) || !(tpFinite(h.x) && tpFinite(h.y) && tpFinite(h.z))) continue;
@@ -132,7 +147,7 @@ extern "C" __global__ void __launch_bounds__(256) sail_reproject_kernel(SailRepr
               m = tpMin(m, h.w);
             }
           }
-          if (wsum > 0.0f) { out = make_float4(ar / wsum, ag / wsum, ab / wsum, m); found = true; }
+          if (wsum > 0.0f) { out = make_float4(ar / wsum, ag / wsum, ab / wsum, MOVED ? tpMin(m, mc) : m); found = true; }
         }
       }
     }
@@ -140,6 +155,14 @@ extern "C" __global__ void __launch_bounds__(256) sail_reproject_kernel(SailRepr
   }
   tpTileCount(hit, sHit, A.tileHit);
   tpTileCount(found, sHist, A.tileHist);
+}
+
+extern "C" __global__ void __launch_bounds__(256) sail_reproject_kernel(SailReprojectArgs A) {
+  tpReproject<false>(A, nullptr, 0, 0.0f);
+}
+
+extern "C" __global__ void __launch_bounds__(256) sail_reproject_moved_kernel(SailReprojectMovedArgs A) {
+  tpReproject<true>(A.base, A.motion, A.n, A.mc);
 }
 
 extern "C" __global__ void __launch_bounds__(256) sail_temporal_resolve_kernel(SailResolveArgs A) {
@@ -184,6 +207,11 @@ hipError_t sail_launch_gbuffer(const SailGbufferArgs& A, hipStream_t s) {
 
 hipError_t sail_launch_reproject(const SailReprojectArgs& A, hipStream_t s) {
   hipLaunchKernelGGL(sail_reproject_kernel, dim3((A.W + 15) / 16, (A.H + 15) / 16), dim3(256), 0, s, A);
+  return hipGetLastError();
+}
+
+hipError_t sail_launch_reproject_moved(const SailReprojectMovedArgs& A, hipStream_t s) {
+  hipLaunchKernelGGL(sail_reproject_moved_kernel, dim3((A.base.W + 15) / 16, (A.base.H + 15) / 16), dim3(256), 0, s, A);
   return hipGetLastError();
 }
 

@@ -15,6 +15,15 @@ struct SailMomentReprojectArgs {
   int haveHist;           // 0: no committed history, MR = 0 everywhere (Gprev and Mhist are not read)
 };
 
+// sail_moment_reproject_moved_kernel: the moment reproject of a begin with an object motion pending (motion, n and mc as
+// SailReprojectMovedArgs)
+struct SailMomentReprojectMovedArgs {
+  SailMomentReprojectArgs base;
+  const float4* motion;
+  int n;
+  float mc;
+};
+
 struct SailMomentResolveArgs {
   const float4* S;        // the accumulator the context shows
   const float4* MR;

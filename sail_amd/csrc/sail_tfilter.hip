@@ -13,6 +13,7 @@
 // MI355X design ("sail_tfilter_prepare_kernel"):
 //  * all three: one 256-thread workgroup per 16x16 tile, one lane per pixel, each wave a 16x4 strip; float4 loads and stores;
 //  * moment reproject: sail_reproject_kernel's gather with Mhist in the place of Hist (Hist is not read), no counts;
+//    sail_moment_reproject_moved_kernel is the same body after sail_move_objects, as sail_reproject_moved_kernel;
 //  * moment resolve: pointwise, one float4 of S and of MR in, one float4 out;
 //  * prepare, three phases with a barrier between them:
 //      1. the tile and a four-texel halo (24x24) are staged in LDS as two float4 per texel: (decoded normal, luminance)
@@ -80,23 +81,34 @@ __device__ __forceinline__ float tfSpatial(const float4* sA, const float4* sB, i
 
 }  // namespace
 
-extern "C" __global__ void __launch_bounds__(256) sail_moment_reproject_kernel(SailMomentReprojectArgs A) {
+// The moment reproject pass. MOVED = false is sail_moment_reproject_kernel as it always was: motion, n and mc are not read.
+// MOVED = true follows sail_reproject_moved_kernel: the same Xp = X - D[id], and MR.z = min(m, mc).
+template <bool MOVED>
+__device__ __forceinline__ void tfMomentReproject(const SailMomentReprojectArgs& A, const float4* motion, int n, float mc) {
   const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
   if (x >= A.W || y >= A.H) return;
   const size_t pix = (size_t)y * A.W + x;
   const float4 g = A.Gcur[pix];
   float4 out = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   if (!(g.w < 0.0f) && A.haveHist) {
-    const float c0 = ((A.Mp[0][0] * g.x + A.Mp[0][1] * g.y) + A.Mp[0][2] * g.z) + A.Mp[0][3];
-    const float c1 = ((A.Mp[1][0] * g.x + A.Mp[1][1] * g.y) + A.Mp[1][2] * g.z) + A.Mp[1][3];
-    const float c3 = ((A.Mp[2][0] * g.x + A.Mp[2][1] * g.y) + A.Mp[2][2] * g.z) + A.Mp[2][3];
+    float px = g.x, py = g.y, pz = g.z;
+    if (MOVED) {
+      const int id = (int)g.w;
+      if ((uint32_t)id < (uint32_t)n) {  // G_cur comes from the rows the table was sized for; a row beyond it is never loaded
+        const float4 d = motion[id];
+        px = g.x - d.x; py = g.y - d.y; pz = g.z - d.z;
+      }
+    }
+    const float c0 = ((A.Mp[0][0] * px + A.Mp[0][1] * py) + A.Mp[0][2] * pz) + A.Mp[0][3];
+    const float c1 = ((A.Mp[1][0] * px + A.Mp[1][1] * py) + A.Mp[1][2] * pz) + A.Mp[1][3];
+    const float c3 = ((A.Mp[2][0] * px + A.Mp[2][1] * py) + A.Mp[2][2] * pz) + A.Mp[2][3];
     if (c3 > 0.0f) {
       const float u = ((c0 / c3) * 0.5f + 0.5f) * (float)A.W - 0.5f;
       const float v = ((c1 / c3) * 0.5f + 0.5f) * (float)A.H - 0.5f;
       if (tfFinite(u) && tfFinite(v)) {
         const float iu = __builtin_floorf(u), iv = __builtin_floorf(v);
         const float fu = u - iu, fv = v - iv;
-        const float rx = g.x - A.eyePrev[0], ry = g.y - A.eyePrev[1], rz = g.z - A.eyePrev[2];
+        const float rx = px - A.eyePrev[0], ry = py - A.eyePrev[1], rz = pz - A.eyePrev[2];
         const float r2 = (rx * rx + ry * ry) + rz * rz;
         const float lim = A.tol2 * r2;
         float a1 = 0.0f, a2 = 0.0f, wsum = 0.0f, m = __builtin_inff();
@@ -112,7 +124,7 @@ extern "C" __global__ void __launch_bounds__(256) sail_moment_reproject_kernel(S
             const size_t q = (size_t)(int)qyf * A.W + (int)qxf;
             const float4 gq = A.Gprev[q];
             if (!(gq.w == g.w)) continue;
-            const float ex = g.x - gq.x, ey = g.y - gq.y, ez = g.z - gq.z;
+            const float ex = px - gq.x, ey = py - gq.y, ez = pz - gq.z;
             if (!((ex * ex + ey * ey) + ez * ez <= lim)) continue;
             const float4 h = A.Mhist[q];
             if (!(h.z > 0.0f) || !(tfFinite(h.x) && tfFinite(h.y))) continue;
@@ -121,11 +133,19 @@ extern "C" __global__ void __launch_bounds__(256) sail_moment_reproject_kernel(S
             m = tfMin(m, h.z);
           }
         }
-        if (wsum > 0.0f) out = make_float4(a1 / wsum, a2 / wsum, m, 0.0f);
+        if (wsum > 0.0f) out = make_float4(a1 / wsum, a2 / wsum, MOVED ? tfMin(m, mc) : m, 0.0f);
       }
     }
   }
   A.MR[pix] = out;
+}
+
+extern "C" __global__ void __launch_bounds__(256) sail_moment_reproject_kernel(SailMomentReprojectArgs A) {
+  tfMomentReproject<false>(A, nullptr, 0, 0.0f);
+}
+
+extern "C" __global__ void __launch_bounds__(256) sail_moment_reproject_moved_kernel(SailMomentReprojectMovedArgs A) {
+  tfMomentReproject<true>(A.base, A.motion, A.n, A.mc);
 }
 
 extern "C" __global__ void __launch_bounds__(256) sail_moment_resolve_kernel(SailMomentResolveArgs A) {
@@ -242,6 +262,11 @@ extern "C" __global__ void __launch_bounds__(256) sail_tfilter_prepare_kernel(Sa
 
 hipError_t sail_launch_moment_reproject(const SailMomentReprojectArgs& A, hipStream_t s) {
   hipLaunchKernelGGL(sail_moment_reproject_kernel, dim3((A.W + 15) / 16, (A.H + 15) / 16), dim3(256), 0, s, A);
+  return hipGetLastError();
+}
+
+hipError_t sail_launch_moment_reproject_moved(const SailMomentReprojectMovedArgs& A, hipStream_t s) {
+  hipLaunchKernelGGL(sail_moment_reproject_moved_kernel, dim3((A.base.W + 15) / 16, (A.base.H + 15) / 16), dim3(256), 0, s, A);
   return hipGetLastError();
 }
 

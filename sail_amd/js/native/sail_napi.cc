@@ -184,6 +184,26 @@ napi_value UpdateObjects(napi_env env, napi_callback_info info) {
   if (rc) return throwSail(env, "sail_update_objects", rc, h->ctx);
   return undef(env);
 }
+// moveObjects(ctx, objects, n, motion | null, histCap): sail_move_objects
+napi_value MoveObjects(napi_env env, napi_callback_info info) {
+  napi_value a[5];
+  if (!args(env, info, 5, a)) return nullptr;
+  Handle* h;
+  float *o, *m = nullptr;
+  size_t no, nm = 0;
+  int n;
+  double cap = 0.0;
+  if (!getHandle(env, a[0], &h) || !getArray(env, a[1], napi_float32_array, &o, &no) || !getInt(env, a[2], &n)) return nullptr;
+  if (!getArray(env, a[3], napi_float32_array, &m, &nm, true)) return nullptr;
+  NAPI_OK(napi_get_value_double(env, a[4], &cap));
+  if (n < 0 || no < (size_t)n * 18 || (m && nm < (size_t)n * 3)) {
+    napi_throw_range_error(env, nullptr, "object rows or motion shorter than n");
+    return nullptr;
+  }
+  const int rc = sail_move_objects(h->ctx, o, n, m, (float)cap);
+  if (rc) return throwSail(env, "sail_move_objects", rc, h->ctx);
+  return undef(env);
+}
 napi_value IntSetter(napi_env env, napi_callback_info info, int nargs, const char* name,
                      int (*fn3)(sail_ctx*, int, int, int), int (*fn1)(sail_ctx*, int)) {
   napi_value a[4];
@@ -883,6 +903,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"destroy", 0, Destroy, 0, 0, 0, napi_enumerable, 0},
       {"setScene", 0, SetScene, 0, 0, 0, napi_enumerable, 0},
       {"updateObjects", 0, UpdateObjects, 0, 0, 0, napi_enumerable, 0},
+      {"moveObjects", 0, MoveObjects, 0, 0, 0, napi_enumerable, 0},
       {"setAccumMode", 0, SetAccumMode, 0, 0, 0, napi_enumerable, 0},
       {"setPartition", 0, SetPartition, 0, 0, 0, napi_enumerable, 0},
       {"setLaunchSamples", 0, SetLaunchSamples, 0, 0, 0, napi_enumerable, 0},

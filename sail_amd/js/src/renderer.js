@@ -20,6 +20,8 @@
 // restart the frame, and image() shows the resolve instead of the bare frame for the pointwise display filters, so an
 // orbit keeps the picture instead of dropping to one noisy sample. With temporal: {moments: true} the luminance moments are
 // tracked as well and temporalFilter({...}) runs the a-trous passes over the resolved picture (sail_temporal_filter).
+// With temporal: {objects: true | {histCap}} a drag keeps the history too: updateObjects hands the library each row's
+// translation (sail_move_objects) and the next frame reprojects the moved object's pixels from where they were.
 const native = require('./native');
 const { filterConfig } = require('./filter');
 
@@ -65,6 +67,14 @@ class Renderer {
     // camera-motion reprojection, off by default: true, or {cap, posTol, moments} (left out: sail_temporal_defaults' 32 and
     // 0.05, no moment tracking)
     this.temporal = opts.temporal ? Object.assign({}, opts.temporal === true ? {} : opts.temporal) : null;
+    // temporal: {objects: true | {histCap}}: a drag keeps the history (sail_move_objects). histCap is the count a history
+    // that crosses a move is clamped to, so that the new samples take over the changed shadows and reflections; its
+    // default, 8, is a policy value, not a tuned one (0: no clamp).
+    this.objectHistCap = null;
+    if (this.temporal && this.temporal.objects) {
+      const h = this.temporal.objects === true ? undefined : this.temporal.objects.histCap;
+      this.objectHistCap = h === undefined ? 8 : h;
+    }
     if (this.temporal && this.accumulation === 'compat8')
       throw new Error("Renderer: temporal needs accumulation 'sum' or 'mix' (8-bit frames carry no sample count)");
     this.lib = native.load();
@@ -98,6 +108,13 @@ class Renderer {
   }
 
   updateObjects(scene) {
+    if (this.objectHistCap !== null) {
+      // the motion first: serializeObjects applies and zeroes it. The current view stays; the _restart that follows begins
+      // the same view again with the motion pending
+      const motion = scene.objectMotion();
+      this.lib.moveObjects(this.ctx, scene.serializeObjects(), this.n, motion, this.objectHistCap);
+      return;
+    }
     this.lib.updateObjects(this.ctx, scene.serializeObjects(), this.n);
     this._temporalView = false;  // so do moved objects: a drag drops the history
   }

@@ -396,6 +396,14 @@ class Scene {
       ln: Math.floor(lights.length / LIGHTS_LENGTH),
     };
   }
+  // every object's pending drag translation (temporaryTranslation), n x 3, for Renderer.updateObjects with the option
+  // temporal: {objects}. Read without consuming it: gen() (serializeObjects) applies and zeroes it afterwards, so take the
+  // motion first, then the rows.
+  objectMotion() {
+    const motion = new Float32Array(this.objects.length * 3);
+    this.objects.forEach((ob, i) => motion.set(ob.temporaryTranslation.elements.slice(0, 3), i * 3));
+    return motion;
+  }
   serializeObjects() {  // Tracer.updateObjects (tracer.js:25-40): object rows with their existing texparam ids
     const objects = [];
     for (const ob of this.objects) objects.push(...ob.gen());
