@@ -36,13 +36,11 @@ hipError_t sail_launch_denoise_atrous(const SailDenoiseAtrousArgs& A, hipStream_
 // sail_temporal.hip: the G-buffer, reproject and temporal resolve passes
 #include "sail_temporal.h"
 hipError_t sail_launch_gbuffer(const SailGbufferArgs& A, hipStream_t s);
-hipError_t sail_launch_reproject(const SailReprojectArgs& A, hipStream_t s);
-hipError_t sail_launch_reproject_moved(const SailReprojectMovedArgs& A, hipStream_t s);
+hipError_t sail_launch_reproject(const SailReprojectArgs& A, bool moved, hipStream_t s);
 hipError_t sail_launch_temporal_resolve(const SailResolveArgs& A, hipStream_t s);
 // sail_tfilter.hip: the moment reproject and resolve passes and the temporal filter's prepare pass
 #include "sail_tfilter.h"
-hipError_t sail_launch_moment_reproject(const SailMomentReprojectArgs& A, hipStream_t s);
-hipError_t sail_launch_moment_reproject_moved(const SailMomentReprojectMovedArgs& A, hipStream_t s);
+hipError_t sail_launch_moment_reproject(const SailReprojectArgs& A, bool moved, hipStream_t s);
 hipError_t sail_launch_moment_resolve(const SailMomentResolveArgs& A, hipStream_t s);
 hipError_t sail_launch_tfilter_prepare(const SailTfilterPrepareArgs& A, hipStream_t s);
 
@@ -558,6 +556,21 @@ int getEvent(sail_ctx* c, hipEvent_t* ev) {
   HIPCHK(c, hipEventCreate(ev));
   return SAIL_OK;
 }
+// up to 8 events of the pool for the length of a scope: rc is getEvent's failure, and the ones taken go back at the end
+struct PooledEvents {
+  sail_ctx* c;
+  hipEvent_t ev[8] = {};
+  int n = 0, rc = SAIL_OK;
+  PooledEvents(sail_ctx* ctx, int want) : c(ctx) {
+    while (n < want && !(rc = getEvent(c, &ev[n]))) n++;
+  }
+  ~PooledEvents() {
+    for (int i = 0; i < n; i++) c->evPool.push_back(ev[i]);
+  }
+  PooledEvents(const PooledEvents&) = delete;
+  PooledEvents& operator=(const PooledEvents&) = delete;
+  hipEvent_t operator[](int i) const { return ev[i]; }
+};
 
 // corner directions of vstrace.glsl:4-6 for one jittered inverse matrix (column-major, f32)
 void cornerDirs(const float* M, const float* eye, float out[4][3]) {
@@ -1152,13 +1165,8 @@ hipError_t runAtrous(sail_ctx* c, const DenoiseWork& w, Prepare prepare, int ite
                      float* total, int* rc) {
   const size_t np = (size_t)c->W * c->H;
   const int nev = iterations + 2;  // before the prepare pass, then after every pass
-  hipEvent_t ev[8] = {};
-  *rc = SAIL_OK;
-  for (int i = 0; i < nev; i++)
-    if ((*rc = getEvent(c, &ev[i]))) {
-      for (int j = 0; j < i; j++) c->evPool.push_back(ev[j]);
-      return hipSuccess;
-    }
+  PooledEvents ev(c, nev);
+  if ((*rc = ev.rc)) return hipSuccess;
   hipError_t e = hipEventRecord(ev[0], c->stream);
   if (e == hipSuccess) e = prepare();
   if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
@@ -1186,7 +1194,6 @@ hipError_t runAtrous(sail_ctx* c, const DenoiseWork& w, Prepare prepare, int ite
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   for (int i = 0; i + 1 < nev && e == hipSuccess; i++) e = hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]);
   if (e == hipSuccess) e = hipEventElapsedTime(total, ev[0], ev[nev - 1]);
-  for (int i = 0; i < nev; i++) c->evPool.push_back(ev[i]);
   if (e == hipSuccess && out_rgba) e = hipMemcpy(out_rgba, w.cv[cur], np * 16, hipMemcpyDeviceToHost);
   if (e == hipSuccess && out_var) e = hipMemcpy(out_var, w.var, np * 4, hipMemcpyDeviceToHost);
   if (e == hipSuccess && out_rgba8) e = hipMemcpy(out_rgba8, w.u8, np * 4, hipMemcpyDeviceToHost);
@@ -2470,43 +2477,33 @@ int sail_temporal_begin(sail_ctx* c, const double mvp[16], const float eye[3], c
   A.G = c->tpGcur;
   SailReprojectArgs B;
   memset(&B, 0, sizeof B);
-  B.Gcur = c->tpGcur; B.Gprev = c->tpGprev; B.Hist = c->tpHist; B.R = c->tpR;
+  B.Gcur = c->tpGcur; B.Gprev = c->tpGprev; B.hist = c->tpHist; B.out = c->tpR;
   B.tileHit = cnt; B.tileHist = cnt + nt;
   for (int j = 0; j < 4; j++) { B.Mp[0][j] = c->tpPrev.m[j]; B.Mp[1][j] = c->tpPrev.m[4 + j]; B.Mp[2][j] = c->tpPrev.m[12 + j]; }
   memcpy(B.eyePrev, c->tpPrev.eye, sizeof B.eyePrev);
   B.tol2 = p.pos_tol * p.pos_tol;
   B.W = c->W; B.H = c->H;
   B.haveHist = c->tpHavePrev;
+  // an object motion is pending (sail_move_objects): the moved kernels, with the table uploaded ahead of them
+  B.motion = c->tpMotionDev; B.n = c->n; B.mc = c->tpMotionCap;
   c->tpResolved = false;
   // moment tracking: the same gather over Mhist, timed with the reproject pass
   const int nev = c->tpMom ? 4 : 3;
-  SailMomentReprojectArgs M;
-  memset(&M, 0, sizeof M);
-  M.Gcur = c->tpGcur; M.Gprev = c->tpGprev; M.Mhist = c->tpMhist; M.MR = c->tpMR;
-  memcpy(M.Mp, B.Mp, sizeof M.Mp);
-  memcpy(M.eyePrev, B.eyePrev, sizeof M.eyePrev);
-  M.tol2 = B.tol2; M.W = c->W; M.H = c->H; M.haveHist = B.haveHist;
-  // an object motion is pending (sail_move_objects): the motion kernels, with the table uploaded ahead of them
-  SailReprojectMovedArgs BM;
-  SailMomentReprojectMovedArgs MM;
-  BM.base = B; BM.motion = c->tpMotionDev; BM.n = c->n; BM.mc = c->tpMotionCap;
-  MM.base = M; MM.motion = c->tpMotionDev; MM.n = c->n; MM.mc = c->tpMotionCap;
-  hipEvent_t ev[4] = {};
-  for (int i = 0; i < nev; i++)
-    if (int rc = getEvent(c, &ev[i])) {
-      for (int j = 0; j < i; j++) c->evPool.push_back(ev[j]);
-      return rc;
-    }
+  SailReprojectArgs M = B;
+  M.hist = c->tpMhist; M.out = c->tpMR;
+  M.tileHit = nullptr; M.tileHist = nullptr;
+  PooledEvents ev(c, nev);
+  if (ev.rc) return ev.rc;
   hipError_t e = hipSuccess;
   if (moved && c->n > 0)
     e = hipMemcpyAsync(c->tpMotionDev, c->tpMotion.data(), sizeof(float4) * (size_t)c->n, hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = hipEventRecord(ev[0], c->stream);
   if (e == hipSuccess) e = sail_launch_gbuffer(A, c->stream);
   if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
-  if (e == hipSuccess) e = moved ? sail_launch_reproject_moved(BM, c->stream) : sail_launch_reproject(B, c->stream);
+  if (e == hipSuccess) e = sail_launch_reproject(B, moved, c->stream);
   if (e == hipSuccess) e = hipEventRecord(ev[2], c->stream);
   if (c->tpMom) {
-    if (e == hipSuccess) e = moved ? sail_launch_moment_reproject_moved(MM, c->stream) : sail_launch_moment_reproject(M, c->stream);
+    if (e == hipSuccess) e = sail_launch_moment_reproject(M, moved, c->stream);
     if (e == hipSuccess) e = hipEventRecord(ev[3], c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(c->tpMout, c->tpMR, np * 16, hipMemcpyDeviceToDevice, c->stream);
   }
@@ -2514,7 +2511,6 @@ int sail_temporal_begin(sail_ctx* c, const double mvp[16], const float eye[3], c
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   float ms[3] = {};
   for (int i = 0; i + 1 < nev && e == hipSuccess; i++) e = hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]);
-  for (int i = 0; i < nev; i++) c->evPool.push_back(ev[i]);
   ms[1] += ms[2];  // the moment reproject, when it ran
   std::vector<uint32_t> host(nt * 2);
   if (e == hipSuccess) e = hipMemcpy(host.data(), cnt, nt * 8, hipMemcpyDeviceToHost);
@@ -2561,11 +2557,10 @@ int sail_temporal_resolve(sail_ctx* c, const sail_temporal_params* params, float
   A.mix = c->accumMode == SAIL_ACCUM_MIX;
   A.kf = (float)c->k;
   A.cap = p.cap; A.display = p.display; A.gammaC = p.gamma_c;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (int rc = getEvent(c, &e0)) return rc;
-  if (int rc = getEvent(c, &e1)) { c->evPool.push_back(e0); return rc; }
+  PooledEvents ev(c, 2);
+  if (ev.rc) return ev.rc;
   float ms = 0.0f;
-  hipError_t e = hipEventRecord(e0, c->stream);
+  hipError_t e = hipEventRecord(ev[0], c->stream);
   if (e == hipSuccess) e = sail_launch_temporal_resolve(A, c->stream);
   if (c->tpMom && e == hipSuccess) {  // moment tracking: blended like the colour, timed with it
     SailMomentResolveArgs M;
@@ -2574,11 +2569,9 @@ int sail_temporal_resolve(sail_ctx* c, const sail_temporal_params* params, float
     M.W = c->W; M.H = c->H; M.mix = A.mix; M.kf = A.kf; M.cap = A.cap;
     e = sail_launch_moment_resolve(M, c->stream);
   }
-  if (e == hipSuccess) e = hipEventRecord(e1, c->stream);
+  if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-  c->evPool.push_back(e0);
-  c->evPool.push_back(e1);
+  if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
   std::vector<uint32_t> host(nt * 2);
   if (e == hipSuccess) e = hipMemcpy(host.data(), cnt + nt, nt * 8, hipMemcpyDeviceToHost);
   if (e == hipSuccess && out_rgba) e = hipMemcpy(out_rgba, c->tpOut, np * 16, hipMemcpyDeviceToHost);

@@ -7,7 +7,9 @@
 // from the two half buffers the noise estimate already keeps (S, the accumulator shown, and P, the mark), and steers the
 // luminance edge stop per pixel; the normal and position AOVs stop the other edges. The formula and its f32 operation
 // order are part of the C ABI (include/sail_hip.h, sail_denoise). Weights are rational, not exp(): every operation is an
-// IEEE one, so a numpy float32 restatement gives the same bits (tests/test_gpu_denoise.py).
+// IEEE one, so a numpy float32 restatement gives the same bits (tests/atrous_ref.py, tests/test_gpu_denoise.py). The
+// shown mean, the 3x3 prefilter, the display transform and the per-tile count are sail_post.h's, shared with the temporal
+// kernels (sail_temporal.hip, sail_tfilter.hip).
 //
 // MI355X design:
 //  * prepare: one 256-thread workgroup per 16x16 tile, one lane per pixel; the raw variance of the tile and a one-texel
@@ -32,15 +34,12 @@
 // run-time kernel's cache key. Built with the library's flags (no contraction, no fast math: `/` is the IEEE divide).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "sail_math.h"
+#include "sail_post.h"
 #include "sail_denoise.h"
 
 namespace {
 
 constexpr int kDnT = 20;  // a-trous LDS tile: 16 + 2 * 2 taps, rows packed
-
-__device__ __forceinline__ bool dnFinite(float x) { return __builtin_fabsf(x) <= 3.402823466e38f; }
-__device__ __forceinline__ float dnLum(float r, float g, float b) { return ((r + g) + b) / 3.0f; }
 
 // variance of the mean's luminance from the two halves (include/sail_hip.h): every operation rounds to f32, in this order
 __device__ __forceinline__ float dnRawVariance(const float4 s, const float4 p, int mix, float kf, float hf) {
@@ -55,27 +54,18 @@ __device__ __forceinline__ float dnRawVariance(const float4 s, const float4 p, i
     ar = p.x / h; ag = p.y / h; ab = p.z / h;
     br = (s.x - p.x) / dn; bg = (s.y - p.y) / dn; bb = (s.z - p.z) / dn;
   }
-  const float dl = dnLum(ar, ag, ab) - dnLum(br, bg, bb);
+  const float dl = sp::lum(ar, ag, ab) - sp::lum(br, bg, bb);
   return (dl * dl) * ((h * dn) / (n * n));
 }
-
-// the filter kernel's pointwise display transforms (sail_filter_kernel kinds 0..2)
-__device__ __forceinline__ float dnDisplay(float c, int kind, float gammaC) {
-  if (kind == 0) return c;
-  if (kind == 1) return sm::powf_(c, sm::rcp_rn(gammaC));
-  const float xx = sm::fmax_(0.0f, c - 0.004f);
-  return sm::fdiv(xx * (6.2f * xx + 0.5f), xx * (6.2f * xx + 1.7f) + 0.06f);
-}
-__device__ __forceinline__ uint32_t dnQuant(float o) { return (uint32_t)(uint8_t)(int)(sm::clamp_(o, 0.0f, 1.0f) * 255.0f + 0.5f); }
 
 }  // namespace
 
 extern "C" __global__ void __launch_bounds__(256) sail_denoise_prepare_kernel(SailDenoisePrepareArgs A) {
-  __shared__ float sV[18 * 18];
-  __shared__ uint32_t sBad[4];
+  __shared__ float sV[sp::kVarT * sp::kVarT];
+  __shared__ uint32_t sBad[1][4];
   const int x0 = (int)blockIdx.x * 16 - 1, y0 = (int)blockIdx.y * 16 - 1;
-  for (int t = threadIdx.x; t < 18 * 18; t += 256) {
-    const int ly = t / 18, lx = t - ly * 18;
+  for (int t = threadIdx.x; t < sp::kVarT * sp::kVarT; t += 256) {
+    const int ly = t / sp::kVarT, lx = t - ly * sp::kVarT;
     const int qx = x0 + lx, qy = y0 + ly;
     float v = __builtin_nanf("");  // outside the frame: skipped by the prefilter
     if (qx >= 0 && qx < A.W && qy >= 0 && qy < A.H) {
@@ -91,33 +81,15 @@ extern "C" __global__ void __launch_bounds__(256) sail_denoise_prepare_kernel(Sa
   if (x < A.W && y < A.H) {
     const size_t pix = (size_t)y * A.W + x;
     const float4 s = A.S[pix];
-    float cr, cg, cb;
-    if (A.mix) { cr = s.x; cg = s.y; cb = s.z; }
-    else if (s.w > 0.0f) { cr = s.x / s.w; cg = s.y / s.w; cb = s.z / s.w; }
-    else { cr = 0.0f; cg = 0.0f; cb = 0.0f; }
-    bad = !(dnFinite(cr) && dnFinite(cg) && dnFinite(cb));
-    float acc = 0.0f, wsum = 0.0f;
-#pragma unroll
-    for (int dy = -1; dy <= 1; dy++) {
-#pragma unroll
-      for (int dx = -1; dx <= 1; dx++) {
-        const int m = (dy < 0 ? -dy : dy) + (dx < 0 ? -dx : dx);
-        const float g = m == 0 ? 0.25f : (m == 1 ? 0.125f : 0.0625f);
-        const float vq = sV[(ly + 1 + dy) * 18 + (lx + 1 + dx)];
-        if (dnFinite(vq)) { acc += g * vq; wsum += g; }
-      }
-    }
-    const float v = wsum > 0.0f ? acc / wsum : 0.0f;
+    const sp::Rgb c = sp::shownMean(s, A.mix, s.w);
+    bad = !(sp::finite(c.r) && sp::finite(c.g) && sp::finite(c.b));
+    const float v = sp::prefilter(sV, lx, ly);
     const float4 nn = A.N[pix], xp = A.X[pix];
-    A.cv[pix] = make_float4(cr, cg, cb, v);
+    A.cv[pix] = make_float4(c.r, c.g, c.b, v);
     A.g0[pix] = make_float4(2.0f * nn.x - 1.0f, 2.0f * nn.y - 1.0f, 2.0f * nn.z - 1.0f, xp.x);
     A.g1[pix] = make_float2(xp.y, xp.z);
   }
-  const uint32_t cnt = (uint32_t)__popcll(__ballot(bad));
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) sBad[wave] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) A.tileBad[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = (sBad[0] + sBad[1]) + (sBad[2] + sBad[3]);
+  sp::tileCounts<1>({sp::waveCount(bad)}, sBad, {A.tileBad});
 }
 
 extern "C" __global__ void __launch_bounds__(256) sail_denoise_atrous_kernel(SailDenoiseAtrousArgs A) {
@@ -149,7 +121,7 @@ extern "C" __global__ void __launch_bounds__(256) sail_denoise_atrous_kernel(Sai
   const float4 gp = sG0[(lj + 2) * kDnT + (li + 2)];
   const float2 hp = sG1[(lj + 2) * kDnT + (li + 2)];
   const float den = A.sl2 * cp.w + 1e-8f;
-  const float lp = dnLum(cp.x, cp.y, cp.z);
+  const float lp = sp::lum(cp.x, cp.y, cp.z);
   float ar = 0.0f, ag = 0.0f, ab = 0.0f, vacc = 0.0f, wsum = 0.0f;
 #pragma unroll
   for (int dy = -2; dy <= 2; dy++) {
@@ -173,11 +145,11 @@ extern "C" __global__ void __launch_bounds__(256) sail_denoise_atrous_kernel(Sai
         const float tx = gp.w - gq.w, ty = hp.x - hq.x, tz = hp.y - hq.y;
         const float dx2 = (tx * tx + ty * ty) + tz * tz;
         const float wx = sm::rcp_rn(1.0f + dx2 / A.sxs);
-        const float dq = lp - dnLum(cq.x, cq.y, cq.z);
+        const float dq = lp - sp::lum(cq.x, cq.y, cq.z);
         const float wl = sm::rcp_rn(1.0f + (dq * dq) / den);
         w = ((kw * d) * wx) * wl;
       }
-      if (w > 0.0f && dnFinite(cq.x) && dnFinite(cq.y) && dnFinite(cq.z) && dnFinite(cq.w)) {
+      if (w > 0.0f && sp::finite(cq.x) && sp::finite(cq.y) && sp::finite(cq.z) && sp::finite(cq.w)) {
         ar += w * cq.x; ag += w * cq.y; ab += w * cq.z;
         vacc += (w * w) * cq.w;
         wsum += w;
@@ -190,9 +162,7 @@ extern "C" __global__ void __launch_bounds__(256) sail_denoise_atrous_kernel(Sai
   if (!A.last) { A.dst[pix] = o; return; }
   if (A.dst) A.dst[pix] = make_float4(o.x, o.y, o.z, 1.0f);
   if (A.outVar) A.outVar[pix] = o.w;
-  if (A.out8)
-    A.out8[pix] = dnQuant(dnDisplay(o.x, A.display, A.gammaC)) | (dnQuant(dnDisplay(o.y, A.display, A.gammaC)) << 8) |
-                  (dnQuant(dnDisplay(o.z, A.display, A.gammaC)) << 16) | 0xff000000u;
+  if (A.out8) A.out8[pix] = sp::rgba8(o.x, o.y, o.z, A.display, A.gammaC);
 }
 
 hipError_t sail_launch_denoise_prepare(const SailDenoisePrepareArgs& A, hipStream_t s) {

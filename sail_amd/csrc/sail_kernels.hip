@@ -2,10 +2,11 @@
 // gfx950 code object (tests/test_jit_compile.py disassembles "the" code object of the library). Each kernel file stays
 // its own source and compiles on its own too (the study and variant builds under tools/ do that); sail_trace.hip is not
 // touched by what is added here: its text is embedded in the library and hashed into every run-time kernel's cache key.
-// sail_noise.hip, sail_denoise.hip and sail_tfilter.hip come first: they define no macro (the latter two include
-// sail_math.h, which sail_trace.hip includes itself), so the trace kernels compile exactly as they do alone.
-// sail_temporal.hip comes last: its G-buffer pass calls sail_trace.hip's mkRay, primT and constRow, and nothing it declares
-// is seen by the trace kernels.
+// sail_post.h (what the post-processing kernels share), sail_noise.hip, sail_denoise.hip and sail_tfilter.hip come first:
+// they define no macro (sail_post.h includes sail_math.h, which sail_trace.hip includes itself), so the trace kernels
+// compile exactly as they do alone. sail_temporal.hip comes last: its G-buffer pass calls sail_trace.hip's mkRay, primT and
+// constRow, and nothing it declares is seen by the trace kernels.
+#include "sail_post.h"
 #include "sail_noise.hip"
 #include "sail_denoise.hip"
 #include "sail_tfilter.hip"

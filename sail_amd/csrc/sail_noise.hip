@@ -13,11 +13,13 @@
 //  * lanes outside the frame (ragged tiles) load nothing and add +0;
 //  * with remark each lane stores the float4 of S it just read into P: a doubling schedule costs one pass per look;
 //  * plain vector stores only.
-// Lives in its own file: the text of sail_trace.hip is embedded in the library and hashed into every run-time kernel's
-// cache key. Built with the library's flags (no contraction, no fast math: `/` and sqrt are the IEEE ones, as
+// The finite test and the wave count are sail_post.h's; the reduction stays here, since the sum and the count share its
+// one barrier. Lives in its own file: the text of sail_trace.hip is embedded in the library and hashed into every
+// run-time kernel's cache key. Built with the library's flags (no contraction, no fast math: `/` and sqrt are the IEEE ones, as
 // sail_math_probe functions 7 and 8 show on the device).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "sail_post.h"
 #include "sail_noise.h"
 
 namespace {
@@ -53,14 +55,14 @@ extern "C" __global__ void __launch_bounds__(256) sail_noise_kernel(SailNoiseArg
     const size_t pix = (size_t)y * A.W + x;
     const float4 s = A.S[pix], p = A.P[pix];
     e = noiseError(s, p, A.mix, A.kf, A.hf);
-    if (!(__builtin_fabsf(e) <= 3.402823466e38f)) { bad = true; e = 0.0f; }  // NaN or Inf: counted, adds nothing
+    if (!sp::finite(e)) { bad = true; e = 0.0f; }  // NaN or Inf: counted, adds nothing
     if (A.pixErr) A.pixErr[pix] = e;
     if (A.remark) A.P[pix] = s;
   }
   // within the wave: a butterfly, every lane ends with the same sum; the count is a ballot
   float v = e;
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  const uint32_t cnt = (uint32_t)__popcll(__ballot(bad));
+  const uint32_t cnt = sp::waveCount(bad);
   // across the four waves through LDS, in a fixed order
   __shared__ float sSum[4];
   __shared__ uint32_t sBad[4];

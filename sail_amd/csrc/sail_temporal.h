@@ -16,23 +16,22 @@ struct SailGbufferArgs {
   float* t;               // out, may be NULL: the hit distance, 1e5 on a miss
 };
 
+// The four reproject kernels: sail_reproject_kernel and sail_reproject_moved_kernel over the colour history (hist = Hist,
+// out = R), sail_moment_reproject_kernel and sail_moment_reproject_moved_kernel over the moments (hist = Mhist, out = MR,
+// no counts). The gather itself is sail_post.h's.
 struct SailReprojectArgs {
   const float4* Gcur;
   const float4* Gprev;
-  const float4* Hist;     // (rgb mean, effective sample count)
-  float4* R;              // out: the history seen from the new view, or 0
-  uint32_t* tileHit;      // out, per 16x16 tile: pixels of the new view that hit the scene
-  uint32_t* tileHist;     // out, per tile: pixels that found a history
+  const float4* hist;     // the previous view's (rgb mean, effective sample count), or its (mu1, mu2, mm, 0)
+  float4* out;            // out: hist seen from the new view, or 0
+  uint32_t* tileHit;      // out, per 16x16 tile: pixels of the new view that hit the scene (NULL for the moments)
+  uint32_t* tileHist;     // out, per tile: pixels that found a history (NULL for the moments)
   float Mp[3][4];         // rows 0, 1 and 3 of the previous view's P*MV in f32
   float eyePrev[3];
   float tol2;             // pos_tol * pos_tol
   int W, H;
-  int haveHist;           // 0: no committed history, R = 0 everywhere (Gprev and Hist are not read)
-};
-
-// sail_reproject_moved_kernel: the reproject pass of a begin with an object motion pending (sail_move_objects)
-struct SailReprojectMovedArgs {
-  SailReprojectArgs base;
+  int haveHist;           // 0: no committed history, out = 0 everywhere (Gprev and hist are not read)
+  // the moved kernels only, after sail_move_objects; the plain ones read none of these
   const float4* motion;   // n rows of (d.xyz, 0): each row's translation since G_prev, read per lane by G_cur's id
   int n;
   float mc;               // the count of a history that crosses the move is at most this (+inf: no cap)

@@ -1,29 +1,29 @@
-// sail_temporal.hip — camera-motion reprojection on the MI355X (gfx950): sail_gbuffer_kernel, sail_reproject_kernel and
-// sail_temporal_resolve_kernel.
+// sail_temporal.hip — camera-motion reprojection on the MI355X (gfx950): sail_gbuffer_kernel, sail_reproject_kernel,
+// sail_reproject_moved_kernel and sail_temporal_resolve_kernel.
 //
 // No reference counterpart (the reference throws the picture away on every camera move, src/core/renderer.js:57-60).
-// This is the temporal part of SVGF (Schied et al. 2017) for a still scene seen from a moving camera: a G-buffer pass
-// gives every pixel of a view the world position and the object row of its first hit, the reproject pass looks each
-// pixel's position up in the previous view's history with a bilinear gather that only accepts taps of the same object
-// at the same place, and the resolve pass blends that history, counted as at most `cap` samples, with the mean of the
-// samples rendered since. The formulas and their f32 operation order are part of the C ABI (include/sail_hip.h,
+// This is the temporal part of SVGF (Schied et al. 2017): a G-buffer pass gives every pixel of a view the world position
+// and the object row of its first hit, the reproject pass looks each pixel's position up in the previous view's colour
+// history, and the resolve pass blends that history, counted as at most `cap` samples, with the mean of the samples
+// rendered since. The formulas and their f32 operation order are part of the C ABI (include/sail_hip.h,
 // sail_temporal_begin / sail_temporal_resolve); every operation is an IEEE one, so a numpy float32 restatement gives the
-// same bits (tests/test_gpu_temporal.py).
+// same bits (tests/temporal_ref.py, tests/test_gpu_temporal.py). The gather, the shown mean, the display transform and
+// the per-tile counts are sail_post.h's, shared with the moment kernels (sail_tfilter.hip) and the denoiser.
 //
 // MI355X design ("sail_gbuffer_kernel, sail_reproject_kernel, sail_temporal_resolve_kernel"):
-//  * all three: one 256-thread workgroup per 16x16 tile, one lane per pixel, each wave a 16x4 strip (the filter and
+//  * all four: one 256-thread workgroup per 16x16 tile, one lane per pixel, each wave a 16x4 strip (the filter and
 //    noise kernels' shape): float4 loads and stores in 256-byte runs per row;
 //  * G-buffer: the pixel's ray is the trace kernels' for a sample of zero jitter (same corner interpolation, mkRay),
 //    the sweep is sail_pick_kernel's: primT over all rows in order, a hit on a strict `<`; the row index is
 //    wave-uniform, so the rows arrive through the scalar cache (constRow). One float4 store per pixel;
-//  * reproject: a data-dependent gather of up to four float4 pairs (G_prev, Hist) per pixel, 16-byte loads, straight
-//    from L2 / HBM: neighbouring pixels of the new view land on neighbouring texels of the old one, so a wave's taps
-//    share cache lines. Taps outside the frame are never loaded. No LDS staging;
+//  * reproject: the tap of sp::gather reads Hist and accepts a texel with a count and a finite colour; up to four float4
+//    pairs (G_prev, Hist) per pixel, 16-byte loads, straight from L2 / HBM: neighbouring pixels of the new view land on
+//    neighbouring texels of the old one, so a wave's taps share cache lines. No LDS staging;
 //  * reproject with an object motion pending (sail_move_objects; sail_reproject_moved_kernel, DESIGN.md §5,
-//    "sail_reproject_moved_kernel"): the same body, which first takes the pixel's row translation from a table of n float4
-//    (one more 16-byte load by the id of G_cur; the table stays in L1/L2) and looks up X - d instead of X;
+//    "sail_reproject_moved_kernel"): the same body as a second instance, MOVED, which looks up X - D[id] and caps the count
+//    that crosses the move. An entry point of its own, not a run-time switch: the plain kernel pays no table load;
 //  * resolve: pointwise, one float4 of S and of R in, one float4 and one RGBA8 word out;
-//  * the counts are wave ballots, summed across the four waves through LDS in a fixed order and per tile on the host;
+//  * the counts are wave ballots, one barrier each (sp::tileCounts), summed per tile on the host;
 //  * lanes outside ragged tiles load nothing and store nothing;
 //  * plain vector stores only, no atomics: equal data give equal bits.
 // Included from sail_kernels.hip AFTER sail_trace.hip (it calls that file's mkRay, primT and constRow) and defines no
@@ -31,32 +31,7 @@
 // with the library's flags (no contraction, no fast math: `/` is the IEEE divide).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "sail_math.h"
-#include "sail_temporal.h"
-
-namespace {
-
-__device__ __forceinline__ bool tpFinite(float x) { return __builtin_fabsf(x) <= 3.402823466e38f; }
-__device__ __forceinline__ float tpMin(float a, float b) { return a < b ? a : b; }
-
-// the filter kernel's pointwise display transforms (sail_filter_kernel kinds 0..2) and its quantisation
-__device__ __forceinline__ float tpDisplay(float c, int kind, float gammaC) {
-  if (kind == 0) return c;
-  if (kind == 1) return sm::powf_(c, sm::rcp_rn(gammaC));
-  const float xx = sm::fmax_(0.0f, c - 0.004f);
-  return sm::fdiv(xx * (6.2f * xx + 0.5f), xx * (6.2f * xx + 1.7f) + 0.06f);
-}
-__device__ __forceinline__ uint32_t tpQuant(float o) { return (uint32_t)(uint8_t)(int)(sm::clamp_(o, 0.0f, 1.0f) * 255.0f + 0.5f); }
-
-// a tile's count from its four waves' ballots, in a fixed order; every thread of the workgroup calls it
-__device__ __forceinline__ void tpTileCount(bool flag, uint32_t* slots, uint32_t* out) {
-  const uint32_t cnt = (uint32_t)__popcll(__ballot(flag));
-  if ((threadIdx.x & 63) == 0) slots[threadIdx.x >> 6] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) out[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = (slots[0] + slots[1]) + (slots[2] + slots[3]);
-}
-
-}  // namespace
+#include "sail_post.h"
 
 extern "C" __global__ void __launch_bounds__(256) sail_gbuffer_kernel(SailGbufferArgs A) {
   const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
@@ -91,12 +66,12 @@ extern "C" __global__ void __launch_bounds__(256) sail_gbuffer_kernel(SailGbuffe
   if (A.t) A.t[pix] = best;
 }
 
-// The reproject pass. MOVED = false is sail_reproject_kernel as it always was: motion, n and mc are not read. MOVED = true is the
-// pass after sail_move_objects: the point the pixel shows sat at Xp = X - D[id] in the previous frame, and the count that
-// crosses the move is at most mc.
+// The reproject pass over the colour history: sp::gather's taps that hold a count and a finite colour. MOVED = false is
+// sail_reproject_kernel (motion, n and mc are not read); MOVED = true is the pass after sail_move_objects, where the count
+// that crosses the move is at most mc.
 template <bool MOVED>
-__device__ __forceinline__ void tpReproject(const SailReprojectArgs& A, const float4* motion, int n, float mc) {
-  __shared__ uint32_t sHit[4], sHist[4];
+__device__ __forceinline__ void tpReproject(const SailReprojectArgs& A) {
+  __shared__ uint32_t sHit[1][4], sHist[1][4];
   const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
   bool hit = false, found = false;
   if (x < A.W && y < A.H) {
@@ -105,79 +80,40 @@ __device__ __forceinline__ void tpReproject(const SailReprojectArgs& A, const fl
     float4 out = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     hit = !(g.w < 0.0f);
     if (hit && A.haveHist) {
-      float px = g.x, py = g.y, pz = g.z;
-      if (MOVED) {
-        const int id = (int)g.w;
-        if ((uint32_t)id < (uint32_t)n) {  // G_cur comes from the rows the table was sized for; a row beyond it is never loaded
-          const float4 d = motion[id];
-          px = g.x - d.x; py = g.y - d.y; pz = g.z - d.z;
-        }
-      }
-      const float c0 = ((A.Mp[0][0] * px + A.Mp[0][1] * py) + A.Mp[0][2] * pz) + A.Mp[0][3];
-      const float c1 = ((A.Mp[1][0] * px + A.Mp[1][1] * py) + A.Mp[1][2] * pz) + A.Mp[1][3];
-      const float c3 = ((A.Mp[2][0] * px + A.Mp[2][1] * py) + A.Mp[2][2] * pz) + A.Mp[2][3];
-      if (c3 > 0.0f) {
-        const float u = ((c0 / c3) * 0.5f + 0.5f) * (float)A.W - 0.5f;
-        const float v = ((c1 / c3) * 0.5f + 0.5f) * (float)A.H - 0.5f;
-        if (tpFinite(u) && tpFinite(v)) {
-          const float iu = __builtin_floorf(u), iv = __builtin_floorf(v);
-          const float fu = u - iu, fv = v - iv;
-          const float rx = px - A.eyePrev[0], ry = py - A.eyePrev[1], rz = pz - A.eyePrev[2];
-          const float r2 = (rx * rx + ry * ry) + rz * rz;
-          const float lim = A.tol2 * r2;
-          float ar = 0.0f, ag = 0.0f, ab = 0.0f, wsum = 0.0f, m = __builtin_inff();
-#pragma unroll
-          for (int b = 0; b < 2; b++) {
-#pragma unroll
-            for (int a = 0; a < 2; a++) {
-              // in floats: u and v may lie far outside the int range
-              const float qxf = iu + (float)a, qyf = iv + (float)b;
-              if (!(qxf >= 0.0f && qxf <= (float)(A.W - 1) && qyf >= 0.0f && qyf <= (float)(A.H - 1))) continue;
-              const float w = (a ? fu : 1.0f - fu) * (b ? fv : 1.0f - fv);
-              if (!(w > 0.0f)) continue;
-              const size_t q = (size_t)(int)qyf * A.W + (int)qxf;
-              const float4 gq = A.Gprev[q];
-              if (!(gq.w == g.w)) continue;
-              const float ex = px - gq.x, ey = py - gq.y, ez = pz - gq.z;
-              if (!((ex * ex + ey * ey) + ez * ez <= lim)) continue;
-              const float4 h = A.Hist[q];
-              if (!(h.w > 0.0f) || !(tpFinite(h.x) && tpFinite(h.y) && tpFinite(h.z))) continue;
-              ar += w * h.x; ag += w * h.y; ab += w * h.z;
-              wsum += w;
-              m = tpMin(m, h.w);
-            }
-          }
-          if (wsum > 0.0f) { out = make_float4(ar / wsum, ag / wsum, ab / wsum, MOVED ? tpMin(m, mc) : m); found = true; }
-        }
-      }
+      float ar = 0.0f, ag = 0.0f, ab = 0.0f, wsum = 0.0f, m = __builtin_inff();
+      sp::gather<MOVED>(
+          A, g,
+          [&](float w, size_t q) {
+            const float4 h = A.hist[q];  // one 16-byte load
+            if (!(h.w > 0.0f) || !(sp::finite(h.x) && sp::finite(h.y) && sp::finite(h.z))) return;
+            ar += w * h.x; ag += w * h.y; ab += w * h.z;
+            wsum += w;
+            m = sp::min_(m, h.w);
+          },
+          [&] {
+            if (wsum > 0.0f) { out = make_float4(ar / wsum, ag / wsum, ab / wsum, MOVED ? sp::min_(m, A.mc) : m); found = true; }
+          });
     }
-    A.R[pix] = out;
+    A.out[pix] = out;
   }
-  tpTileCount(hit, sHit, A.tileHit);
-  tpTileCount(found, sHist, A.tileHist);
+  sp::tileCounts<1>({sp::waveCount(hit)}, sHit, {A.tileHit});
+  sp::tileCounts<1>({sp::waveCount(found)}, sHist, {A.tileHist});
 }
 
-extern "C" __global__ void __launch_bounds__(256) sail_reproject_kernel(SailReprojectArgs A) {
-  tpReproject<false>(A, nullptr, 0, 0.0f);
-}
+extern "C" __global__ void __launch_bounds__(256) sail_reproject_kernel(SailReprojectArgs A) { tpReproject<false>(A); }
 
-extern "C" __global__ void __launch_bounds__(256) sail_reproject_moved_kernel(SailReprojectMovedArgs A) {
-  tpReproject<true>(A.base, A.motion, A.n, A.mc);
-}
+extern "C" __global__ void __launch_bounds__(256) sail_reproject_moved_kernel(SailReprojectArgs A) { tpReproject<true>(A); }
 
 extern "C" __global__ void __launch_bounds__(256) sail_temporal_resolve_kernel(SailResolveArgs A) {
-  __shared__ uint32_t sHist[4], sBad[4];
+  __shared__ uint32_t sHist[1][4], sBad[1][4];
   const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
   bool hist = false, bad = false;
   if (x < A.W && y < A.H) {
     const size_t pix = (size_t)y * A.W + x;
     const float4 s = A.S[pix], r = A.R[pix];
-    const float n = A.mix ? A.kf : s.w;
-    float cr, cg, cb;
-    if (A.mix) { cr = s.x; cg = s.y; cb = s.z; }
-    else if (n > 0.0f) { cr = s.x / n; cg = s.y / n; cb = s.z / n; }
-    else { cr = 0.0f; cg = 0.0f; cb = 0.0f; }
-    const bool fin = tpFinite(cr) && tpFinite(cg) && tpFinite(cb);
+    const float n = sp::shownCount(s, A.mix, A.kf);
+    const sp::Rgb c = sp::shownMean(s, A.mix, n);
+    const bool fin = sp::finite(c.r) && sp::finite(c.g) && sp::finite(c.b);
     bad = !fin;
     const float m = r.w;
     hist = m > 0.0f;
@@ -185,19 +121,17 @@ extern "C" __global__ void __launch_bounds__(256) sail_temporal_resolve_kernel(S
     float4 o;
     if (hist && cur) {
       const float ws = m + n;
-      o = make_float4(((m * r.x) + (n * cr)) / ws, ((m * r.y) + (n * cg)) / ws, ((m * r.z) + (n * cb)) / ws, tpMin(ws, A.cap));
+      o = make_float4(((m * r.x) + (n * c.r)) / ws, ((m * r.y) + (n * c.g)) / ws, ((m * r.z) + (n * c.b)) / ws, sp::min_(ws, A.cap));
     } else if (hist) {
       o = make_float4(r.x, r.y, r.z, m);
     } else {
-      o = make_float4(cr, cg, cb, tpMin(n, A.cap));
+      o = make_float4(c.r, c.g, c.b, sp::min_(n, A.cap));
     }
     A.Out[pix] = o;
-    if (A.out8)
-      A.out8[pix] = tpQuant(tpDisplay(o.x, A.display, A.gammaC)) | (tpQuant(tpDisplay(o.y, A.display, A.gammaC)) << 8) |
-                    (tpQuant(tpDisplay(o.z, A.display, A.gammaC)) << 16) | 0xff000000u;
+    if (A.out8) A.out8[pix] = sp::rgba8(o.x, o.y, o.z, A.display, A.gammaC);
   }
-  tpTileCount(hist, sHist, A.tileHist);
-  tpTileCount(bad, sBad, A.tileBad);
+  sp::tileCounts<1>({sp::waveCount(hist)}, sHist, {A.tileHist});
+  sp::tileCounts<1>({sp::waveCount(bad)}, sBad, {A.tileBad});
 }
 
 hipError_t sail_launch_gbuffer(const SailGbufferArgs& A, hipStream_t s) {
@@ -205,13 +139,9 @@ hipError_t sail_launch_gbuffer(const SailGbufferArgs& A, hipStream_t s) {
   return hipGetLastError();
 }
 
-hipError_t sail_launch_reproject(const SailReprojectArgs& A, hipStream_t s) {
-  hipLaunchKernelGGL(sail_reproject_kernel, dim3((A.W + 15) / 16, (A.H + 15) / 16), dim3(256), 0, s, A);
-  return hipGetLastError();
-}
-
-hipError_t sail_launch_reproject_moved(const SailReprojectMovedArgs& A, hipStream_t s) {
-  hipLaunchKernelGGL(sail_reproject_moved_kernel, dim3((A.base.W + 15) / 16, (A.base.H + 15) / 16), dim3(256), 0, s, A);
+hipError_t sail_launch_reproject(const SailReprojectArgs& A, bool moved, hipStream_t s) {
+  hipLaunchKernelGGL(moved ? sail_reproject_moved_kernel : sail_reproject_kernel, dim3((A.W + 15) / 16, (A.H + 15) / 16), dim3(256),
+                     0, s, A);
   return hipGetLastError();
 }
 
@@ -219,3 +149,4 @@ hipError_t sail_launch_temporal_resolve(const SailResolveArgs& A, hipStream_t s)
   hipLaunchKernelGGL(sail_temporal_resolve_kernel, dim3((A.W + 15) / 16, (A.H + 15) / 16), dim3(256), 0, s, A);
   return hipGetLastError();
 }
+

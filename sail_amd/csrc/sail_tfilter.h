@@ -3,27 +3,6 @@
 #pragma once
 #include <stdint.h>
 
-struct SailMomentReprojectArgs {
-  const float4* Gcur;
-  const float4* Gprev;
-  const float4* Mhist;    // (mu1, mu2, mm, 0) of the previous view
-  float4* MR;             // out: Mhist seen from the new view, or 0
-  float Mp[3][4];         // rows 0, 1 and 3 of the previous view's P*MV in f32 (as SailReprojectArgs)
-  float eyePrev[3];
-  float tol2;             // pos_tol * pos_tol
-  int W, H;
-  int haveHist;           // 0: no committed history, MR = 0 everywhere (Gprev and Mhist are not read)
-};
-
-// sail_moment_reproject_moved_kernel: the moment reproject of a begin with an object motion pending (motion, n and mc as
-// SailReprojectMovedArgs)
-struct SailMomentReprojectMovedArgs {
-  SailMomentReprojectArgs base;
-  const float4* motion;
-  int n;
-  float mc;
-};
-
 struct SailMomentResolveArgs {
   const float4* S;        // the accumulator the context shows
   const float4* MR;

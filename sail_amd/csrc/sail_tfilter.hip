@@ -8,12 +8,13 @@
 // prepare pass writes exactly the (cv, g0, g1) maps sail_denoise_atrous_kernel reads, so the a-trous passes run unchanged
 // over the resolved picture `Out`. The formulas and their f32 operation order are part of the C ABI (include/sail_hip.h,
 // sail_temporal_moments / sail_temporal_filter); every operation is an IEEE one, so a numpy float32 restatement gives the
-// same bits (tests/temporal_filter_ref.py, tests/test_gpu_temporal_filter.py).
+// same bits (tests/temporal_filter_ref.py, tests/test_gpu_temporal_filter.py). The gather, the shown mean, the 3x3
+// prefilter and the per-tile counts are sail_post.h's, shared with sail_temporal.hip and sail_denoise.hip.
 //
 // MI355X design ("sail_tfilter_prepare_kernel"):
 //  * all three: one 256-thread workgroup per 16x16 tile, one lane per pixel, each wave a 16x4 strip; float4 loads and stores;
-//  * moment reproject: sail_reproject_kernel's gather with Mhist in the place of Hist (Hist is not read), no counts;
-//    sail_moment_reproject_moved_kernel is the same body after sail_move_objects, as sail_reproject_moved_kernel;
+//  * moment reproject: the tap of sp::gather reads Mhist and accepts a texel with a count (.z) and finite moments; no
+//    per-tile counts. sail_moment_reproject_moved_kernel is the MOVED instance, as sail_reproject_moved_kernel;
 //  * moment resolve: pointwise, one float4 of S and of MR in, one float4 out;
 //  * prepare, three phases with a barrier between them:
 //      1. the tile and a four-texel halo (24x24) are staged in LDS as two float4 per texel: (decoded normal, luminance)
@@ -28,24 +29,19 @@
 //    96 dwords); phase 2 walks the 18x18 grid row-major, so the 16 lanes of a ds_read_b128 group read consecutive texels
 //    except where a row ends;
 //  * texels outside the frame are never loaded; lanes outside ragged tiles store nothing;
-//  * the counts are wave ballots, summed across the four waves through LDS in a fixed order and per tile on the host;
+//  * the prepare pass's two counts are wave ballots behind one barrier (sp::tileCounts), summed per tile on the host;
 //  * plain vector stores only, no atomics: equal data give equal bits.
 // Lives in its own file and defines no macro: the text of sail_trace.hip is embedded in the library and hashed into every
 // run-time kernel's cache key. Built with the library's flags (no contraction, no fast math: `/` is the IEEE divide).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "sail_math.h"
+#include "sail_post.h"
 #include "sail_tfilter.h"
 
 namespace {
 
-constexpr int kTfS = 24;  // stage: 16 + 2 * (1 prefilter + 3 window) texels, rows packed
-constexpr int kTfV = 18;  // v0: 16 + 2 * 1
-
-__device__ __forceinline__ bool tfFinite(float x) { return __builtin_fabsf(x) <= 3.402823466e38f; }
-__device__ __forceinline__ float tfMin(float a, float b) { return a < b ? a : b; }
-__device__ __forceinline__ float tfMax(float a, float b) { return a > b ? a : b; }
-__device__ __forceinline__ float tfLum(float r, float g, float b) { return ((r + g) + b) / 3.0f; }
+constexpr int kTfS = 24;        // stage: 16 + 2 * (1 prefilter + 3 window) texels, rows packed
+constexpr int kTfV = sp::kVarT;  // v0: 16 + 2 * 1, the tile sp::prefilter reads
 
 // the 7x7 spatial variance of the luminance round stage texel (cx, cy), 3 <= cx, cy <= 20 (include/sail_hip.h)
 __device__ __forceinline__ float tfSpatial(const float4* sA, const float4* sB, int cx, int cy, float sx0) {
@@ -60,7 +56,7 @@ __device__ __forceinline__ float tfSpatial(const float4* sA, const float4* sB, i
       const float4 qa = sA[q];
       float w = 1.0f;
       if (dy != 0 || dx != 0) {
-        float d = tfMax((pa.x * qa.x + pa.y * qa.y) + pa.z * qa.z, 0.0f);
+        float d = sp::max_((pa.x * qa.x + pa.y * qa.y) + pa.z * qa.z, 0.0f);
         d = d * d; d = d * d; d = d * d; d = d * d; d = d * d; d = d * d;
         const float tx = pb.x - qb.x, ty = pb.y - qb.y, tz = pb.z - qb.z;
         const float dx2 = (tx * tx + ty * ty) + tz * tz;
@@ -76,100 +72,61 @@ __device__ __forceinline__ float tfSpatial(const float4* sA, const float4* sB, i
   }
   if (!(ws > 0.0f)) return 0.0f;
   const float m1 = a1 / ws;
-  return tfMax(a2 / ws - m1 * m1, 0.0f);
+  return sp::max_(a2 / ws - m1 * m1, 0.0f);
 }
 
 }  // namespace
 
-// The moment reproject pass. MOVED = false is sail_moment_reproject_kernel as it always was: motion, n and mc are not read.
-// MOVED = true follows sail_reproject_moved_kernel: the same Xp = X - D[id], and MR.z = min(m, mc).
+// The moment reproject pass: sail_temporal.hip's tpReproject over Mhist, with .z as the count, and no per-tile counts.
+// MOVED as there.
 template <bool MOVED>
-__device__ __forceinline__ void tfMomentReproject(const SailMomentReprojectArgs& A, const float4* motion, int n, float mc) {
+__device__ __forceinline__ void tfMomentReproject(const SailReprojectArgs& A) {
   const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
   if (x >= A.W || y >= A.H) return;
   const size_t pix = (size_t)y * A.W + x;
   const float4 g = A.Gcur[pix];
   float4 out = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   if (!(g.w < 0.0f) && A.haveHist) {
-    float px = g.x, py = g.y, pz = g.z;
-    if (MOVED) {
-      const int id = (int)g.w;
-      if ((uint32_t)id < (uint32_t)n) {  // G_cur comes from the rows the table was sized for; a row beyond it is never loaded
-        const float4 d = motion[id];
-        px = g.x - d.x; py = g.y - d.y; pz = g.z - d.z;
-      }
-    }
-    const float c0 = ((A.Mp[0][0] * px + A.Mp[0][1] * py) + A.Mp[0][2] * pz) + A.Mp[0][3];
-    const float c1 = ((A.Mp[1][0] * px + A.Mp[1][1] * py) + A.Mp[1][2] * pz) + A.Mp[1][3];
-    const float c3 = ((A.Mp[2][0] * px + A.Mp[2][1] * py) + A.Mp[2][2] * pz) + A.Mp[2][3];
-    if (c3 > 0.0f) {
-      const float u = ((c0 / c3) * 0.5f + 0.5f) * (float)A.W - 0.5f;
-      const float v = ((c1 / c3) * 0.5f + 0.5f) * (float)A.H - 0.5f;
-      if (tfFinite(u) && tfFinite(v)) {
-        const float iu = __builtin_floorf(u), iv = __builtin_floorf(v);
-        const float fu = u - iu, fv = v - iv;
-        const float rx = px - A.eyePrev[0], ry = py - A.eyePrev[1], rz = pz - A.eyePrev[2];
-        const float r2 = (rx * rx + ry * ry) + rz * rz;
-        const float lim = A.tol2 * r2;
-        float a1 = 0.0f, a2 = 0.0f, wsum = 0.0f, m = __builtin_inff();
-#pragma unroll
-        for (int b = 0; b < 2; b++) {
-#pragma unroll
-          for (int a = 0; a < 2; a++) {
-            // in floats: u and v may lie far outside the int range
-            const float qxf = iu + (float)a, qyf = iv + (float)b;
-            if (!(qxf >= 0.0f && qxf <= (float)(A.W - 1) && qyf >= 0.0f && qyf <= (float)(A.H - 1))) continue;
-            const float w = (a ? fu : 1.0f - fu) * (b ? fv : 1.0f - fv);
-            if (!(w > 0.0f)) continue;
-            const size_t q = (size_t)(int)qyf * A.W + (int)qxf;
-            const float4 gq = A.Gprev[q];
-            if (!(gq.w == g.w)) continue;
-            const float ex = px - gq.x, ey = py - gq.y, ez = pz - gq.z;
-            if (!((ex * ex + ey * ey) + ez * ez <= lim)) continue;
-            const float4 h = A.Mhist[q];
-            if (!(h.z > 0.0f) || !(tfFinite(h.x) && tfFinite(h.y))) continue;
-            a1 += w * h.x; a2 += w * h.y;
-            wsum += w;
-            m = tfMin(m, h.z);
-          }
-        }
-        if (wsum > 0.0f) out = make_float4(a1 / wsum, a2 / wsum, MOVED ? tfMin(m, mc) : m, 0.0f);
-      }
-    }
+    float a1 = 0.0f, a2 = 0.0f, wsum = 0.0f, m = __builtin_inff();
+    sp::gather<MOVED>(
+        A, g,
+        [&](float w, size_t q) {
+          const float4& h = A.hist[q];  // a reference: .z, .x and .y are loaded one by one, each where it is first tested
+          if (!(h.z > 0.0f) || !(sp::finite(h.x) && sp::finite(h.y))) return;
+          a1 += w * h.x; a2 += w * h.y;
+          wsum += w;
+          m = sp::min_(m, h.z);
+        },
+        [&] {
+          if (wsum > 0.0f) out = make_float4(a1 / wsum, a2 / wsum, MOVED ? sp::min_(m, A.mc) : m, 0.0f);
+        });
   }
-  A.MR[pix] = out;
+  A.out[pix] = out;
 }
 
-extern "C" __global__ void __launch_bounds__(256) sail_moment_reproject_kernel(SailMomentReprojectArgs A) {
-  tfMomentReproject<false>(A, nullptr, 0, 0.0f);
-}
+extern "C" __global__ void __launch_bounds__(256) sail_moment_reproject_kernel(SailReprojectArgs A) { tfMomentReproject<false>(A); }
 
-extern "C" __global__ void __launch_bounds__(256) sail_moment_reproject_moved_kernel(SailMomentReprojectMovedArgs A) {
-  tfMomentReproject<true>(A.base, A.motion, A.n, A.mc);
-}
+extern "C" __global__ void __launch_bounds__(256) sail_moment_reproject_moved_kernel(SailReprojectArgs A) { tfMomentReproject<true>(A); }
 
 extern "C" __global__ void __launch_bounds__(256) sail_moment_resolve_kernel(SailMomentResolveArgs A) {
   const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
   if (x >= A.W || y >= A.H) return;
   const size_t pix = (size_t)y * A.W + x;
   const float4 s = A.S[pix], r = A.MR[pix];
-  const float n = A.mix ? A.kf : s.w;
-  float cr, cg, cb;
-  if (A.mix) { cr = s.x; cg = s.y; cb = s.z; }
-  else if (n > 0.0f) { cr = s.x / n; cg = s.y / n; cb = s.z / n; }
-  else { cr = 0.0f; cg = 0.0f; cb = 0.0f; }
-  const float l = tfLum(cr, cg, cb);
-  const bool cur = n > 0.0f && tfFinite(cr) && tfFinite(cg) && tfFinite(cb);
+  const float n = sp::shownCount(s, A.mix, A.kf);
+  const sp::Rgb c = sp::shownMean(s, A.mix, n);
+  const float l = sp::lum(c.r, c.g, c.b);
+  const bool cur = n > 0.0f && sp::finite(c.r) && sp::finite(c.g) && sp::finite(c.b);
   const float mh = r.z;
   const bool hist = mh > 0.0f;
   float4 o = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   if (hist && cur) {
     const float ws = mh + n;
-    o = make_float4(((mh * r.x) + (n * l)) / ws, ((mh * r.y) + (n * (l * l))) / ws, tfMin(ws, A.cap), 0.0f);
+    o = make_float4(((mh * r.x) + (n * l)) / ws, ((mh * r.y) + (n * (l * l))) / ws, sp::min_(ws, A.cap), 0.0f);
   } else if (hist) {
     o = r;
   } else if (cur) {
-    o = make_float4(l, l * l, tfMin(n, A.cap), 0.0f);
+    o = make_float4(l, l * l, sp::min_(n, A.cap), 0.0f);
   }
   A.Mout[pix] = o;
 }
@@ -178,7 +135,7 @@ extern "C" __global__ void __launch_bounds__(256) sail_tfilter_prepare_kernel(Sa
   __shared__ float4 sA[kTfS * kTfS];  // (decoded normal, luminance)
   __shared__ float4 sB[kTfS * kTfS];  // (position, usable)
   __shared__ float sV[kTfV * kTfV];
-  __shared__ uint32_t sBad[4], sTmp[4];
+  __shared__ uint32_t sCnt[2][4];
   const int tx0 = (int)blockIdx.x * 16, ty0 = (int)blockIdx.y * 16;
   // 1. the stage
   for (int t = threadIdx.x; t < kTfS * kTfS; t += 256) {
@@ -188,8 +145,8 @@ extern "C" __global__ void __launch_bounds__(256) sail_tfilter_prepare_kernel(Sa
     if (qx >= 0 && qx < A.W && qy >= 0 && qy < A.H) {
       const size_t q = (size_t)qy * A.W + qx;
       const float4 o = A.Out[q], nn = A.N[q], xp = A.X[q];
-      const bool fin = tfFinite(o.x) && tfFinite(o.y) && tfFinite(o.z);
-      a = make_float4(2.0f * nn.x - 1.0f, 2.0f * nn.y - 1.0f, 2.0f * nn.z - 1.0f, tfLum(o.x, o.y, o.z));
+      const bool fin = sp::finite(o.x) && sp::finite(o.y) && sp::finite(o.z);
+      a = make_float4(2.0f * nn.x - 1.0f, 2.0f * nn.y - 1.0f, 2.0f * nn.z - 1.0f, sp::lum(o.x, o.y, o.z));
       b = make_float4(xp.x, xp.y, xp.z, fin ? 1.0f : 0.0f);
     }
     sA[t] = a;
@@ -211,8 +168,8 @@ extern "C" __global__ void __launch_bounds__(256) sail_tfilter_prepare_kernel(Sa
       const float4 m = A.Mout[q];
       const float n = A.mix ? A.kf : A.S[q].w;
       const float nn = n > 0.0f ? n : 1.0f;
-      const float vt = (tfMax(m.y - m.x * m.x, 0.0f) * nn) / m.z;
-      temporal = m.z >= A.minHist && tfFinite(vt);
+      const float vt = (sp::max_(m.y - m.x * m.x, 0.0f) * nn) / m.z;
+      temporal = m.z >= A.minHist && sp::finite(vt);
       if (temporal) v0 = vt;
     }
     const bool need = inside && !temporal;
@@ -222,7 +179,7 @@ extern "C" __global__ void __launch_bounds__(256) sail_tfilter_prepare_kernel(Sa
     if (t < kTfV * kTfV) sV[t] = v0;
     // the tile's own pixels, not its halo
     const bool own = temporal && vx >= 1 && vx <= 16 && vy >= 1 && vy <= 16;
-    nTemporal += (uint32_t)__popcll(__ballot(own));
+    nTemporal += sp::waveCount(own);
   }
   __syncthreads();
   // 3. the prefilter and the a-trous passes' inputs
@@ -234,39 +191,17 @@ extern "C" __global__ void __launch_bounds__(256) sail_tfilter_prepare_kernel(Sa
     const float4 o = A.Out[pix];
     const float4 ga = sA[(ly + 4) * kTfS + (lx + 4)], gb = sB[(ly + 4) * kTfS + (lx + 4)];
     bad = !(gb.w > 0.0f);
-    float acc = 0.0f, wsum = 0.0f;
-#pragma unroll
-    for (int dy = -1; dy <= 1; dy++) {
-#pragma unroll
-      for (int dx = -1; dx <= 1; dx++) {
-        const int m = (dy < 0 ? -dy : dy) + (dx < 0 ? -dx : dx);
-        const float g = m == 0 ? 0.25f : (m == 1 ? 0.125f : 0.0625f);
-        const float vq = sV[(ly + 1 + dy) * kTfV + (lx + 1 + dx)];
-        if (tfFinite(vq)) { acc += g * vq; wsum += g; }
-      }
-    }
-    const float v = wsum > 0.0f ? acc / wsum : 0.0f;
+    const float v = sp::prefilter(sV, lx, ly);
     A.cv[pix] = make_float4(o.x, o.y, o.z, v);
     A.g0[pix] = make_float4(ga.x, ga.y, ga.z, gb.x);
     A.g1[pix] = make_float2(gb.y, gb.z);
   }
-  const uint32_t nBad = (uint32_t)__popcll(__ballot(bad));
-  if ((threadIdx.x & 63) == 0) { sBad[threadIdx.x >> 6] = nBad; sTmp[threadIdx.x >> 6] = nTemporal; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const size_t tile = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-    A.tileBad[tile] = (sBad[0] + sBad[1]) + (sBad[2] + sBad[3]);
-    A.tileTemporal[tile] = (sTmp[0] + sTmp[1]) + (sTmp[2] + sTmp[3]);
-  }
+  sp::tileCounts<2>({sp::waveCount(bad), nTemporal}, sCnt, {A.tileBad, A.tileTemporal});
 }
 
-hipError_t sail_launch_moment_reproject(const SailMomentReprojectArgs& A, hipStream_t s) {
-  hipLaunchKernelGGL(sail_moment_reproject_kernel, dim3((A.W + 15) / 16, (A.H + 15) / 16), dim3(256), 0, s, A);
-  return hipGetLastError();
-}
-
-hipError_t sail_launch_moment_reproject_moved(const SailMomentReprojectMovedArgs& A, hipStream_t s) {
-  hipLaunchKernelGGL(sail_moment_reproject_moved_kernel, dim3((A.base.W + 15) / 16, (A.base.H + 15) / 16), dim3(256), 0, s, A);
+hipError_t sail_launch_moment_reproject(const SailReprojectArgs& A, bool moved, hipStream_t s) {
+  hipLaunchKernelGGL(moved ? sail_moment_reproject_moved_kernel : sail_moment_reproject_kernel, dim3((A.W + 15) / 16, (A.H + 15) / 16),
+                     dim3(256), 0, s, A);
   return hipGetLastError();
 }
 

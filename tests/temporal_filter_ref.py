@@ -2,78 +2,35 @@
 float32, one operation at a time, the tap loops in the stated order and vectorised over pixels: the reference of
 tests/test_gpu_temporal_filter.py and tests/test_temporal_filter_host.py. Written from the header, not from the kernels.
 Every operation of the formulas is an IEEE f32 one, so the device's maps must equal these bit for bit. The colour passes
-are tests/temporal_ref.py's; the prefilter and the a-trous passes restate sail_denoise's text."""
+and the gather are tests/temporal_ref.py's; the prefilter and the a-trous passes are sail_denoise's, tests/atrous_ref.py."""
 import numpy as np
 
 import temporal_ref as tr
-from temporal_ref import bits  # noqa: F401  (re-exported for the tests)
+from atrous_ref import atrous, lum, prefilter, shifted
+from temporal_ref import bits, fmax, fmin  # noqa: F401  (bits is re-exported for the tests)
 
 F = np.float32
 
 
-def lum(c):
-    return ((c[..., 0] + c[..., 1]) + c[..., 2]) / F(3)
-
-
-def fmax(a, b):
-    """the header's max(a, b) = a > b ? a : b"""
-    return np.where(a > b, a, b).astype(F)
-
-
-def fmin(a, b):
-    """the header's min(a, b) = a < b ? a : b"""
-    return np.where(a < b, a, b).astype(F)
-
-
-def shifted(a, dy, dx, fill):
-    """(a[y + dy, x + dx] with `fill` outside the frame, mask of the taps inside it)"""
-    H, W = a.shape[:2]
-    out = np.full_like(a, fill)
-    inside = np.zeros((H, W), bool)
-    if abs(dy) < H and abs(dx) < W:
-        dst = (slice(max(0, -dy), H - max(0, dy)), slice(max(0, -dx), W - max(0, dx)))
-        src = (slice(max(0, dy), H - max(0, -dy)), slice(max(0, dx), W - max(0, -dx)))
-        out[dst] = a[src]
-        inside[dst] = True
-    return out, inside
-
-
 # ---- moment reproject ---------------------------------------------------------------------------------------------------------
-def ref_moment_reproject(Gcur, Gprev, Mhist, mvp_prev, eye_prev, pos_tol=0.05):
-    """MR (H, W, 4): tests/temporal_ref.py's ref_reproject with Mhist in the place of Hist"""
-    Gcur, Gprev, Mhist = (np.asarray(a, F) for a in (Gcur, Gprev, Mhist))
-    H, W = Gcur.shape[:2]
-    Mp, ep, tol = tr.mp32(mvp_prev), np.asarray(eye_prev, F), F(pos_tol)
-    X, idf = Gcur[..., :3], Gcur[..., 3]
-    u, v, valid = tr.project(Gcur, Mp, W, H)
+def ref_moment_reproject(Gcur, Gprev, Mhist, mvp_prev, eye_prev, pos_tol=0.05, D=None, mc=np.inf):
+    """MR (H, W, 4): tests/temporal_ref.py's ref_reproject with Mhist in the place of Hist and .z as the count"""
+    Mhist = np.asarray(Mhist, F)
+    H, W = Mhist.shape[:2]
+    a1, a2, wsum, m = np.zeros((H, W), F), np.zeros((H, W), F), np.zeros((H, W), F), np.full((H, W), np.inf, F)
     with np.errstate(all="ignore"):
-        iu, iv = np.floor(u), np.floor(v)
-        fu, fv = u - iu, v - iv
-        r = X - ep
-        r2 = (r[..., 0] * r[..., 0] + r[..., 1] * r[..., 1]) + r[..., 2] * r[..., 2]
-        lim = (tol * tol) * r2
-        a1, a2, wsum, m = np.zeros((H, W), F), np.zeros((H, W), F), np.zeros((H, W), F), np.full((H, W), np.inf, F)
-        for b in (0, 1):
-            for a in (0, 1):
-                qx, qy = iu + F(a), iv + F(b)
-                inside = valid & (qx >= F(0)) & (qx <= F(W - 1)) & (qy >= F(0)) & (qy <= F(H - 1))
-                w = (fu if a else F(1) - fu) * (fv if b else F(1) - fv)
-                xi = np.where(inside, qx, F(0)).astype(np.int64)
-                yi = np.where(inside, qy, F(0)).astype(np.int64)
-                gq, h = Gprev[yi, xi], Mhist[yi, xi]
-                e = X - gq[..., :3]
-                e2 = (e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1]) + e[..., 2] * e[..., 2]
-                ok = (inside & (w > F(0)) & (gq[..., 3] == idf) & (e2 <= lim) & (h[..., 2] > F(0))
-                      & np.isfinite(h[..., 0]) & np.isfinite(h[..., 1]))
-                a1 = np.where(ok, a1 + w * h[..., 0], a1)
-                a2 = np.where(ok, a2 + w * h[..., 1], a2)
-                wsum = np.where(ok, wsum + w, wsum)
-                m = np.where(ok & (h[..., 2] < m), h[..., 2], m)
+        for w, ok, yi, xi in tr.gather(Gcur, Gprev, mvp_prev, eye_prev, pos_tol, D):
+            h = Mhist[yi, xi]
+            ok = ok & (h[..., 2] > F(0)) & np.isfinite(h[..., 0]) & np.isfinite(h[..., 1])
+            a1 = np.where(ok, a1 + w * h[..., 0], a1)
+            a2 = np.where(ok, a2 + w * h[..., 1], a2)
+            wsum = np.where(ok, wsum + w, wsum)
+            m = np.where(ok & (h[..., 2] < m), h[..., 2], m)
         found = wsum > F(0)
         MR = np.zeros((H, W, 4), F)
         MR[..., 0] = np.where(found, a1 / wsum, F(0))
         MR[..., 1] = np.where(found, a2 / wsum, F(0))
-        MR[..., 2] = np.where(found, m, F(0))
+        MR[..., 2] = np.where(found, fmin(m, F(mc)), F(0))
     assert a1.dtype == F and wsum.dtype == F
     return MR
 
@@ -151,66 +108,6 @@ def ref_variance(Out, Mout, n, N, X, sigma_x=0.2, min_hist=4.0):
         v0 = np.where(temporal, vt, vs).astype(F)
     assert vt.dtype == F and vs.dtype == F and a1.dtype == F
     return v0, vt, vs, temporal
-
-
-def prefilter(v0):
-    """sail_denoise's 3x3 prefilter of the raw variance"""
-    shape = v0.shape
-    acc, wsum = np.zeros(shape, F), np.zeros(shape, F)
-    g = (F(0.25), F(0.125), F(0.0625))
-    with np.errstate(all="ignore"):
-        for dy in (-1, 0, 1):
-            for dx in (-1, 0, 1):
-                vq, inside = shifted(v0, dy, dx, F(np.nan))
-                ok = inside & np.isfinite(vq)
-                w = g[abs(dy) + abs(dx)]
-                acc = np.where(ok, acc + w * vq, acc)
-                wsum = np.where(ok, wsum + w, wsum)
-        v = np.where(wsum > F(0), acc / wsum, F(0)).astype(F)
-    return v
-
-
-def atrous(c, v, nd, x, iterations=4, sigma_l=1.0, sigma_x=0.2):
-    """sail_denoise's a-trous passes over (c, v) with the guides nd and x"""
-    sl, sx = F(sigma_l), F(sigma_x)
-    kk = (F(0.375), F(0.25), F(0.0625))
-    with np.errstate(all="ignore"):
-        for it in range(iterations):
-            s = 1 << it
-            den = (sl * sl) * v + F(1e-8)
-            sxs = (sx * F(s)) * (sx * F(s))
-            lp = lum(c)
-            acc, vacc, wsum = np.zeros_like(c), np.zeros_like(v), np.zeros_like(v)
-            for dy in range(-2, 3):
-                for dx in range(-2, 3):
-                    cq, inside = shifted(c, s * dy, s * dx, F(0))
-                    if not inside.any():
-                        continue
-                    vq, _ = shifted(v, s * dy, s * dx, F(0))
-                    kw = kk[abs(dy)] * kk[abs(dx)]
-                    if dy == 0 and dx == 0:
-                        w = np.full(v.shape, kw, F)
-                    else:
-                        nq, _ = shifted(nd, s * dy, s * dx, F(0))
-                        xq, _ = shifted(x, s * dy, s * dx, F(0))
-                        d = np.fmax((nd[..., 0] * nq[..., 0] + nd[..., 1] * nq[..., 1]) + nd[..., 2] * nq[..., 2], F(0))
-                        for _ in range(6):
-                            d = d * d
-                        t = x - xq
-                        dx2 = (t[..., 0] * t[..., 0] + t[..., 1] * t[..., 1]) + t[..., 2] * t[..., 2]
-                        wx = F(1) / (F(1) + dx2 / sxs)
-                        dq = lp - lum(cq)
-                        wl = F(1) / (F(1) + (dq * dq) / den)
-                        w = ((kw * d) * wx) * wl
-                    ok = inside & (w > F(0)) & np.isfinite(cq).all(axis=-1) & np.isfinite(vq)
-                    acc = np.where(ok[..., None], acc + w[..., None] * cq, acc)
-                    vacc = np.where(ok, vacc + (w * w) * vq, vacc)
-                    wsum = np.where(ok, wsum + w, wsum)
-            upd = wsum > F(0)
-            c = np.where(upd[..., None], acc / wsum[..., None], c).astype(F)
-            v = np.where(upd, vacc / (wsum * wsum), v).astype(F)
-    assert c.dtype == F and v.dtype == F
-    return c, v
 
 
 def ref_filter(Out, Mout, S, N, X, mix=False, k=0, iterations=4, sigma_l=4.0, sigma_x=0.2, min_hist=4.0):

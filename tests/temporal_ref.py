@@ -102,20 +102,46 @@ def project(G, Mp, W, H):
     return u, v, valid
 
 
-def ref_reproject(Gcur, Gprev, Hist, mvp_prev, eye_prev, pos_tol=0.05):
-    """(R (H, W, 4), the number of pixels that found a history)"""
-    Gcur, Gprev, Hist = (np.asarray(a, F) for a in (Gcur, Gprev, Hist))
+def fmax(a, b):
+    """the header's max(a, b) = a > b ? a : b"""
+    return np.where(a > b, a, b).astype(F)
+
+
+def fmin(a, b):
+    """the header's min(a, b) = a < b ? a : b"""
+    return np.where(a < b, a, b).astype(F)
+
+
+def previous_position(Gcur, D):
+    """(H, W, 4): (Xp, id) with Xp = X - D[(int)id] per component; pixels that miss keep X"""
+    Gcur, D = np.asarray(Gcur, F), np.asarray(D, F).reshape(-1, 3)
+    idf = Gcur[..., 3]
+    hit = ~(idf < F(0))
+    row = np.where(hit, idf, F(0)).astype(np.int64)
+    d = np.where(hit[..., None], D[row], F(0)).astype(F)
+    Gp = Gcur.copy()
+    Gp[..., :3] = Gcur[..., :3] - d
+    assert Gp.dtype == F
+    return Gp
+
+
+def gather(Gcur, Gprev, mvp_prev, eye_prev, pos_tol, D=None):
+    """the reproject passes' up to four taps per pixel, b then a: a list of (w, ok, yi, xi), ok = the tap lies inside the
+    frame with a weight and shows the same object at the same place. With a motion table D (sail_move_objects) the point
+    looked up is Xp = X - D[id]"""
+    Gcur, Gprev = np.asarray(Gcur, F), np.asarray(Gprev, F)
     H, W = Gcur.shape[:2]
     Mp, ep, tol = mp32(mvp_prev), np.asarray(eye_prev, F), F(pos_tol)
-    X, idf = Gcur[..., :3], Gcur[..., 3]
-    u, v, valid = project(Gcur, Mp, W, H)
+    Gp = Gcur if D is None else previous_position(Gcur, D)
+    Xp, idf = Gp[..., :3], Gcur[..., 3]
+    u, v, valid = project(Gp, Mp, W, H)
+    taps = []
     with np.errstate(all="ignore"):
         iu, iv = np.floor(u), np.floor(v)
         fu, fv = u - iu, v - iv
-        r = X - ep
+        r = Xp - ep
         r2 = (r[..., 0] * r[..., 0] + r[..., 1] * r[..., 1]) + r[..., 2] * r[..., 2]
         lim = (tol * tol) * r2
-        acc, wsum, m = np.zeros((H, W, 3), F), np.zeros((H, W), F), np.full((H, W), np.inf, F)
         for b in (0, 1):
             for a in (0, 1):
                 qx, qy = iu + F(a), iv + F(b)
@@ -123,18 +149,31 @@ def ref_reproject(Gcur, Gprev, Hist, mvp_prev, eye_prev, pos_tol=0.05):
                 w = (fu if a else F(1) - fu) * (fv if b else F(1) - fv)
                 xi = np.where(inside, qx, F(0)).astype(np.int64)
                 yi = np.where(inside, qy, F(0)).astype(np.int64)
-                gq, h = Gprev[yi, xi], Hist[yi, xi]
-                e = X - gq[..., :3]
+                gq = Gprev[yi, xi]
+                e = Xp - gq[..., :3]
                 e2 = (e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1]) + e[..., 2] * e[..., 2]
-                ok = (inside & (w > F(0)) & (gq[..., 3] == idf) & (h[..., 3] > F(0)) & np.isfinite(h[..., :3]).all(axis=-1)
-                      & (e2 <= lim))
-                acc = np.where(ok[..., None], acc + w[..., None] * h[..., :3], acc)
-                wsum = np.where(ok, wsum + w, wsum)
-                m = np.where(ok & (h[..., 3] < m), h[..., 3], m)
+                ok = inside & (w > F(0)) & (gq[..., 3] == idf) & (e2 <= lim)
+                assert w.dtype == F and e2.dtype == F
+                taps.append((w, ok, yi, xi))
+    return taps
+
+
+def ref_reproject(Gcur, Gprev, Hist, mvp_prev, eye_prev, pos_tol=0.05, D=None, mc=np.inf):
+    """(R (H, W, 4), the number of pixels that found a history); with D and mc, the pass after sail_move_objects"""
+    Hist = np.asarray(Hist, F)
+    H, W = Hist.shape[:2]
+    acc, wsum, m = np.zeros((H, W, 3), F), np.zeros((H, W), F), np.full((H, W), np.inf, F)
+    with np.errstate(all="ignore"):
+        for w, ok, yi, xi in gather(Gcur, Gprev, mvp_prev, eye_prev, pos_tol, D):
+            h = Hist[yi, xi]
+            ok = ok & (h[..., 3] > F(0)) & np.isfinite(h[..., :3]).all(axis=-1)
+            acc = np.where(ok[..., None], acc + w[..., None] * h[..., :3], acc)
+            wsum = np.where(ok, wsum + w, wsum)
+            m = np.where(ok & (h[..., 3] < m), h[..., 3], m)
         found = wsum > F(0)
         R = np.zeros((H, W, 4), F)
         R[..., :3] = np.where(found[..., None], acc / wsum[..., None], F(0))
-        R[..., 3] = np.where(found, m, F(0))
+        R[..., 3] = np.where(found, fmin(m, F(mc)), F(0))
     assert acc.dtype == F and wsum.dtype == F
     return R, int(found.sum())
 
