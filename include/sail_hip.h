@@ -491,6 +491,75 @@ int sail_move_objects(sail_ctx* ctx, const float* objects, int n, const float* m
  * after a sail_move_objects that found temporal state, until the next successful begin); each may be NULL */
 int sail_temporal_pending_motion(sail_ctx* ctx, float* motion, float* hist_cap, int* pending);
 
+/* ---- albedo map of a view, and the albedo-demodulated denoiser and temporal filter (no reference counterpart; the
+ * demodulation stage of SVGF, Schied et al. 2017) ----
+ * Both a-trous filters stop at normals, positions and a luminance stop scaled by the variance. A procedural texture on one
+ * plane has one normal and one depth, and at low sample counts the variance is large, so nothing stops them from averaging
+ * across the texture. The demodulated calls divide the picture by the first hit's surface colour before filtering and
+ * multiply it back afterwards. The surface colour of a hit is the texture value the trace kernels shade with (the shader's
+ * getSurfaceColor): it enters every material's throughput linearly; emission and the material constants (kd, kr, kt) are
+ * not part of the map.
+ *
+ * The map A of a view (mvp, eye) with grid g in 1..4; pixel (x, y), row 0 = bottom; every operation an f32 IEEE one, in
+ * this order:
+ *   d0..d3 = the corner directions of the G-buffer pass above
+ *   sum = (+0, +0, +0);  cnt = 0
+ *   for j = 0..g-1 (outer), i = 0..g-1:
+ *     s = ((float)x + ((float)i + 0.5f) / (float)g) / (float)W
+ *     t = ((float)y + ((float)j + 0.5f) / (float)g) / (float)H
+ *     d = the G-buffer pass's interpolation of d0..d3 at (s, t);  o = eye
+ *     the sweep of the G-buffer pass: every row in order, the first row with the smallest distance
+ *     on a hit: sc = the trace kernels' hit record's surface colour for that row and distance, with the scene's own texture
+ *               plugins (a texture the scene does not compile gives 0, as in a render)
+ *               sum = sum + sc  (per channel);  cnt = cnt + 1
+ *   A[p] = cnt > 0 ? (sum / (float)cnt, (float)cnt) : (1, 1, 1, 0)
+ * The g x g grid covers exactly the pixel square the frozen schedule's jitter covers (+-1/W in NDC). For g = 1 the ray is
+ * the G-buffer pass's ray bit for bit, so A.w > 0 exactly where its id is >= 0. hit_pixels counts A.w > 0, partial_pixels
+ * 0 < A.w < g*g (a silhouette runs through the pixel).
+ *
+ * State. The albedo call follows the G-buffer call's rules: it launches queued samples, needs a scene (SAIL_E_STATE), and
+ * refuses a singular mvp and, before anything else, a grid outside 1..4 (SAIL_E_INVALID); a multi-device context works on
+ * device 0's scene. It keeps the map as the context's albedo map together with its view, stored as the temporal views are
+ * (each double of P*MV rounded to f32, and the eye); the map is allocated on first use (device 0 of a multi-device
+ * context). The load call installs a caller's map (W H 4 f32) for the view the caller passes. A new scene, updated rows and
+ * moved rows invalidate the map; a reset, a loaded checkpoint, the accumulation mode, the partition and the temporal
+ * calls keep it. Without a valid map the read call and both demodulated filters return SAIL_E_STATE. A context that never
+ * calls these functions allocates nothing, launches nothing new and produces the same bits as before.
+ *
+ * Demodulation, for both filters (amin finite and > 0, else SAIL_E_INVALID before anything else):
+ *   f_c(p) = (A_c(p) is finite and A_c(p) > amin) ? A_c(p) : 1          c in r, g, b
+ *   lf(p) = ((f.r + f.g) + f.b) / 3
+ * The demodulated denoiser: S'(p) = (S.rgb / f, S.w) and P'(p) = (P.rgb / f, P.w), an IEEE divide per channel; the
+ * denoiser's text above is applied to S', P', N and X unchanged and gives (o, ov); out.rgb = o.rgb * f, out.w = 1,
+ * out_var = ov * (lf*lf), out_rgba8 = the display transform of out.rgb. nonfinite counts the pixels whose demodulated c0
+ * is not finite. Parameters and state rules are otherwise the denoiser's.
+ * The demodulated temporal filter: the temporal filter's text with c(q) = Out(q).rgb / f(q) wherever it reads c (the
+ * centre, the 49 spatial taps, the a-trous input) and vt' = vt / (lf_p*lf_p) in vt's place, its finiteness test included;
+ * the outputs are remodulated as above. The history stays un-demodulated: Out, Hist and the moment maps do not change.
+ * It also returns SAIL_E_STATE unless the map's stored view equals the current temporal view bit for bit.
+ * With A = (1, 1, 1, .) everywhere f = 1 and lf = 1 exactly, every x/1, x*1 and x/(1*1) is exact, and both calls return
+ * the plain calls' bits. */
+typedef struct sail_albedo_info {
+  uint64_t hit_pixels;      /* pixels where some sub-ray hit the scene */
+  uint64_t partial_pixels;  /* pixels where some but not all did */
+  int grid;
+  double kernel_ms;         /* HIP events */
+} sail_albedo_info;
+#define SAIL_ALBEDO_AMIN_DEFAULT 0.01f   /* a guard, not a tuned value */
+/* compute the map of a view and keep it; out_rgba (W H 4 f32) and info may each be NULL */
+int sail_albedo(sail_ctx* ctx, const double mvp_rowmajor[16], const float eye[3], int grid, float* out_rgba,
+                sail_albedo_info* info);
+/* install map (W H 4 f32) as the context's albedo map of the view (mvp, eye) */
+int sail_albedo_load(sail_ctx* ctx, const float* map, const double mvp_rowmajor[16], const float eye[3]);
+/* copy the context's albedo map into out (W H 4 f32) */
+int sail_albedo_read(sail_ctx* ctx, float* out);
+/* the denoiser over the demodulated frame; arguments as the plain call's */
+int sail_denoise_albedo(sail_ctx* ctx, const sail_denoise_params* p, float amin, float* out_rgba, float* out_var,
+                        uint8_t* out_rgba8, sail_denoise_info* info);
+/* the temporal filter over the demodulated picture; arguments as the plain call's */
+int sail_temporal_filter_albedo(sail_ctx* ctx, const sail_tfilter_params* p, float amin, float* out_rgba, float* out_var,
+                                uint8_t* out_rgba8, sail_tfilter_info* info);
+
 /* ---- checkpoint / resume of a progressive render (no reference counterpart: the reference restarts its
  * accumulation on every camera or object change, src/core/renderer.js:57-60, src/scene/scene.js:65-68) ----
  * A context's accumulation is `parts` raw accumulators (1 for sail_create, one per device for sail_create_multi),

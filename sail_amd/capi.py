@@ -57,6 +57,7 @@ EXPORTS = (
     "sail_temporal_moments", "sail_temporal_load_moments", "sail_temporal_read_moments",
     "sail_temporal_filter_defaults", "sail_temporal_filter",
     "sail_move_objects", "sail_temporal_pending_motion",
+    "sail_albedo", "sail_albedo_load", "sail_albedo_read", "sail_denoise_albedo", "sail_temporal_filter_albedo",
 )
 
 
@@ -130,6 +131,14 @@ class TfilterInfo(ctypes.Structure):
     _fields_ = [("k", ctypes.c_uint64), ("temporal_pixels", ctypes.c_uint64), ("spatial_pixels", ctypes.c_uint64),
                 ("nonfinite", ctypes.c_uint64), ("iterations", ctypes.c_int), ("kernel_ms", ctypes.c_double),
                 ("pass_ms", ctypes.c_double * 8)]
+
+
+class AlbedoInfo(ctypes.Structure):
+    _fields_ = [("hit_pixels", ctypes.c_uint64), ("partial_pixels", ctypes.c_uint64), ("grid", ctypes.c_int),
+                ("kernel_ms", ctypes.c_double)]
+
+
+ALBEDO_AMIN_DEFAULT = 0.01      # SAIL_ALBEDO_AMIN_DEFAULT: a guard, not a tuned value
 
 
 _SHAPES = {"cube": 1, "sphere": 2, "rectangle": 3, "cone": 4, "cylinder": 5, "disk": 6,
@@ -247,6 +256,13 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
                                                 ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(TfilterInfo)]),
         "sail_move_objects": (ctypes.c_int, [vp, f32p, ctypes.c_int, f32p, ctypes.c_float]),
         "sail_temporal_pending_motion": (ctypes.c_int, [vp, f32p, f32p, ctypes.POINTER(ctypes.c_int)]),
+        "sail_albedo": (ctypes.c_int, [vp, f64p, f32p, ctypes.c_int, f32p, ctypes.POINTER(AlbedoInfo)]),
+        "sail_albedo_load": (ctypes.c_int, [vp, f32p, f64p, f32p]),
+        "sail_albedo_read": (ctypes.c_int, [vp, f32p]),
+        "sail_denoise_albedo": (ctypes.c_int, [vp, ctypes.POINTER(DenoiseParams), ctypes.c_float, f32p, f32p,
+                                               ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(DenoiseInfo)]),
+        "sail_temporal_filter_albedo": (ctypes.c_int, [vp, ctypes.POINTER(TfilterParams), ctypes.c_float, f32p, f32p,
+                                                       ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(TfilterInfo)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -697,11 +713,13 @@ class Context:
         out["history"] = [{"k": int(s.k), "mean": s.mean, "max_tile": s.max_tile} for s in hist[:min(looks.value, cap)]]
         return out
 
-    def denoise(self, params: Optional[dict] = None, want_var: bool = False, want_u8: bool = False) -> dict:
+    def denoise(self, params: Optional[dict] = None, want_var: bool = False, want_u8: bool = False,
+                albedo: Optional[float] = None) -> dict:
         """The variance-guided a-trous denoiser over the frame, the noise mark and the AOV maps (sail_denoise). `params`
         overrides entries of denoise_defaults(). Returns "rgba" (H, W, 4) f32, with want_var "var" (H, W) f32, with
         want_u8 "u8" (H, W, 4) uint8 (the display transform), and k, k_mark, nonfinite, iterations, kernel_ms and
-        pass_ms (prepare, then each a-trous pass)."""
+        pass_ms (prepare, then each a-trous pass). With `albedo` = amin (ALBEDO_AMIN_DEFAULT) the frame is divided by the
+        context's albedo map before the filter and multiplied by it afterwards (sail_denoise_albedo)."""
         p = None
         if params is not None:
             d = denoise_defaults()
@@ -715,8 +733,13 @@ class Context:
         rgba = np.zeros((self.H, self.W, 4), dtype=np.float32)
         var = np.zeros((self.H, self.W), dtype=np.float32) if want_var else None
         u8 = np.zeros((self.H, self.W, 4), dtype=np.uint8) if want_u8 else None
-        self._check(self.lib.sail_denoise(self.h, ctypes.byref(p) if p is not None else None, _ptr(rgba), _ptr(var),
-                                          _ptr(u8, ctypes.c_uint8), ctypes.byref(info)), "sail_denoise")
+        pp = ctypes.byref(p) if p is not None else None
+        if albedo is None:
+            self._check(self.lib.sail_denoise(self.h, pp, _ptr(rgba), _ptr(var), _ptr(u8, ctypes.c_uint8),
+                                              ctypes.byref(info)), "sail_denoise")
+        else:
+            self._check(self.lib.sail_denoise_albedo(self.h, pp, float(albedo), _ptr(rgba), _ptr(var),
+                                                     _ptr(u8, ctypes.c_uint8), ctypes.byref(info)), "sail_denoise_albedo")
         out = {"rgba": rgba, "k": int(info.k), "k_mark": int(info.k_mark), "nonfinite": int(info.nonfinite),
                "iterations": info.iterations, "kernel_ms": info.kernel_ms,
                "pass_ms": [info.pass_ms[i] for i in range(info.iterations + 1)]}
@@ -724,6 +747,35 @@ class Context:
             out["var"] = var
         if want_u8:
             out["u8"] = u8
+        return out
+
+    def albedo(self, mvp, eye, grid: int = 2) -> dict:
+        """The albedo map of a view (sail_albedo): the mean surface colour of the first hits of grid x grid sub-pixel
+        rays per pixel, kept by the context for denoise(albedo=...) and temporal_filter(albedo=...). Returns "rgba"
+        (H, W, 4) f32 (.w: the rays that hit; (1, 1, 1, 0) where none did), hit_pixels, partial_pixels, grid and
+        kernel_ms."""
+        m = np.ascontiguousarray(np.asarray(mvp, dtype=np.float64).reshape(16))
+        e = _f32(eye)
+        out = np.zeros((self.H, self.W, 4), dtype=np.float32)
+        info = AlbedoInfo()
+        self._check(self.lib.sail_albedo(self.h, _ptr(m, ctypes.c_double), _ptr(e), int(grid), _ptr(out),
+                                         ctypes.byref(info)), "sail_albedo")
+        return {"rgba": out, "hit_pixels": int(info.hit_pixels), "partial_pixels": int(info.partial_pixels),
+                "grid": info.grid, "kernel_ms": info.kernel_ms}
+
+    def albedo_load(self, amap, mvp, eye):
+        """Install an albedo map (H, W, 4) f32 for the view (mvp, eye) (sail_albedo_load)."""
+        a = _f32(amap)
+        if a.shape != (self.H, self.W, 4):
+            raise SailError(f"albedo_load: the map must have shape {(self.H, self.W, 4)}")
+        m = np.ascontiguousarray(np.asarray(mvp, dtype=np.float64).reshape(16))
+        e = _f32(eye)
+        self._check(self.lib.sail_albedo_load(self.h, _ptr(a), _ptr(m, ctypes.c_double), _ptr(e)), "sail_albedo_load")
+
+    def albedo_read(self) -> np.ndarray:
+        """The context's albedo map as (H, W, 4) f32 (sail_albedo_read)."""
+        out = np.zeros((self.H, self.W, 4), dtype=np.float32)
+        self._check(self.lib.sail_albedo_read(self.h, _ptr(out)), "sail_albedo_read")
         return out
 
     def gbuffer(self, mvp, eye, rays: bool = False) -> dict:
@@ -835,11 +887,14 @@ class Context:
         self._check(self.lib.sail_temporal_read_moments(self.h, int(which), _ptr(out)), "sail_temporal_read_moments")
         return out
 
-    def temporal_filter(self, params: Optional[dict] = None, want_var: bool = False, want_u8: bool = False) -> dict:
+    def temporal_filter(self, params: Optional[dict] = None, want_var: bool = False, want_u8: bool = False,
+                        albedo: Optional[float] = None) -> dict:
         """The a-trous passes over the resolved picture of the current view, steered by the variance of the tracked
         moments (sail_temporal_filter). `params` overrides entries of temporal_filter_defaults(). Returns "rgba"
         (H, W, 4) f32, with want_var "var" (H, W) f32, with want_u8 "u8" (H, W, 4) uint8 (the display transform), and k,
-        temporal_pixels, spatial_pixels, nonfinite, iterations, kernel_ms and pass_ms (prepare, then each a-trous pass)."""
+        temporal_pixels, spatial_pixels, nonfinite, iterations, kernel_ms and pass_ms (prepare, then each a-trous pass).
+        With `albedo` = amin the picture is filtered divided by the context's albedo map, which must belong to the
+        current temporal view (sail_temporal_filter_albedo)."""
         p = None
         if params is not None:
             d = temporal_filter_defaults()
@@ -853,9 +908,14 @@ class Context:
         rgba = np.zeros((self.H, self.W, 4), dtype=np.float32)
         var = np.zeros((self.H, self.W), dtype=np.float32) if want_var else None
         u8 = np.zeros((self.H, self.W, 4), dtype=np.uint8) if want_u8 else None
-        self._check(self.lib.sail_temporal_filter(self.h, ctypes.byref(p) if p is not None else None, _ptr(rgba),
-                                                  _ptr(var), _ptr(u8, ctypes.c_uint8), ctypes.byref(info)),
-                    "sail_temporal_filter")
+        pp = ctypes.byref(p) if p is not None else None
+        if albedo is None:
+            self._check(self.lib.sail_temporal_filter(self.h, pp, _ptr(rgba), _ptr(var), _ptr(u8, ctypes.c_uint8),
+                                                      ctypes.byref(info)), "sail_temporal_filter")
+        else:
+            self._check(self.lib.sail_temporal_filter_albedo(self.h, pp, float(albedo), _ptr(rgba), _ptr(var),
+                                                             _ptr(u8, ctypes.c_uint8), ctypes.byref(info)),
+                        "sail_temporal_filter_albedo")
         out = {"rgba": rgba, "k": int(info.k), "temporal_pixels": int(info.temporal_pixels),
                "spatial_pixels": int(info.spatial_pixels), "nonfinite": int(info.nonfinite),
                "iterations": info.iterations, "kernel_ms": info.kernel_ms,

@@ -43,6 +43,12 @@ hipError_t sail_launch_temporal_resolve(const SailResolveArgs& A, hipStream_t s)
 hipError_t sail_launch_moment_reproject(const SailReprojectArgs& A, bool moved, hipStream_t s);
 hipError_t sail_launch_moment_resolve(const SailMomentResolveArgs& A, hipStream_t s);
 hipError_t sail_launch_tfilter_prepare(const SailTfilterPrepareArgs& A, hipStream_t s);
+// sail_albedo.hip: the albedo map of a view; the albedo-demodulated instances live beside the plain kernels
+#include "sail_albedo.h"
+hipError_t sail_launch_albedo(const SailAlbedoArgs& A, hipStream_t s);
+hipError_t sail_launch_denoise_prepare_demod(const SailDenoisePrepareDemodArgs& A, hipStream_t s);
+hipError_t sail_launch_denoise_atrous_remod(const SailDenoiseAtrousRemodArgs& A, hipStream_t s);
+hipError_t sail_launch_tfilter_prepare_demod(const SailTfilterPrepareDemodArgs& A, hipStream_t s);
 
 namespace {
 
@@ -249,6 +255,12 @@ struct sail_ctx {
   float tpMotionCap = INFINITY;
   float4* tpMotionDev = nullptr;
   int tpMotionDevRows = 0;
+  // Albedo map (sail_albedo / sail_albedo_load): one float4 map and two counts per 16x16 tile, allocated on first use,
+  // with the view it belongs to, kept as the temporal views are. sail_set_scene, sail_update_objects and sail_move_objects
+  // invalidate it (the rows it shows are gone); on a multi-device context device 0's sub-context holds it.
+  float4* albMap = nullptr;
+  bool albHave = false;
+  TpView albView{};
   nccl_comm_t comm = nullptr;
   int commRanks = 0, commRank = 0;
   // Reduced frame (root of sail_reduce / device 0 of a multi-device context): the sum of every rank's
@@ -1159,10 +1171,11 @@ DenoiseWork denoiseWork(const sail_ctx* c) {
 // What sail_denoise and sail_temporal_filter share: `prepare` launches the pass that fills (cv[0], g0, g1) and the
 // per-tile counts, then the a-trous passes run with steps 1, 2, 4, ..., an event round every pass (ms[0] = prepare,
 // ms[1..] = the passes); the stream is synchronised and the outputs that are asked for are copied back.
+// With a map `alb` (the demodulated calls) the last pass is the remodulating instance.
 template <class Prepare>
 hipError_t runAtrous(sail_ctx* c, const DenoiseWork& w, Prepare prepare, int iterations, float sigma_l, float sigma_x,
                      int display, float gamma_c, float* out_rgba, float* out_var, uint8_t* out_rgba8, float ms[8],
-                     float* total, int* rc) {
+                     float* total, int* rc, const float4* alb = nullptr, float amin = 0.0f) {
   const size_t np = (size_t)c->W * c->H;
   const int nev = iterations + 2;  // before the prepare pass, then after every pass
   PooledEvents ev(c, nev);
@@ -1187,7 +1200,14 @@ hipError_t runAtrous(sail_ctx* c, const DenoiseWork& w, Prepare prepare, int ite
     const float sx = sigma_x * (float)B.step;
     B.sxs = sx * sx;
     B.display = display; B.gammaC = gamma_c;
-    e = sail_launch_denoise_atrous(B, c->stream);
+    if (last && alb) {
+      SailDenoiseAtrousRemodArgs R;
+      memset(&R, 0, sizeof R);
+      R.P = B; R.alb = alb; R.amin = amin;
+      e = sail_launch_denoise_atrous_remod(R, c->stream);
+    } else {
+      e = sail_launch_denoise_atrous(B, c->stream);
+    }
     if (e == hipSuccess) e = hipEventRecord(ev[it + 2], c->stream);
     cur ^= 1;
   }
@@ -1503,7 +1523,7 @@ void sail_destroy(sail_ctx* c) {
   for (auto& pr : c->pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
   for (auto e : c->evPool) (void)hipEventDestroy(e);
   void* bufs[] = {c->accum, c->frame, c->frameN, c->frameP, c->aovN, c->aovP, c->filterOut, c->filterOut8, c->stage, c->segCounter, c->prims, c->tp, c->lt, c->lightObjRow, c->samples, c->wf,
-                  c->noiseMark, c->noiseOut, c->noisePix, c->denoiseWork, c->tpWork, c->tpMom, c->tpMotionDev};
+                  c->noiseMark, c->noiseOut, c->noisePix, c->denoiseWork, c->tpWork, c->tpMom, c->tpMotionDev, c->albMap};
   for (void* b : bufs) if (b) (void)hipFree(b);
   if (c->samplesPinned) (void)hipHostFree(c->samplesPinned);
   if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1698,6 +1718,7 @@ int sail_set_scene(sail_ctx* c, const float* objects, int n, const float* texpar
   c->n = n; c->tn = tn; c->ln = ln;
   c->haveScene = true;
   c->tpHaveCur = c->tpHavePrev = c->tpResolved = false;  // the temporal maps' ids and positions are stale
+  c->albHave = false;                                    // and so are the albedo map's colours
   clearMotion(c);
   HIPCHK(c, zeroMoments(c));
   // Tracer.update links the scene's program (tracer.js:42-90): the plugin set's kernel starts building now, in the
@@ -1725,6 +1746,7 @@ static int updateRows(sail_ctx* c, const float* objects, int n, bool keepTempora
   if (int rc = uploadPrims(c, prims)) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->objectsRows.assign(objects, objects + (size_t)n * 18);
+  c->albHave = false;  // the albedo map shows the rows as they were, whoever moved them
   if (!keepTemporal) {
     c->tpHaveCur = c->tpHavePrev = c->tpResolved = false;  // the temporal maps' ids and positions are stale
     clearMotion(c);
@@ -2277,32 +2299,42 @@ int sail_denoise_defaults(sail_denoise_params* p) {
   return SAIL_OK;
 }
 
-int sail_denoise(sail_ctx* c, const sail_denoise_params* params, float* out_rgba, float* out_var, uint8_t* out_rgba8,
-                 sail_denoise_info* info) {
+}  // extern "C"
+
+namespace {
+
+bool aminOk(float amin) { return std::isfinite(amin) && amin > 0.0f; }
+
+// sail_denoise (demod = false: amin is not read, no map is needed) and sail_denoise_albedo
+int denoiseCall(sail_ctx* c, const char* who, bool demod, const sail_denoise_params* params, float amin, float* out_rgba,
+                float* out_var, uint8_t* out_rgba8, sail_denoise_info* info) {
   if (!c) return SAIL_E_INVALID;
   sail_denoise_params p;
   sail_denoise_defaults(&p);
   if (params) p = *params;
   if (p.iterations < 1 || p.iterations > 6 || !(p.sigma_l > 0.0f) || !std::isfinite(p.sigma_l) || !(p.sigma_x > 0.0f) ||
       !std::isfinite(p.sigma_x) || p.display < SAIL_FILTER_COLOR || p.display > SAIL_FILTER_TONEMAPPING)
-    return fail(c, SAIL_E_INVALID, "sail_denoise: bad parameters (iterations %d of 1..6, sigma_l %g and sigma_x %g finite and > 0, display %d of 0..2)",
-                p.iterations, (double)p.sigma_l, (double)p.sigma_x, p.display);
+    return fail(c, SAIL_E_INVALID, "%s: bad parameters (iterations %d of 1..6, sigma_l %g and sigma_x %g finite and > 0, display %d of 0..2)",
+                who, p.iterations, (double)p.sigma_l, (double)p.sigma_x, p.display);
+  if (demod && !aminOk(amin)) return fail(c, SAIL_E_INVALID, "%s: amin %g must be finite and > 0", who, (double)amin);
   if (!c->subs.empty()) {  // device 0's reduced frame and AOV maps, like sail_filter
-    if (int rc = loadIncomplete(c, "sail_denoise")) return rc;
+    if (int rc = loadIncomplete(c, who)) return rc;
     if (int rc = groupReduce(c)) return rc;
-    return relay(c, sail_denoise(c->subs[0], &p, out_rgba, out_var, out_rgba8, info), c->subs[0]);
+    return relay(c, denoiseCall(c->subs[0], who, demod, &p, amin, out_rgba, out_var, out_rgba8, info), c->subs[0]);
   }
   if (!c->aovN || !c->aovP)
-    return fail(c, SAIL_E_STATE, "sail_denoise: reads the normal and position AOVs (create with SAIL_FLAG_AOV)");
+    return fail(c, SAIL_E_STATE, "%s: reads the normal and position AOVs (create with SAIL_FLAG_AOV)", who);
   if (c->accumMode == SAIL_ACCUM_COMPAT8)
-    return fail(c, SAIL_E_STATE, "sail_denoise: SAIL_ACCUM_COMPAT8 stores 8-bit frames, whose halves cannot be compared");
+    return fail(c, SAIL_E_STATE, "%s: SAIL_ACCUM_COMPAT8 stores 8-bit frames, whose halves cannot be compared", who);
   HIPCHK(c, hipSetDevice(c->device));
   if (int rc = sail_sync(c)) return rc;
   if (!c->noiseHave || !c->noiseMark)
-    return fail(c, SAIL_E_STATE, "sail_denoise: no mark (sail_noise_mark first; a reset or a new scene drops it)");
+    return fail(c, SAIL_E_STATE, "%s: no mark (sail_noise_mark first; a reset or a new scene drops it)", who);
   if (c->k <= c->noiseK)
-    return fail(c, SAIL_E_STATE, "sail_denoise: no sample since the mark (k = %llu, marked at %llu)",
+    return fail(c, SAIL_E_STATE, "%s: no sample since the mark (k = %llu, marked at %llu)", who,
                 (unsigned long long)c->k, (unsigned long long)c->noiseK);
+  if (demod && (!c->albHave || !c->albMap))
+    return fail(c, SAIL_E_STATE, "%s: no albedo map (sail_albedo or sail_albedo_load first; new rows drop it)", who);
   const size_t nt = (size_t)((c->W + 15) / 16) * (size_t)((c->H + 15) / 16);
   if (int rc = ensureDenoiseWork(c)) return rc;
   const DenoiseWork w = denoiseWork(c);
@@ -2315,12 +2347,17 @@ int sail_denoise(sail_ctx* c, const sail_denoise_params* params, float* out_rgba
   A.kf = (float)c->k; A.hf = (float)c->noiseK;
   float ms[8] = {}, total = 0.0f;
   int rc = SAIL_OK;
-  hipError_t e = runAtrous(c, w, [&] { return sail_launch_denoise_prepare(A, c->stream); }, p.iterations, p.sigma_l,
-                           p.sigma_x, p.display, p.gamma_c, out_rgba, out_var, out_rgba8, ms, &total, &rc);
+  SailDenoisePrepareDemodArgs D;
+  memset(&D, 0, sizeof D);
+  D.P = A; D.alb = c->albMap; D.amin = amin;
+  hipError_t e = runAtrous(c, w, [&] { return demod ? sail_launch_denoise_prepare_demod(D, c->stream)
+                                                      : sail_launch_denoise_prepare(A, c->stream); },
+                           p.iterations, p.sigma_l, p.sigma_x, p.display, p.gamma_c, out_rgba, out_var, out_rgba8, ms, &total,
+                           &rc, demod ? c->albMap : nullptr, amin);
   if (rc) return rc;
   std::vector<uint32_t> bad(nt);
   if (e == hipSuccess) e = hipMemcpy(bad.data(), w.bad, nt * 4, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return fail(c, SAIL_E_HIP, "sail_denoise: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return fail(c, SAIL_E_HIP, "%s: %s", who, hipGetErrorString(e));
   if (info) {
     memset(info, 0, sizeof *info);
     info->k = c->k;
@@ -2331,6 +2368,20 @@ int sail_denoise(sail_ctx* c, const sail_denoise_params* params, float* out_rgba
     for (int i = 0; i <= p.iterations; i++) info->pass_ms[i] = ms[i];
   }
   return SAIL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sail_denoise(sail_ctx* c, const sail_denoise_params* params, float* out_rgba, float* out_var, uint8_t* out_rgba8,
+                 sail_denoise_info* info) {
+  return denoiseCall(c, "sail_denoise", false, params, 0.0f, out_rgba, out_var, out_rgba8, info);
+}
+
+int sail_denoise_albedo(sail_ctx* c, const sail_denoise_params* params, float amin, float* out_rgba, float* out_var,
+                        uint8_t* out_rgba8, sail_denoise_info* info) {
+  return denoiseCall(c, "sail_denoise_albedo", true, params, amin, out_rgba, out_var, out_rgba8, info);
 }
 
 // ---- camera-motion reprojection (include/sail_hip.h; the kernels are sail_temporal.hip) ---------------------------------------
@@ -2702,8 +2753,13 @@ int sail_temporal_filter_defaults(sail_tfilter_params* p) {
   return SAIL_OK;
 }
 
-int sail_temporal_filter(sail_ctx* c, const sail_tfilter_params* params, float* out_rgba, float* out_var,
-                         uint8_t* out_rgba8, sail_tfilter_info* info) {
+}  // extern "C"
+
+namespace {
+
+// sail_temporal_filter (demod = false: amin is not read, no map is needed) and sail_temporal_filter_albedo
+int tfilterCall(sail_ctx* c, const char* who, bool demod, const sail_tfilter_params* params, float amin, float* out_rgba,
+                float* out_var, uint8_t* out_rgba8, sail_tfilter_info* info) {
   // the parameters first, so that they can be checked without a device (a NULL context's message: sail_last_error(NULL))
   sail_tfilter_params p;
   sail_temporal_filter_defaults(&p);
@@ -2711,28 +2767,33 @@ int sail_temporal_filter(sail_ctx* c, const sail_tfilter_params* params, float* 
   if (p.iterations < 1 || p.iterations > 6 || !(p.sigma_l > 0.0f) || !std::isfinite(p.sigma_l) || !(p.sigma_x > 0.0f) ||
       !std::isfinite(p.sigma_x) || !std::isfinite(p.min_hist) || p.min_hist < 1.0f || p.display < SAIL_FILTER_COLOR ||
       p.display > SAIL_FILTER_TONEMAPPING)
-    return fail(c, SAIL_E_INVALID, "sail_temporal_filter: bad parameters (iterations %d of 1..6, sigma_l %g and sigma_x %g finite and > 0, min_hist %g finite and >= 1, display %d of 0..2)",
-                p.iterations, (double)p.sigma_l, (double)p.sigma_x, (double)p.min_hist, p.display);
-  if (!c) return fail(c, SAIL_E_INVALID, "sail_temporal_filter: a context is required");
+    return fail(c, SAIL_E_INVALID, "%s: bad parameters (iterations %d of 1..6, sigma_l %g and sigma_x %g finite and > 0, min_hist %g finite and >= 1, display %d of 0..2)",
+                who, p.iterations, (double)p.sigma_l, (double)p.sigma_x, (double)p.min_hist, p.display);
+  if (demod && !aminOk(amin)) return fail(c, SAIL_E_INVALID, "%s: amin %g must be finite and > 0", who, (double)amin);
+  if (!c) return fail(c, SAIL_E_INVALID, "%s: a context is required", who);
   if (!c->subs.empty()) {  // device 0's reduced frame, AOV and temporal maps, like sail_denoise
-    if (int rc = loadIncomplete(c, "sail_temporal_filter")) return rc;
+    if (int rc = loadIncomplete(c, who)) return rc;
     if (int rc = groupReduce(c)) return rc;
-    return relay(c, sail_temporal_filter(c->subs[0], &p, out_rgba, out_var, out_rgba8, info), c->subs[0]);
+    return relay(c, tfilterCall(c->subs[0], who, demod, &p, amin, out_rgba, out_var, out_rgba8, info), c->subs[0]);
   }
   HIPCHK(c, hipSetDevice(c->device));
   if (int rc = sail_sync(c)) return rc;
   if (!c->tpMom)
-    return fail(c, SAIL_E_STATE, "sail_temporal_filter: moment tracking is off (sail_temporal_moments first)");
+    return fail(c, SAIL_E_STATE, "%s: moment tracking is off (sail_temporal_moments first)", who);
   if (!c->aovN || !c->aovP)
-    return fail(c, SAIL_E_STATE, "sail_temporal_filter: reads the normal and position AOVs (create with SAIL_FLAG_AOV)");
+    return fail(c, SAIL_E_STATE, "%s: reads the normal and position AOVs (create with SAIL_FLAG_AOV)", who);
   if (c->accumMode == SAIL_ACCUM_COMPAT8)
-    return fail(c, SAIL_E_STATE, "sail_temporal_filter: SAIL_ACCUM_COMPAT8 stores 8-bit frames, which carry no sample count to blend with");
+    return fail(c, SAIL_E_STATE, "%s: SAIL_ACCUM_COMPAT8 stores 8-bit frames, which carry no sample count to blend with", who);
   if (!c->tpHaveCur || !c->tpWork)
-    return fail(c, SAIL_E_STATE, "sail_temporal_filter: no current view (sail_temporal_begin first; a new scene drops it)");
+    return fail(c, SAIL_E_STATE, "%s: no current view (sail_temporal_begin first; a new scene drops it)", who);
   if (!c->tpResolved)
-    return fail(c, SAIL_E_STATE, "sail_temporal_filter: the current view is not resolved (sail_temporal_resolve first)");
+    return fail(c, SAIL_E_STATE, "%s: the current view is not resolved (sail_temporal_resolve first)", who);
   if (c->k == 0)
-    return fail(c, SAIL_E_STATE, "sail_temporal_filter: no sample of the current view (k = 0: the AOVs belong to another view)");
+    return fail(c, SAIL_E_STATE, "%s: no sample of the current view (k = 0: the AOVs belong to another view)", who);
+  if (demod && (!c->albHave || !c->albMap))
+    return fail(c, SAIL_E_STATE, "%s: no albedo map (sail_albedo or sail_albedo_load first; new rows drop it)", who);
+  if (demod && memcmp(&c->albView, &c->tpCur, sizeof c->albView) != 0)
+    return fail(c, SAIL_E_STATE, "%s: the albedo map belongs to another view than the current temporal view", who);
   const size_t nt = temporalTiles(c), np = (size_t)c->W * c->H;
   if (int rc = ensureDenoiseWork(c)) return rc;
   const DenoiseWork w = denoiseWork(c);  // sail_denoise's work buffers; the count of temporal pixels sits behind the moments
@@ -2749,13 +2810,18 @@ int sail_temporal_filter(sail_ctx* c, const sail_tfilter_params* params, float* 
   A.sx0 = sx2 * sx2;
   float ms[8] = {}, total = 0.0f;
   int rc = SAIL_OK;
-  hipError_t e = runAtrous(c, w, [&] { return sail_launch_tfilter_prepare(A, c->stream); }, p.iterations, p.sigma_l,
-                           p.sigma_x, p.display, p.gamma_c, out_rgba, out_var, out_rgba8, ms, &total, &rc);
+  SailTfilterPrepareDemodArgs D;
+  memset(&D, 0, sizeof D);
+  D.P = A; D.alb = c->albMap; D.amin = amin;
+  hipError_t e = runAtrous(c, w, [&] { return demod ? sail_launch_tfilter_prepare_demod(D, c->stream)
+                                                      : sail_launch_tfilter_prepare(A, c->stream); },
+                           p.iterations, p.sigma_l, p.sigma_x, p.display, p.gamma_c, out_rgba, out_var, out_rgba8, ms, &total,
+                           &rc, demod ? c->albMap : nullptr, amin);
   if (rc) return rc;
   std::vector<uint32_t> bad(nt), tmp(nt);
   if (e == hipSuccess) e = hipMemcpy(bad.data(), w.bad, nt * 4, hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(tmp.data(), dTmp, nt * 4, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return fail(c, SAIL_E_HIP, "sail_temporal_filter: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return fail(c, SAIL_E_HIP, "%s: %s", who, hipGetErrorString(e));
   if (info) {
     memset(info, 0, sizeof *info);
     info->k = c->k;
@@ -2766,6 +2832,110 @@ int sail_temporal_filter(sail_ctx* c, const sail_tfilter_params* params, float* 
     info->kernel_ms = total;
     for (int i = 0; i <= p.iterations; i++) info->pass_ms[i] = ms[i];
   }
+  return SAIL_OK;
+}
+
+uint32_t* albedoCounts(const sail_ctx* c) { return (uint32_t*)(c->albMap + (size_t)c->W * c->H); }
+
+// the albedo map and its two counts per tile, allocated on first use
+int ensureAlbedo(sail_ctx* c) {
+  if (c->albMap) return SAIL_OK;
+  if (hipMalloc(&c->albMap, (size_t)c->W * c->H * 16 + temporalTiles(c) * 8) != hipSuccess) {
+    c->albMap = nullptr;
+    return fail(c, SAIL_E_OOM, "albedo map");
+  }
+  return SAIL_OK;
+}
+
+void albedoView(sail_ctx* c, const double mvp[16], const float eye[3]) {
+  memset(&c->albView, 0, sizeof c->albView);
+  for (int i = 0; i < 16; i++) c->albView.m[i] = (float)mvp[i];
+  memcpy(c->albView.eye, eye, sizeof c->albView.eye);
+}
+
+}  // namespace
+
+extern "C" {
+
+int sail_temporal_filter(sail_ctx* c, const sail_tfilter_params* params, float* out_rgba, float* out_var,
+                         uint8_t* out_rgba8, sail_tfilter_info* info) {
+  return tfilterCall(c, "sail_temporal_filter", false, params, 0.0f, out_rgba, out_var, out_rgba8, info);
+}
+
+int sail_temporal_filter_albedo(sail_ctx* c, const sail_tfilter_params* params, float amin, float* out_rgba, float* out_var,
+                                uint8_t* out_rgba8, sail_tfilter_info* info) {
+  return tfilterCall(c, "sail_temporal_filter_albedo", true, params, amin, out_rgba, out_var, out_rgba8, info);
+}
+
+// ---- the albedo map of a view (include/sail_hip.h; the kernel is sail_albedo.hip) ----------------------------------------------
+int sail_albedo(sail_ctx* c, const double mvp[16], const float eye[3], int grid, float* out_rgba, sail_albedo_info* info) {
+  if (grid < 1 || grid > 4) return fail(c, SAIL_E_INVALID, "sail_albedo: grid %d of 1..4", grid);
+  if (!c) return fail(c, SAIL_E_INVALID, "sail_albedo: a context is required");
+  if (!mvp || !eye) return fail(c, SAIL_E_INVALID, "sail_albedo: mvp and eye are required");
+  if (!c->subs.empty()) return relay(c, sail_albedo(c->subs[0], mvp, eye, grid, out_rgba, info), c->subs[0]);
+  if (!c->haveScene) return fail(c, SAIL_E_STATE, "sail_albedo: no scene (call sail_set_scene first)");
+  SailGbufferArgs G;
+  if (int rc = gbufferArgs(c, "sail_albedo", mvp, eye, &G)) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = sail_sync(c)) return rc;
+  if (int rc = ensureAlbedo(c)) return rc;
+  const size_t nt = temporalTiles(c), np = (size_t)c->W * c->H;
+  SailAlbedoArgs A;
+  memset(&A, 0, sizeof A);
+  A.prims = c->prims; A.texparams = c->tp; A.n = c->n; A.tn = c->tn;
+  A.texMask = c->plugins.texture_mask;
+  memcpy(A.d, G.d, sizeof A.d);
+  memcpy(A.eye, eye, sizeof A.eye);
+  A.W = c->W; A.H = c->H; A.grid = grid;
+  A.A = c->albMap;
+  A.tileHit = albedoCounts(c); A.tilePartial = A.tileHit + nt;
+  c->albHave = false;  // a call that fails leaves no map
+  PooledEvents ev(c, 2);
+  if (ev.rc) return ev.rc;
+  float ms = 0.0f;
+  hipError_t e = hipEventRecord(ev[0], c->stream);
+  if (e == hipSuccess) e = sail_launch_albedo(A, c->stream);
+  if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+  std::vector<uint32_t> host(nt * 2);
+  if (e == hipSuccess) e = hipMemcpy(host.data(), A.tileHit, nt * 8, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && out_rgba) e = hipMemcpy(out_rgba, c->albMap, np * 16, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(c, SAIL_E_HIP, "sail_albedo: %s", hipGetErrorString(e));
+  albedoView(c, mvp, eye);
+  c->albHave = true;
+  if (info) {
+    memset(info, 0, sizeof *info);
+    info->hit_pixels = sumTiles(host, 0, nt);
+    info->partial_pixels = sumTiles(host, nt, nt);
+    info->grid = grid;
+    info->kernel_ms = ms;
+  }
+  return SAIL_OK;
+}
+
+int sail_albedo_load(sail_ctx* c, const float* map, const double mvp[16], const float eye[3]) {
+  if (!c) return SAIL_E_INVALID;
+  if (!map || !mvp || !eye) return fail(c, SAIL_E_INVALID, "sail_albedo_load: map, mvp and eye are required");
+  if (!c->subs.empty()) return relay(c, sail_albedo_load(c->subs[0], map, mvp, eye), c->subs[0]);
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (int rc = ensureAlbedo(c)) return rc;
+  HIPCHK(c, hipMemcpy(c->albMap, map, (size_t)c->W * c->H * 16, hipMemcpyHostToDevice));
+  albedoView(c, mvp, eye);
+  c->albHave = true;
+  return SAIL_OK;
+}
+
+int sail_albedo_read(sail_ctx* c, float* out) {
+  if (!c) return SAIL_E_INVALID;
+  if (!out) return fail(c, SAIL_E_INVALID, "sail_albedo_read: an output is required");
+  if (!c->subs.empty()) return relay(c, sail_albedo_read(c->subs[0], out), c->subs[0]);
+  if (!c->albHave || !c->albMap)
+    return fail(c, SAIL_E_STATE, "sail_albedo_read: no albedo map (sail_albedo or sail_albedo_load first; new rows drop it)");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(out, c->albMap, (size_t)c->W * c->H * 16, hipMemcpyDeviceToHost));
   return SAIL_OK;
 }
 

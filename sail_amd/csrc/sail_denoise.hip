@@ -1,5 +1,7 @@
 // sail_denoise.hip — the variance-guided a-trous denoiser of a progressive frame on the MI355X (gfx950):
-// sail_denoise_prepare_kernel and sail_denoise_atrous_kernel.
+// sail_denoise_prepare_kernel and sail_denoise_atrous_kernel, and their albedo-demodulated instances
+// sail_denoise_prepare_demod_kernel and sail_denoise_atrous_remod_kernel (sail_denoise_albedo; the remodulating pass also
+// ends sail_temporal_filter_albedo).
 //
 // No reference counterpart (the reference's only denoiser is the `wavelet` display filter, sail_filter_kernel kind 4,
 // whose edge stops are constants and which never reads the normal map). This one is the edge-avoiding a-trous wavelet of
@@ -29,13 +31,16 @@
 //  * texels outside the frame are never loaded (their LDS slots hold zeros and their taps are skipped by coordinates);
 //    lanes outside ragged tiles load nothing and store nothing;
 //  * the last pass stores the RGBA output, the variance and the display transform as RGBA8 in one 32-bit store;
-//  * plain vector stores only, no atomics: equal data give equal bits.
+//  * plain vector stores only, no atomics: equal data give equal bits;
+//  * the demodulated instances ("sail_albedo_kernel and the albedo-demodulated filters") are second
+//    instances of the same bodies, entry points of their own, not run-time switches: the plain kernels pay no map load.
 // Lives in its own file and defines no macro: the text of sail_trace.hip is embedded in the library and hashed into every
 // run-time kernel's cache key. Built with the library's flags (no contraction, no fast math: `/` is the IEEE divide).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "sail_post.h"
 #include "sail_denoise.h"
+#include "sail_albedo.h"
 
 namespace {
 
@@ -60,7 +65,12 @@ __device__ __forceinline__ float dnRawVariance(const float4 s, const float4 p, i
 
 }  // namespace
 
-extern "C" __global__ void __launch_bounds__(256) sail_denoise_prepare_kernel(SailDenoisePrepareArgs A) {
+// The prepare pass. DEMOD = false is sail_denoise_prepare_kernel (alb and amin are not read). DEMOD = true is
+// sail_denoise_albedo's (include/sail_hip.h): S and P are divided by the albedo factor f channel by channel, an IEEE divide
+// each, before anything else reads them: two more float4 loads per texel of the variance stage's halo (the map at q) and
+// one per pixel, which the plain kernel does not pay.
+template <bool DEMOD>
+__device__ __forceinline__ void dnPrepare(const SailDenoisePrepareArgs& A, const float4* alb, float amin) {
   __shared__ float sV[sp::kVarT * sp::kVarT];
   __shared__ uint32_t sBad[1][4];
   const int x0 = (int)blockIdx.x * 16 - 1, y0 = (int)blockIdx.y * 16 - 1;
@@ -70,7 +80,13 @@ extern "C" __global__ void __launch_bounds__(256) sail_denoise_prepare_kernel(Sa
     float v = __builtin_nanf("");  // outside the frame: skipped by the prefilter
     if (qx >= 0 && qx < A.W && qy >= 0 && qy < A.H) {
       const size_t q = (size_t)qy * A.W + qx;
-      v = dnRawVariance(A.S[q], A.P[q], A.mix, A.kf, A.hf);
+      float4 sq = A.S[q], pq = A.P[q];
+      if (DEMOD) {
+        const sp::Rgb f = sp::albedoFactor(alb[q], amin);
+        sq = make_float4(sq.x / f.r, sq.y / f.g, sq.z / f.b, sq.w);
+        pq = make_float4(pq.x / f.r, pq.y / f.g, pq.z / f.b, pq.w);
+      }
+      v = dnRawVariance(sq, pq, A.mix, A.kf, A.hf);
     }
     sV[t] = v;
   }
@@ -80,7 +96,11 @@ extern "C" __global__ void __launch_bounds__(256) sail_denoise_prepare_kernel(Sa
   bool bad = false;
   if (x < A.W && y < A.H) {
     const size_t pix = (size_t)y * A.W + x;
-    const float4 s = A.S[pix];
+    float4 s = A.S[pix];
+    if (DEMOD) {
+      const sp::Rgb f = sp::albedoFactor(alb[pix], amin);
+      s = make_float4(s.x / f.r, s.y / f.g, s.z / f.b, s.w);
+    }
     const sp::Rgb c = sp::shownMean(s, A.mix, s.w);
     bad = !(sp::finite(c.r) && sp::finite(c.g) && sp::finite(c.b));
     const float v = sp::prefilter(sV, lx, ly);
@@ -92,7 +112,20 @@ extern "C" __global__ void __launch_bounds__(256) sail_denoise_prepare_kernel(Sa
   sp::tileCounts<1>({sp::waveCount(bad)}, sBad, {A.tileBad});
 }
 
-extern "C" __global__ void __launch_bounds__(256) sail_denoise_atrous_kernel(SailDenoiseAtrousArgs A) {
+extern "C" __global__ void __launch_bounds__(256) sail_denoise_prepare_kernel(SailDenoisePrepareArgs A) {
+  dnPrepare<false>(A, nullptr, 0.0f);
+}
+
+extern "C" __global__ void __launch_bounds__(256) sail_denoise_prepare_demod_kernel(SailDenoisePrepareDemodArgs A) {
+  dnPrepare<true>(A.P, A.alb, A.amin);
+}
+
+// One a-trous pass. REMOD = false is sail_denoise_atrous_kernel (alb and amin are not read). REMOD = true is the last pass
+// of the demodulated filters: the outputs are multiplied by the albedo factor again (colour by f, variance by lf * lf): one
+// more float4 load per pixel. With a step above 1 a wave's pixels lie `step` texels apart, so that load, like the pass's
+// stores, uses 16 bytes of every cache line it touches: loading the texel ahead of the taps measured the same.
+template <bool REMOD>
+__device__ __forceinline__ void dnAtrous(const SailDenoiseAtrousArgs& A, const float4* alb, float amin) {
   __shared__ float4 sCV[kDnT * kDnT];
   __shared__ float4 sG0[kDnT * kDnT];
   __shared__ float2 sG1[kDnT * kDnT];
@@ -160,13 +193,31 @@ extern "C" __global__ void __launch_bounds__(256) sail_denoise_atrous_kernel(Sai
   if (wsum > 0.0f) o = make_float4(ar / wsum, ag / wsum, ab / wsum, vacc / (wsum * wsum));
   const size_t pix = (size_t)y * A.W + x;
   if (!A.last) { A.dst[pix] = o; return; }
+  if (REMOD) {
+    const sp::Rgb f = sp::albedoFactor(alb[pix], amin);
+    const float lf = sp::lum(f.r, f.g, f.b);
+    o = make_float4(o.x * f.r, o.y * f.g, o.z * f.b, o.w * (lf * lf));
+  }
   if (A.dst) A.dst[pix] = make_float4(o.x, o.y, o.z, 1.0f);
   if (A.outVar) A.outVar[pix] = o.w;
   if (A.out8) A.out8[pix] = sp::rgba8(o.x, o.y, o.z, A.display, A.gammaC);
 }
 
+extern "C" __global__ void __launch_bounds__(256) sail_denoise_atrous_kernel(SailDenoiseAtrousArgs A) {
+  dnAtrous<false>(A, nullptr, 0.0f);
+}
+
+extern "C" __global__ void __launch_bounds__(256) sail_denoise_atrous_remod_kernel(SailDenoiseAtrousRemodArgs A) {
+  dnAtrous<true>(A.P, A.alb, A.amin);
+}
+
 hipError_t sail_launch_denoise_prepare(const SailDenoisePrepareArgs& A, hipStream_t s) {
   hipLaunchKernelGGL(sail_denoise_prepare_kernel, dim3((A.W + 15) / 16, (A.H + 15) / 16), dim3(256), 0, s, A);
+  return hipGetLastError();
+}
+
+hipError_t sail_launch_denoise_prepare_demod(const SailDenoisePrepareDemodArgs& A, hipStream_t s) {
+  hipLaunchKernelGGL(sail_denoise_prepare_demod_kernel, dim3((A.P.W + 15) / 16, (A.P.H + 15) / 16), dim3(256), 0, s, A);
   return hipGetLastError();
 }
 
@@ -175,5 +226,13 @@ hipError_t sail_launch_denoise_atrous(const SailDenoiseAtrousArgs& A, hipStream_
   const int cx = A.step < A.W ? A.step : A.W, cy = A.step < A.H ? A.step : A.H;
   const int nx = ((A.W + A.step - 1) / A.step + 15) / 16, ny = ((A.H + A.step - 1) / A.step + 15) / 16;
   hipLaunchKernelGGL(sail_denoise_atrous_kernel, dim3(cx * nx, cy * ny), dim3(256), 0, s, A);
+  return hipGetLastError();
+}
+
+hipError_t sail_launch_denoise_atrous_remod(const SailDenoiseAtrousRemodArgs& R, hipStream_t s) {
+  const SailDenoiseAtrousArgs& A = R.P;
+  const int cx = A.step < A.W ? A.step : A.W, cy = A.step < A.H ? A.step : A.H;
+  const int nx = ((A.W + A.step - 1) / A.step + 15) / 16, ny = ((A.H + A.step - 1) / A.step + 15) / 16;
+  hipLaunchKernelGGL(sail_denoise_atrous_remod_kernel, dim3(cx * nx, cy * ny), dim3(256), 0, s, R);
   return hipGetLastError();
 }

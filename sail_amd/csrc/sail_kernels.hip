@@ -5,10 +5,12 @@
 // sail_post.h (what the post-processing kernels share), sail_noise.hip, sail_denoise.hip and sail_tfilter.hip come first:
 // they define no macro (sail_post.h includes sail_math.h, which sail_trace.hip includes itself), so the trace kernels
 // compile exactly as they do alone. sail_temporal.hip comes last: its G-buffer pass calls sail_trace.hip's mkRay, primT and
-// constRow, and nothing it declares is seen by the trace kernels.
+// constRow, and nothing it declares is seen by the trace kernels. sail_albedo.hip follows it for the same reason: its
+// kernel calls mkRay, primT, constRow and hitRecordU.
 #include "sail_post.h"
 #include "sail_noise.hip"
 #include "sail_denoise.hip"
 #include "sail_tfilter.hip"
 #include "sail_trace.hip"
 #include "sail_temporal.hip"
+#include "sail_albedo.hip"

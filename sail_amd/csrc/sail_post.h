@@ -43,6 +43,14 @@ __device__ __forceinline__ Rgb shownMean(const float4 s, int mix, float n) {
   return {0.0f, 0.0f, 0.0f};
 }
 
+// the albedo factor of a texel of the albedo map (include/sail_hip.h, sail_denoise_albedo): a channel that is finite and
+// above amin, else 1. The demodulated instances of the prepare passes divide by it, the remodulating a-trous pass
+// multiplies by it; with a map of ones every x / 1 and x * 1 is exact
+__device__ __forceinline__ float albedoChannel(float a, float amin) { return (finite(a) && a > amin) ? a : 1.0f; }
+__device__ __forceinline__ Rgb albedoFactor(const float4 a, float amin) {
+  return {albedoChannel(a.x, amin), albedoChannel(a.y, amin), albedoChannel(a.z, amin)};
+}
+
 // Per-tile counts of a 256-thread workgroup: each wave's count (waveCount of a flag, or a sum of them) goes through LDS
 // and thread 0 stores (w0 + w1) + (w2 + w3) at the tile's index of out[i]. N counts share ONE barrier; every thread of
 // the workgroup calls it.

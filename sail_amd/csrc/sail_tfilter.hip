@@ -1,5 +1,6 @@
 // sail_tfilter.hip — the filter of a reprojected frame on the MI355X (gfx950): sail_moment_reproject_kernel,
-// sail_moment_resolve_kernel and sail_tfilter_prepare_kernel.
+// sail_moment_resolve_kernel and sail_tfilter_prepare_kernel, and the latter's albedo-demodulated instance
+// sail_tfilter_prepare_demod_kernel (sail_temporal_filter_albedo).
 //
 // No reference counterpart (the reference throws the picture away on every camera move). This is the piece SVGF (Schied et
 // al. 2017) has between its temporal accumulation and its a-trous filter: the first two moments of each pixel's luminance
@@ -37,6 +38,7 @@
 #include <stdint.h>
 #include "sail_post.h"
 #include "sail_tfilter.h"
+#include "sail_albedo.h"
 
 namespace {
 
@@ -131,7 +133,12 @@ extern "C" __global__ void __launch_bounds__(256) sail_moment_resolve_kernel(Sai
   A.Mout[pix] = o;
 }
 
-extern "C" __global__ void __launch_bounds__(256) sail_tfilter_prepare_kernel(SailTfilterPrepareArgs A) {
+// The prepare pass. DEMOD = false is sail_tfilter_prepare_kernel (alb and amin are not read). DEMOD = true is
+// sail_temporal_filter_albedo's (include/sail_hip.h): wherever the text reads c it is Out.rgb divided by the albedo factor
+// f channel by channel, so the stage holds the demodulated luminance and its finiteness, vt is divided by lf * lf, and
+// the a-trous input is the demodulated colour: one more float4 load per texel of the stage, of the v0 tile and per pixel.
+template <bool DEMOD>
+__device__ __forceinline__ void tfPrepare(const SailTfilterPrepareArgs& A, const float4* alb, float amin) {
   __shared__ float4 sA[kTfS * kTfS];  // (decoded normal, luminance)
   __shared__ float4 sB[kTfS * kTfS];  // (position, usable)
   __shared__ float sV[kTfV * kTfV];
@@ -144,7 +151,12 @@ extern "C" __global__ void __launch_bounds__(256) sail_tfilter_prepare_kernel(Sa
     float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a;
     if (qx >= 0 && qx < A.W && qy >= 0 && qy < A.H) {
       const size_t q = (size_t)qy * A.W + qx;
-      const float4 o = A.Out[q], nn = A.N[q], xp = A.X[q];
+      float4 o = A.Out[q];
+      const float4 nn = A.N[q], xp = A.X[q];
+      if (DEMOD) {
+        const sp::Rgb f = sp::albedoFactor(alb[q], amin);
+        o = make_float4(o.x / f.r, o.y / f.g, o.z / f.b, o.w);
+      }
       const bool fin = sp::finite(o.x) && sp::finite(o.y) && sp::finite(o.z);
       a = make_float4(2.0f * nn.x - 1.0f, 2.0f * nn.y - 1.0f, 2.0f * nn.z - 1.0f, sp::lum(o.x, o.y, o.z));
       b = make_float4(xp.x, xp.y, xp.z, fin ? 1.0f : 0.0f);
@@ -168,7 +180,12 @@ extern "C" __global__ void __launch_bounds__(256) sail_tfilter_prepare_kernel(Sa
       const float4 m = A.Mout[q];
       const float n = A.mix ? A.kf : A.S[q].w;
       const float nn = n > 0.0f ? n : 1.0f;
-      const float vt = (sp::max_(m.y - m.x * m.x, 0.0f) * nn) / m.z;
+      float vt = (sp::max_(m.y - m.x * m.x, 0.0f) * nn) / m.z;
+      if (DEMOD) {
+        const sp::Rgb f = sp::albedoFactor(alb[q], amin);
+        const float lf = sp::lum(f.r, f.g, f.b);
+        vt = vt / (lf * lf);
+      }
       temporal = m.z >= A.minHist && sp::finite(vt);
       if (temporal) v0 = vt;
     }
@@ -188,7 +205,11 @@ extern "C" __global__ void __launch_bounds__(256) sail_tfilter_prepare_kernel(Sa
   bool bad = false;
   if (x < A.W && y < A.H) {
     const size_t pix = (size_t)y * A.W + x;
-    const float4 o = A.Out[pix];
+    float4 o = A.Out[pix];
+    if (DEMOD) {
+      const sp::Rgb f = sp::albedoFactor(alb[pix], amin);
+      o = make_float4(o.x / f.r, o.y / f.g, o.z / f.b, o.w);
+    }
     const float4 ga = sA[(ly + 4) * kTfS + (lx + 4)], gb = sB[(ly + 4) * kTfS + (lx + 4)];
     bad = !(gb.w > 0.0f);
     const float v = sp::prefilter(sV, lx, ly);
@@ -197,6 +218,14 @@ extern "C" __global__ void __launch_bounds__(256) sail_tfilter_prepare_kernel(Sa
     A.g1[pix] = make_float2(gb.y, gb.z);
   }
   sp::tileCounts<2>({sp::waveCount(bad), nTemporal}, sCnt, {A.tileBad, A.tileTemporal});
+}
+
+extern "C" __global__ void __launch_bounds__(256) sail_tfilter_prepare_kernel(SailTfilterPrepareArgs A) {
+  tfPrepare<false>(A, nullptr, 0.0f);
+}
+
+extern "C" __global__ void __launch_bounds__(256) sail_tfilter_prepare_demod_kernel(SailTfilterPrepareDemodArgs A) {
+  tfPrepare<true>(A.P, A.alb, A.amin);
 }
 
 hipError_t sail_launch_moment_reproject(const SailReprojectArgs& A, bool moved, hipStream_t s) {
@@ -212,5 +241,10 @@ hipError_t sail_launch_moment_resolve(const SailMomentResolveArgs& A, hipStream_
 
 hipError_t sail_launch_tfilter_prepare(const SailTfilterPrepareArgs& A, hipStream_t s) {
   hipLaunchKernelGGL(sail_tfilter_prepare_kernel, dim3((A.W + 15) / 16, (A.H + 15) / 16), dim3(256), 0, s, A);
+  return hipGetLastError();
+}
+
+hipError_t sail_launch_tfilter_prepare_demod(const SailTfilterPrepareDemodArgs& A, hipStream_t s) {
+  hipLaunchKernelGGL(sail_tfilter_prepare_demod_kernel, dim3((A.P.W + 15) / 16, (A.P.H + 15) / 16), dim3(256), 0, s, A);
   return hipGetLastError();
 }

@@ -4,7 +4,7 @@
 // assigns `scene`, then Renderer.update(scene)), render N samples on the GPU and write the frame to disk.
 //
 //   node sail_amd/js/cli.js scene.js [--width 512] [--height 512] [--spp 64] [--bounces 5] [--device -1]
-//        [--noise X [--min-spp 16] [--max-spp 65536]] [--denoise [--denoise-iterations 4]]
+//        [--noise X [--min-spp 16] [--max-spp 65536]] [--denoise [--denoise-iterations 4] [--albedo [--albedo-grid 2]]]
 //        [--filter <name>] [--filter-r 'vec2(2.0,2.0)'] [--gamma 2.2] [--deterministic]
 //        [--png out.png] [--pfm out.pfm] [--exr out.exr] [--stats]
 //
@@ -12,6 +12,8 @@
 // every doubling, up to --max-spp. --stats then also prints the spp reached, the noise and whether it converged.
 // --denoise writes the variance-guided a-trous denoiser's image instead of the frame: with --spp N it marks the frame at
 // floor(N/2) samples, with --noise X it uses the mark of the look before the last. --stats then also prints denoise_ms.
+// --albedo divides the frame by the albedo map of the view before the denoiser and multiplies it back afterwards, so that
+// procedural textures survive; --albedo-grid N (1..4) is the map's sub-pixel grid. --stats then also prints albedo_ms.
 // The script sees `Sail` (the full API) and must assign `scene` (a Sail.Scene with a camera), exactly as the
 // editor text does. --filter overrides scene.filter for the PNG (with --denoise it becomes the denoiser's display transform:
 // color, gamma or tonemapping); without --denoise the PFM and EXR are always the unfiltered mean image.
@@ -36,6 +38,8 @@ function parse(argv) {
       case '--max-spp': opt.maxSpp = parseInt(val(), 10); opt.untilGiven = a; break;
       case '--denoise': opt.denoise = true; break;
       case '--denoise-iterations': opt.denoiseIterations = parseInt(val(), 10); break;
+      case '--albedo': opt.albedo = true; break;
+      case '--albedo-grid': opt.albedoGrid = parseInt(val(), 10); break;
       case '--bounces': opt.bounces = parseInt(val(), 10); break;
       case '--device': opt.device = parseInt(val(), 10); break;
       case '--filter': opt.filter = val(); break;
@@ -58,6 +62,10 @@ function parse(argv) {
   if (opt.denoiseIterations !== undefined && !opt.denoise) throw new Error('--denoise-iterations needs --denoise');
   if (opt.denoiseIterations !== undefined && !(opt.denoiseIterations >= 1 && opt.denoiseIterations <= 6))
     throw new Error('--denoise-iterations needs a number from 1 to 6');
+  if (opt.albedo && !opt.denoise) throw new Error('--albedo needs --denoise');
+  if (opt.albedoGrid !== undefined && !opt.albedo) throw new Error('--albedo-grid needs --albedo');
+  if (opt.albedoGrid !== undefined && !(opt.albedoGrid >= 1 && opt.albedoGrid <= 4))
+    throw new Error('--albedo-grid needs a number from 1 to 4');
   if (opt.denoise && opt.noise === undefined && !(opt.spp >= 2))
     throw new Error('--denoise needs --spp 2 or more: it compares the two halves of the samples');
   opt.script = rest[0];
@@ -76,7 +84,7 @@ function loadScene(file) {
 function main() {
   const opt = parse(process.argv.slice(2));
   if (opt.help || !opt.script) {
-    process.stdout.write(fs.readFileSync(__filename, 'utf8').split('\n').slice(2, 17).map((l) => l.replace(/^\/\/ ?/, '')).join('\n') + '\n');
+    process.stdout.write(fs.readFileSync(__filename, 'utf8').split('\n').slice(2, 19).map((l) => l.replace(/^\/\/ ?/, '')).join('\n') + '\n');
     return opt.help ? 0 : 2;
   }
   const scene = loadScene(opt.script);
@@ -98,11 +106,13 @@ function main() {
     r.noiseMark();
     r.renderSamples(scene, opt.spp - Math.floor(opt.spp / 2));
   } else r.renderSamples(scene, opt.spp);
-  let mean, den = null;
+  let mean, den = null, alb = null;
   if (opt.denoise) {
     if (until && until.history.length < 2)
       throw new Error(`--denoise: the render stopped at its first look (${until.k} spp), which only marks the frame: no second look, so there are no two halves to compare (raise --max-spp above --min-spp)`);
-    den = r.denoise({ iterations: opt.denoiseIterations, display: opt.png ? r.filter.kind : undefined, gamma: r.filter.gamma });
+    if (opt.albedo) alb = r.albedo(scene, { grid: opt.albedoGrid === undefined ? 2 : opt.albedoGrid });
+    den = r.denoise({ iterations: opt.denoiseIterations, display: opt.png ? r.filter.kind : undefined, gamma: r.filter.gamma,
+      albedo: opt.albedo ? { grid: alb.grid } : undefined });
     mean = den.rgba;
   } else mean = r.readPixels();
   const ms = Number(process.hrtime.bigint() - t0) / 1e6;
@@ -116,6 +126,7 @@ function main() {
     // (a frame that never reached a second look has no estimate: its noise is infinite, null in JSON)
     if (until) Object.assign(out, { noise: until.mean, converged: until.converged });
     if (den) out.denoise_ms = den.info.kernelMs;
+    if (alb) Object.assign(out, { albedo_ms: alb.kernelMs, albedo_grid: alb.grid });
     process.stdout.write(JSON.stringify(out) + '\n');
   }
   r.destroy();

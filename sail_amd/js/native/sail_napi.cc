@@ -39,6 +39,16 @@ bool args(napi_env env, napi_callback_info info, size_t n, napi_value* out) {
   }
   return true;
 }
+// at least n arguments, up to cap: those not passed are undefined
+bool argsUpTo(napi_env env, napi_callback_info info, size_t n, size_t cap, napi_value* out) {
+  size_t argc = cap;
+  if (napi_get_cb_info(env, info, &argc, out, nullptr, nullptr) != napi_ok) return false;
+  if (argc < n) {
+    napi_throw_type_error(env, nullptr, "not enough arguments");
+    return false;
+  }
+  return true;
+}
 bool getInt(napi_env env, napi_value v, int* out) {
   if (napi_get_value_int32(env, v, out) != napi_ok) { napi_throw_type_error(env, nullptr, "expected a number"); return false; }
   return true;
@@ -480,11 +490,21 @@ napi_value RenderUntil(napi_env env, napi_callback_info info) {
   NAPI_OK(napi_set_named_property(env, out, "history", list));
   return out;
 }
-// the denoiser (sail_denoise): (ctx, iterations, sigmaL, sigmaX, display, gamma, wantU8) -> {rgba, rgba8?, info}; a
-// parameter that is undefined or null keeps sail_denoise_defaults' value
+// an optional amin: undefined or null is the plain call (*have = false)
+bool optionalAmin(napi_env env, napi_value v, bool* have, float* amin) {
+  napi_valuetype vt;
+  napi_typeof(env, v, &vt);
+  *have = !(vt == napi_undefined || vt == napi_null);
+  double d = 0.0;
+  if (*have && !getDouble(env, v, &d)) return false;
+  *amin = (float)d;
+  return true;
+}
+// the denoiser (sail_denoise): (ctx, iterations, sigmaL, sigmaX, display, gamma, wantU8[, amin]) -> {rgba, rgba8?, info};
+// a parameter that is undefined or null keeps sail_denoise_defaults' value; with amin, sail_denoise_albedo
 napi_value Denoise(napi_env env, napi_callback_info info) {
-  napi_value a[7];
-  if (!args(env, info, 7, a)) return nullptr;
+  napi_value a[8];
+  if (!argsUpTo(env, info, 7, 8, a)) return nullptr;
   Handle* h;
   if (!getHandle(env, a[0], &h)) return nullptr;
   sail_denoise_params p;
@@ -507,9 +527,13 @@ napi_value Denoise(napi_env env, napi_callback_info info) {
   void *pf = nullptr, *p8 = nullptr;
   napi_value f = makeTyped(env, napi_float32_array, np, 4, &pf), u8 = nullptr;
   if (wantU8) u8 = makeTyped(env, napi_uint8_array, np, 1, &p8);
+  bool demod = false;
+  float amin = 0.0f;
+  if (!optionalAmin(env, a[7], &demod, &amin)) return nullptr;
   sail_denoise_info n;
-  const int rc = sail_denoise(h->ctx, &p, (float*)pf, nullptr, (uint8_t*)p8, &n);
-  if (rc) return throwSail(env, "sail_denoise", rc, h->ctx);
+  const int rc = demod ? sail_denoise_albedo(h->ctx, &p, amin, (float*)pf, nullptr, (uint8_t*)p8, &n)
+                       : sail_denoise(h->ctx, &p, (float*)pf, nullptr, (uint8_t*)p8, &n);
+  if (rc) return throwSail(env, demod ? "sail_denoise_albedo" : "sail_denoise", rc, h->ctx);
   napi_value out, inf, passes;
   NAPI_OK(napi_create_object(env, &out));
   NAPI_OK(napi_create_object(env, &inf));
@@ -712,11 +736,11 @@ napi_value TemporalFilterDefaults(napi_env env, napi_callback_info info) {
   napi_set_named_property(env, out, "gamma", num(env, p.gamma_c));
   return out;
 }
-// (ctx, iterations, sigmaL, sigmaX, minHist, display, gamma, wantU8) -> {rgba, rgba8?, info}; a parameter that is
-// undefined or null keeps sail_temporal_filter_defaults' value
+// (ctx, iterations, sigmaL, sigmaX, minHist, display, gamma, wantU8[, amin]) -> {rgba, rgba8?, info}; a parameter that is
+// undefined or null keeps sail_temporal_filter_defaults' value; with amin, sail_temporal_filter_albedo
 napi_value TemporalFilter(napi_env env, napi_callback_info info) {
-  napi_value a[8];
-  if (!args(env, info, 8, a)) return nullptr;
+  napi_value a[9];
+  if (!argsUpTo(env, info, 8, 9, a)) return nullptr;
   Handle* h;
   if (!getHandle(env, a[0], &h)) return nullptr;
   sail_tfilter_params p;
@@ -742,9 +766,13 @@ napi_value TemporalFilter(napi_env env, napi_callback_info info) {
   void *pf = nullptr, *p8 = nullptr;
   napi_value f = makeTyped(env, napi_float32_array, np, 4, &pf), u8 = nullptr;
   if (wantU8) u8 = makeTyped(env, napi_uint8_array, np, 1, &p8);
+  bool demod = false;
+  float amin = 0.0f;
+  if (!optionalAmin(env, a[8], &demod, &amin)) return nullptr;
   sail_tfilter_info n;
-  const int rc = sail_temporal_filter(h->ctx, &p, (float*)pf, nullptr, (uint8_t*)p8, &n);
-  if (rc) return throwSail(env, "sail_temporal_filter", rc, h->ctx);
+  const int rc = demod ? sail_temporal_filter_albedo(h->ctx, &p, amin, (float*)pf, nullptr, (uint8_t*)p8, &n)
+                       : sail_temporal_filter(h->ctx, &p, (float*)pf, nullptr, (uint8_t*)p8, &n);
+  if (rc) return throwSail(env, demod ? "sail_temporal_filter_albedo" : "sail_temporal_filter", rc, h->ctx);
   napi_value out, inf, passes;
   NAPI_OK(napi_create_object(env, &out));
   NAPI_OK(napi_create_object(env, &inf));
@@ -761,6 +789,59 @@ napi_value TemporalFilter(napi_env env, napi_callback_info info) {
   if (wantU8) NAPI_OK(napi_set_named_property(env, out, "rgba8", u8));
   NAPI_OK(napi_set_named_property(env, out, "info", inf));
   return out;
+}
+// (ctx, mvp f64[16] row-major, eye f32[3], grid) -> {rgba: Float32Array (4 per pixel), hitPixels, partialPixels, grid,
+// kernelMs}: the albedo map of a view, kept by the context (sail_albedo)
+napi_value Albedo(napi_env env, napi_callback_info info) {
+  napi_value a[4];
+  if (!args(env, info, 4, a)) return nullptr;
+  Handle* h;
+  double* m;
+  float* eye;
+  int grid = 0;
+  if (!getHandle(env, a[0], &h) || !viewArgs(env, a[1], a[2], &m, &eye) || !getInt(env, a[3], &grid)) return nullptr;
+  void* pf = nullptr;
+  napi_value f = makeTyped(env, napi_float32_array, (size_t)h->W * h->H * 4, 4, &pf);
+  sail_albedo_info n;
+  const int rc = sail_albedo(h->ctx, m, eye, grid, (float*)pf, &n);
+  if (rc) return throwSail(env, "sail_albedo", rc, h->ctx);
+  napi_value out;
+  NAPI_OK(napi_create_object(env, &out));
+  NAPI_OK(napi_set_named_property(env, out, "rgba", f));
+  napi_set_named_property(env, out, "hitPixels", num(env, (double)n.hit_pixels));
+  napi_set_named_property(env, out, "partialPixels", num(env, (double)n.partial_pixels));
+  napi_set_named_property(env, out, "grid", num(env, n.grid));
+  napi_set_named_property(env, out, "kernelMs", num(env, n.kernel_ms));
+  return out;
+}
+// (ctx, map f32[W H 4], mvp, eye): install a caller's albedo map for a view (sail_albedo_load)
+napi_value AlbedoLoad(napi_env env, napi_callback_info info) {
+  napi_value a[4];
+  if (!args(env, info, 4, a)) return nullptr;
+  Handle* h;
+  float* map;
+  size_t len;
+  double* m;
+  float* eye;
+  if (!getHandle(env, a[0], &h) || !getArray(env, a[1], napi_float32_array, &map, &len) ||
+      !viewArgs(env, a[2], a[3], &m, &eye))
+    return nullptr;
+  if (len < (size_t)h->W * h->H * 4) { napi_throw_range_error(env, nullptr, "the map needs W * H * 4 floats"); return nullptr; }
+  const int rc = sail_albedo_load(h->ctx, map, m, eye);
+  if (rc) return throwSail(env, "sail_albedo_load", rc, h->ctx);
+  return undef(env);
+}
+// (ctx) -> Float32Array (4 per pixel): the context's albedo map (sail_albedo_read)
+napi_value AlbedoRead(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  if (!args(env, info, 1, a)) return nullptr;
+  Handle* h;
+  if (!getHandle(env, a[0], &h)) return nullptr;
+  void* pf = nullptr;
+  napi_value f = makeTyped(env, napi_float32_array, (size_t)h->W * h->H * 4, 4, &pf);
+  const int rc = sail_albedo_read(h->ctx, (float*)pf);
+  if (rc) return throwSail(env, "sail_albedo_read", rc, h->ctx);
+  return f;
 }
 // (ctx, timeoutMs) -> whether the scene's run-time kernel is loaded (sail_kernel_ready; -1 waits for its build)
 napi_value KernelReady(napi_env env, napi_callback_info info) {
@@ -931,6 +1012,9 @@ napi_value Init(napi_env env, napi_value exports) {
       {"temporalReadMoments", 0, TemporalReadMoments, 0, 0, 0, napi_enumerable, 0},
       {"temporalFilterDefaults", 0, TemporalFilterDefaults, 0, 0, 0, napi_enumerable, 0},
       {"temporalFilter", 0, TemporalFilter, 0, 0, 0, napi_enumerable, 0},
+      {"albedo", 0, Albedo, 0, 0, 0, napi_enumerable, 0},
+      {"albedoLoad", 0, AlbedoLoad, 0, 0, 0, napi_enumerable, 0},
+      {"albedoRead", 0, AlbedoRead, 0, 0, 0, napi_enumerable, 0},
       {"kernelReady", 0, KernelReady, 0, 0, 0, napi_enumerable, 0},
       {"kernelInfo", 0, KernelInfo, 0, 0, 0, napi_enumerable, 0},
       {"pick", 0, Pick, 0, 0, 0, napi_enumerable, 0},

@@ -22,10 +22,14 @@
 // tracked as well and temporalFilter({...}) runs the a-trous passes over the resolved picture (sail_temporal_filter).
 // With temporal: {objects: true | {histCap}} a drag keeps the history too: updateObjects hands the library each row's
 // translation (sail_move_objects) and the next frame reprojects the moved object's pixels from where they were.
+// albedo(scene, {grid}) is the albedo map of a view (sail_albedo); denoise({albedo: true}) and
+// temporalFilter({albedo: true}) filter the picture divided by it, so that procedural textures survive
+// (sail_denoise_albedo / sail_temporal_filter_albedo); the map is computed when the option is set and it is stale.
 const native = require('./native');
 const { filterConfig } = require('./filter');
 
 const MAXBOUNCES = 5;  // define.glsl:6
+const ALBEDO_AMIN = 0.01;  // SAIL_ALBEDO_AMIN_DEFAULT: a guard, not a tuned value
 const ACCUM = { sum: 0, mix: 1, compat8: 2 };
 const SHAPE_ID = { cube: 1, sphere: 2, rectangle: 3, cone: 4, cylinder: 5, disk: 6, hyperboloid: 7, paraboloid: 8, cornellbox: 9 };
 const MAT_ID = { matte: 1, mirror: 2, metal: 3, glass: 4 };
@@ -94,6 +98,10 @@ class Renderer {
     this.pixels = null;
     this.n = 0;
     this._temporalView = false;  // a temporalBegin has made a view current since the last scene change
+    // the albedo map (sail_albedo): the view last rendered or begun, and the view and grid the context's map was made for
+    // (null: none, or the rows have changed since)
+    this._view = null;
+    this._albedoKey = null;
   }
 
   update(scene) {
@@ -105,9 +113,11 @@ class Renderer {
     this.n = s.n;
     scene.sampleCount = 0;
     this._temporalView = false;  // a new scene drops the temporal state
+    this._albedoKey = null;      // and the albedo map
   }
 
   updateObjects(scene) {
+    this._albedoKey = null;  // new rows drop the albedo map, whichever call brings them
     if (this.objectHistCap !== null) {
       // the motion first: serializeObjects applies and zeroes it. The current view stays; the _restart that follows begins
       // the same view again with the motion pending
@@ -120,9 +130,12 @@ class Renderer {
   }
 
   _mvp(scene) { return rowMajor(scene.mat); }
+  // remember the view the frame belongs to: denoise({albedo}) and temporalFilter({albedo}) compute the map for it
+  _see(scene) { this._view = { mvp: this._mvp(scene), eye: Float32Array.from(scene.eye.elements) }; }
 
   // the frame restarts (the reference's textureWeight 0); with the temporal option the new view takes over the history
   _restart(scene) {
+    this._see(scene);
     this.lib.reset(this.ctx);
     if (this.temporal) this.temporalBegin(scene);
   }
@@ -189,7 +202,10 @@ class Renderer {
   // defaults (4 passes, sigmaL 1, sigmaX 0.2, display 'color', gamma 2.2); display ('color' | 'gamma' | 'tonemapping')
   // asks for rgba8 as well. Returns {rgba: Float32Array (the denoised mean, row 0 = bottom), rgba8?, info: {k, kMark,
   // nonfinite, iterations, kernelMs, passMs}}. The frame itself is not changed.
-  denoise({ iterations, sigmaL, sigmaX, display, gamma } = {}) {
+  // albedo: true, or {amin, grid}: the frame is divided by the albedo map of its view before the filter and multiplied
+  // by it afterwards, so that procedural textures survive (sail_denoise_albedo); the map is computed here when the
+  // context has none for this view and grid.
+  denoise({ iterations, sigmaL, sigmaX, display, gamma, albedo } = {}) {
     if (!this.aov) throw new Error('Renderer.denoise reads the normal and position AOVs: create the Renderer with aov: true');
     const kinds = { color: 0, gamma: 1, tonemapping: 2 };
     let kind;
@@ -197,7 +213,30 @@ class Renderer {
       kind = typeof display === 'number' ? display : kinds[display];
       if (kind === undefined) throw new Error(`Renderer.denoise: unknown display '${display}' (color | gamma | tonemapping)`);
     }
+    if (albedo) return this.lib.denoise(this.ctx, iterations, sigmaL, sigmaX, kind, gamma, display !== undefined, this._albedoFor(albedo));
     return this.lib.denoise(this.ctx, iterations, sigmaL, sigmaX, kind, gamma, display !== undefined);
+  }
+
+  // The albedo map of a view (sail_albedo): the mean surface colour of the first hits of grid x grid sub-pixel rays per
+  // pixel (grid 1..4; 2 is a policy value), kept by the context for the demodulated filters. `scene` left out: the view
+  // last rendered. Returns {rgba: Float32Array (.w: the rays that hit; (1, 1, 1, 0) where none did), hitPixels,
+  // partialPixels, grid, kernelMs}.
+  albedo(scene, { grid = 2 } = {}) {
+    if (scene) this._see(scene);
+    if (!this._view) throw new Error('Renderer.albedo: no view yet (pass the scene, or render first)');
+    this._albedoKey = null;
+    const r = this.lib.albedo(this.ctx, this._view.mvp, this._view.eye, grid);
+    this._albedoKey = this._viewKey(grid);
+    return r;
+  }
+  _viewKey(grid) { return `${grid}|${Array.from(this._view.mvp).join(',')}|${Array.from(this._view.eye).join(',')}`; }
+  // the amin of a demodulated call; computes the map first when it is stale
+  _albedoFor(opt) {
+    const o = opt === true ? {} : opt;
+    const grid = o.grid === undefined ? 2 : o.grid;
+    if (!this._view) throw new Error('Renderer: the albedo option needs a rendered view');
+    if (this._albedoKey !== this._viewKey(grid)) this.albedo(null, { grid });
+    return o.amin === undefined ? ALBEDO_AMIN : o.amin;
   }
 
   // The G-buffer pass of the scene's view (sail_gbuffer): {id: Int32Array (object row of each pixel's first hit, -1 = miss),
@@ -208,6 +247,7 @@ class Renderer {
   // "The camera is now at the scene's view" (sail_temporal_begin): the view that was current is committed as the history,
   // which is reprojected into the new view. Returns {k, hitPixels, historyPixels, nonfinite, kernelMs, passMs}.
   temporalBegin(scene) {
+    this._see(scene);
     const t = this.temporal || {};
     this._temporalView = false;  // a begin that throws leaves no current view: image() then shows the bare frame
     const info = this.lib.temporalBegin(this.ctx, this._mvp(scene), Float32Array.from(scene.eye.elements), t.cap, t.posTol);
@@ -232,7 +272,8 @@ class Renderer {
   // current view. Options left out keep the library's defaults (4 passes, sigmaL 4, sigmaX 0.2, minHist 4, display
   // 'color', gamma 2.2); display asks for rgba8 as well. Returns {rgba: Float32Array (row 0 = bottom), rgba8?, info: {k,
   // temporalPixels, spatialPixels, nonfinite, iterations, kernelMs, passMs}}. Neither the frame nor the history changes.
-  temporalFilter({ iterations, sigmaL, sigmaX, minHist, display, gamma } = {}) {
+  // albedo: true, or {amin, grid}: as in denoise (sail_temporal_filter_albedo); the history stays un-demodulated.
+  temporalFilter({ iterations, sigmaL, sigmaX, minHist, display, gamma, albedo } = {}) {
     if (!this.aov)
       throw new Error('Renderer.temporalFilter reads the normal and position AOVs: create the Renderer with aov: true');
     if (!(this.temporal && this.temporal.moments))
@@ -243,6 +284,8 @@ class Renderer {
       kind = typeof display === 'number' ? display : kinds[display];
       if (kind === undefined) throw new Error(`Renderer.temporalFilter: unknown display '${display}' (color | gamma | tonemapping)`);
     }
+    if (albedo)
+      return this.lib.temporalFilter(this.ctx, iterations, sigmaL, sigmaX, minHist, kind, gamma, display !== undefined, this._albedoFor(albedo));
     return this.lib.temporalFilter(this.ctx, iterations, sigmaL, sigmaX, minHist, kind, gamma, display !== undefined);
   }
 
