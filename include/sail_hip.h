@@ -122,7 +122,10 @@ enum sail_debug_option {
    * SAIL_DEBUG_CULL_MIN_PRIMS primitives) that the precompiled Cornell and room kernels do not cover, 8 those as a
    * room-family kernel (SAIL_JIT_MODE_ROOM) instead of a plain one, 4 scenes of the room kernel's set, 2 pre-cull-path
    * scenes, 16 every flat-path scene of at most 8 primitives compiled for its rows too (their count and shape types).
-   * 0: the precompiled kernels only. Same results [27 = 1 + 2 + 8 + 16; measured in profiles/r04_jit_*.jsonl] */
+   * 32 the value kernel (SAIL_DEBUG_JIT_VALUES_AFTER) of a scene of at most 3 rows in the row-shading form: a wave whose
+   * paths all hit one quiet row (no emission, a light term of exactly +0) shades in that row's branch, on the row's
+   * material constants and without touching the radiance (profiles/rowshade.jsonl).
+   * 0: the precompiled kernels only. Same results [59 = 1 + 2 + 8 + 16 + 32; measured in profiles/r04_jit_*.jsonl] */
   SAIL_DEBUG_JIT = 9,
   /* how long (ms) a launch waits for the scene's run-time kernel while it is still being built in the background; -1:
    * until it is built. Meanwhile the precompiled kernel of the scene's set renders, with the same results [0: never
@@ -643,6 +646,10 @@ int sail_jit_prebuild(const float* objects, int n, const float* texparams, int t
  * *defs_len (may be NULL) = the prefix's size with its terminator; copied into defs when *defs_len on entry is enough. */
 int sail_jit_value_key(const float* objects, int n, const float* texparams, int tn, const sail_plugins* plugins,
                        const char* arch, uint64_t* key, char* defs, size_t* defs_len);
+/* The same for a context with SAIL_DEBUG_JIT = jit (< 0: the default switches): the key and source prefix of its value
+ * kernel (value != 0) or of the run-time kernel under it (value == 0; the types kernel). */
+int sail_jit_spec_key(const float* objects, int n, const float* texparams, int tn, const sail_plugins* plugins,
+                      const char* arch, int jit, int value, uint64_t* key, char* defs, size_t* defs_len);
 /* 1 when a context that rendered `settled` samples since its rows last changed asks for its value kernel under
  * SAIL_DEBUG_JIT_VALUES_AFTER = after (0: at once, < 0: never), else 0 */
 int sail_plan_settle(uint64_t settled, int after);

@@ -48,7 +48,7 @@ EXPORTS = (
     "sail_prim_bounds", "sail_math_probe", "sail_pick", "sail_kernel_name", "sail_filter_ms",
     "sail_abi_version", "sail_accum_parts", "sail_save_accum", "sail_load_accum", "sail_jit_compile",
     "sail_get_kernel_info", "sail_kernel_ready", "sail_set_jit_cache", "sail_jit_prebuild",
-    "sail_jit_value_key", "sail_plan_settle", "sail_jit_resident",
+    "sail_jit_value_key", "sail_jit_spec_key", "sail_plan_settle", "sail_jit_resident",
     "sail_plan_reduce", "sail_plan_keep", "sail_plan_load_part", "sail_plan_last_bounce",
     "sail_noise_mark", "sail_noise_estimate", "sail_plan_until", "sail_render_until",
     "sail_denoise_defaults", "sail_denoise",
@@ -225,6 +225,9 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
                                              ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]),
         "sail_jit_value_key": (ctypes.c_int, [f32p, ctypes.c_int, f32p, ctypes.c_int, ctypes.POINTER(Plugins), ctypes.c_char_p,
                                               ctypes.POINTER(ctypes.c_uint64), ctypes.c_char_p, ctypes.POINTER(ctypes.c_size_t)]),
+        "sail_jit_spec_key": (ctypes.c_int, [f32p, ctypes.c_int, f32p, ctypes.c_int, ctypes.POINTER(Plugins), ctypes.c_char_p,
+                                             ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64), ctypes.c_char_p,
+                                             ctypes.POINTER(ctypes.c_size_t)]),
         "sail_plan_settle": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_int]),
         "sail_jit_resident": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
         "sail_plan_reduce": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
@@ -517,9 +520,12 @@ def jit_prebuild(sc: dict, arch: str = "gfx950", cache_dir: Optional[str] = None
     return bool(built.value)
 
 
-def jit_value_key(sc: dict, arch: str = "gfx950"):
+def jit_value_key(sc: dict, arch: str = "gfx950", jit: Optional[int] = None, value: bool = True):
     """Host-only, nothing is compiled: (key, source prefix) of the value kernel a default context derives for scene `sc`
-    once it has settled; its cache object is <cache dir>-values/<key>.co. (None, "") when the scene gets no value kernel."""
+    once it has settled; its cache object is <cache dir>-values/<key>.co. (None, "") when the scene gets no value kernel.
+    jit: the context's DEBUG_JIT switches instead of the defaults; value=False: the types kernel under the value kernel."""
+    if jit is not None or not value:
+        return _jit_spec_key(sc, arch, -1 if jit is None else jit, value)
     lib = load()
     o, t = _f32(sc["objects"]), _f32(sc["texparams"])
     pl = Plugins(*[int(m) for m in plugin_masks(sc["plugins"])])
@@ -530,6 +536,24 @@ def jit_value_key(sc: dict, arch: str = "gfx950"):
                                     buf, ctypes.byref(size))
         if rc:
             raise SailError(f"sail_jit_value_key: {rc}: {lib.sail_last_error(None).decode()}")
+        if size.value == 0:
+            return None, ""
+        if buf is None:
+            buf = ctypes.create_string_buffer(size.value)
+    return f"{key.value:016x}", buf.value.decode()
+
+
+def _jit_spec_key(sc: dict, arch: str, jit: int, value: bool):
+    lib = load()
+    o, t = _f32(sc["objects"]), _f32(sc["texparams"])
+    pl = Plugins(*[int(m) for m in plugin_masks(sc["plugins"])])
+    key, size = ctypes.c_uint64(0), ctypes.c_size_t(0)
+    buf = None
+    for _ in range(2):  # the size, then the text
+        rc = lib.sail_jit_spec_key(_ptr(o), sc["n"], _ptr(t), sc["tn"], ctypes.byref(pl), arch.encode(), int(jit), int(value),
+                                   ctypes.byref(key), buf, ctypes.byref(size))
+        if rc:
+            raise SailError(f"sail_jit_spec_key: {rc}: {lib.sail_last_error(None).decode()}")
         if size.value == 0:
             return None, ""
         if buf is None:

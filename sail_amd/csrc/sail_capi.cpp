@@ -172,7 +172,7 @@ struct sail_ctx {
   int forceGeneric = 0;  // SAIL_FORCE_GENERIC=1: always launch the all-plugin kernel (tests)
   int forceGroups = 0;   // SAIL_SAMPLE_GROUPS=g: fixed sample-group count (tests); 0 = by occupancy
   int wavefront = 0;     // SAIL_DEBUG_WAVEFRONT: the pre-cull path by the wavefront split (study)
-  int jit = 27;  // SAIL_DEBUG_JIT bits: which scenes get a run-time kernel (jitKernels; instrumented in the phase build)
+  int jit = 59;  // SAIL_DEBUG_JIT bits: which scenes get a run-time kernel (jitKernels; instrumented in the phase build)
   // The scene's run-time kernel (refreshJit): its spec, and whether it is still being built, loaded or failed. Until it
   // is loaded the precompiled kernel of the scene's set serves (same results); a launch waits up to jitWait ms for it
   // (SAIL_DEBUG_JIT_WAIT; -1 until it is built).
@@ -369,7 +369,8 @@ int jitNtFor(int mode, int kernelSet) {
 }
 // The run-time kernel spec of the context's scene under its switches, or false when none applies.
 // SAIL_DEBUG_JIT bits (include/sail_hip.h): 1 flat scenes outside the Cornell and room sets, 2 pre-cull scenes, 4 room-set
-// scenes, 8 the flat scenes of bit 1 in the room form, 16 flat scenes compiled for their rows as well (any flat scene).
+// scenes, 8 the flat scenes of bit 1 in the room form, 16 flat scenes compiled for their rows as well (any flat scene),
+// 32 the row-shading form of the value kernel (valueSpecFor).
 bool jitSpecFor(const sail_ctx* c, SailJitSpec* out, int* mode) {
   if (!c->jit || !c->haveScene || c->forceGeneric) return false;
   const int set = kernelSetFor(c);
@@ -432,12 +433,16 @@ void dropValues(sail_ctx* c) {
 // Whether the value kernel of a scene that rendered `settled` samples since its rows changed is asked for now
 // (sail_plan_settle; after: SAIL_DEBUG_JIT_VALUES_AFTER)
 bool settledFor(uint64_t settled, int after) { return after >= 0 && settled >= (uint64_t)after; }
+void lastBounceRows(const std::vector<SailPrim>& prims, const float* tp, int tn, uint32_t matMask, bool lights,
+                    uint32_t* quietRows, int* skipSort);  // below
 // The value spec of a types spec: the flat form compiled for rows, with a texParams table small enough to compile in.
 // Scenes of the Cornell plugin set only (cubes, spheres, the box; matte and mirror; no textures, no lights): the form
 // that was measured and that the parity tests run with constant rows. A flat-form kernel of a wider set (SAIL_DEBUG_JIT
 // without bit 8) would read its light sampler's geometry rows, textures and a full texParams table through the constant
 // tables too, which no test covers: it keeps its types kernel.
-bool valueSpecFor(const SailJitSpec& types, const std::vector<uint32_t>& rowWords, const float* tp, int tn, SailJitSpec* out) {
+// jit: the SAIL_DEBUG_JIT switches; bit 32 gives scenes of at most kSailJitRowRecordMax rows the row-shading form
+// (SAIL_JIT_ROWSHADE in sail_trace.hip).
+bool valueSpecFor(const SailJitSpec& types, const std::vector<uint32_t>& rowWords, const float* tp, int tn, int jit, SailJitSpec* out) {
   const bool cornellSet = (types.ks & ~SAIL_KSET_CORNELL_SHAPES) == 0 && (types.km & ~SAIL_KSET_CORNELL_MATS) == 0 &&
                           (types.kt & ~SAIL_KSET_CORNELL_TEX) == 0 && types.kl == 0;
   if (!cornellSet || types.mode != SAIL_JIT_MODE_FLAT || types.rows <= 0 || types.tn != 0 || tn < 0 || tn > kSailJitMaxFlatTp ||
@@ -447,6 +452,21 @@ bool valueSpecFor(const SailJitSpec& types, const std::vector<uint32_t>& rowWord
   out->rowWords = rowWords;
   out->tpWords.resize((size_t)tn * 16);
   if (tn > 0) memcpy(out->tpWords.data(), tp, sizeof(float) * 16 * (size_t)tn);
+  out->rowForm = out->rowShade = out->rowQuiet = 0;
+  if ((jit & 32) && types.rows <= kSailJitRowRecordMax) {
+    out->rowForm = 1;
+    // The rows that get a shading copy of their own: the quiet ones (lastBounceRows, for a kernel without a light plugin:
+    // cornellSet), whose copies also leave the radiance alone. Measured on C2: a copy
+    // for every row lost 4.8 % (VGPR spills 22 -> 50), copies for the quiet rows gained 4.5 %, and 6.7 % without the
+    // radiance round trip; a copy for the emitting row on top of those gained less (3.9 %).
+    std::vector<SailPrim> prims((size_t)types.rows);
+    memcpy(prims.data(), rowWords.data(), sizeof(SailPrim) * prims.size());
+    uint32_t quiet = 0;
+    int skip = 0;
+    lastBounceRows(prims, tp, tn, types.km, false, &quiet, &skip);
+    out->rowShade = (int)(quiet & ((1u << types.rows) - 1u));
+    out->rowQuiet = out->rowShade;
+  }
   return true;
 }
 // Ask for the scene's value kernel once it has settled (after every refreshJit, and between and after launches): the build
@@ -454,7 +474,7 @@ bool valueSpecFor(const SailJitSpec& types, const std::vector<uint32_t>& rowWord
 void refreshValues(sail_ctx* c) {
   if (!c->subs.empty() || c->valHave || !c->jitHave || !settledFor(c->settled, c->jitValuesAfter)) return;
   SailJitSpec spec;
-  if (!valueSpecFor(c->jitSpec, c->rowWords, c->tpRows.data(), c->tn, &spec)) return;
+  if (!valueSpecFor(c->jitSpec, c->rowWords, c->tpRows.data(), c->tn, c->jit, &spec)) return;
   sail_jit_hold(c->device, spec, +1);
   c->valHave = true;
   c->valSpec = spec;
@@ -1608,7 +1628,11 @@ int sail_set_debug(sail_ctx* c, int option, int value) {
     case SAIL_DEBUG_CULL_FMA: c->cullFma = value; break;
     case SAIL_DEBUG_SAMPLE_GROUPS: c->forceGroups = value; break;
     case SAIL_DEBUG_WAVEFRONT: c->wavefront = value; break;
-    case SAIL_DEBUG_JIT: c->jit = value; break;
+    case SAIL_DEBUG_JIT:
+      // the value kernel's other form, derived anew below (refreshValues); the rows did not move: the count stays
+      if ((c->jit ^ value) & 32) { const uint64_t s = c->settled; dropValues(c); c->settled = s; }
+      c->jit = value;
+      break;
     case SAIL_DEBUG_JIT_NT:
       if (value != 0 && value != 128 && value != 256 && value != 512 && value != 1024)
         return fail(c, SAIL_E_INVALID, "sail_set_debug: threads per workgroup must be 0 (default), 128, 256, 512 or 1024");
@@ -3133,7 +3157,7 @@ int sail_jit_prebuild(const float* objects, int n, const float* texparams, int t
     if (sail_jit_code_to_dir(arch, spec, dir, &err)) return fail(nullptr, SAIL_E_INVALID, "sail_jit_prebuild: %s", err.c_str());
     // and the value kernel a context loads once the scene has settled, where the spec has one
     SailJitSpec vspec;
-    if (valueSpecFor(spec, rowWords, texparams, tn, &vspec) && sail_jit_code_to_dir(arch, vspec, dir, &err))
+    if (valueSpecFor(spec, rowWords, texparams, tn, t.jit, &vspec) && sail_jit_code_to_dir(arch, vspec, dir, &err))
       return fail(nullptr, SAIL_E_INVALID, "sail_jit_prebuild: %s", err.c_str());
     if (!cornell) break;
   }
@@ -3151,10 +3175,16 @@ int sail_jit_resident(int* code_objects, int* modules) {
 
 int sail_jit_value_key(const float* objects, int n, const float* texparams, int tn, const sail_plugins* plugins,
                        const char* arch, uint64_t* key, char* defs, size_t* defs_len) {
+  return sail_jit_spec_key(objects, n, texparams, tn, plugins, arch, -1, 1, key, defs, defs_len);
+}
+
+int sail_jit_spec_key(const float* objects, int n, const float* texparams, int tn, const sail_plugins* plugins,
+                      const char* arch, int jit, int value, uint64_t* key, char* defs, size_t* defs_len) {
   if (n < 1 || tn < 1 || !objects || !texparams || !plugins || !arch || !key)
-    return fail(nullptr, SAIL_E_INVALID, "sail_jit_value_key: bad arguments");
-  // as sail_jit_prebuild: the spec a context with the product's defaults derives, without a device
+    return fail(nullptr, SAIL_E_INVALID, "sail_jit_spec_key: bad arguments");
+  // as sail_jit_prebuild: the spec a context with these switches (else the product's defaults) derives, without a device
   sail_ctx t;
+  if (jit >= 0) t.jit = jit;
   t.plugins = *plugins;
   t.n = n; t.tn = tn;
   t.haveScene = true;
@@ -3168,12 +3198,13 @@ int sail_jit_value_key(const float* objects, int n, const float* texparams, int 
   SailJitSpec spec, vspec;
   int mode = 0;
   *key = 0;
-  if (!jitSpecFor(&t, &spec, &mode) || !valueSpecFor(spec, rowWords, texparams, tn, &vspec)) {
+  if (!jitSpecFor(&t, &spec, &mode) || (value && !valueSpecFor(spec, rowWords, texparams, tn, t.jit, &vspec))) {
     if (defs_len) *defs_len = 0;
-    return SAIL_OK;  // the scene gets no value kernel
+    return SAIL_OK;  // the scene gets no such kernel
   }
   std::string text, err;
-  if (sail_jit_key(arch, vspec, key, &text, &err)) return fail(nullptr, SAIL_E_INVALID, "sail_jit_value_key: %s", err.c_str());
+  if (sail_jit_key(arch, value ? vspec : spec, key, &text, &err))
+    return fail(nullptr, SAIL_E_INVALID, "sail_jit_spec_key: %s", err.c_str());
   if (defs_len) {
     const size_t have = *defs_len;
     *defs_len = text.size() + 1;

@@ -56,7 +56,7 @@ int sailJitThreads(const SailJitSpec& s) { return s.nt ? s.nt : (s.mode == 1 ? 1
 bool sailJitSpecEqual(const SailJitSpec& a, const SailJitSpec& b) {
   const auto t = [](const SailJitSpec& x) {
     return std::tie(x.ks, x.km, x.kt, x.kl, x.mode, x.waves, x.rows, x.ldsFit, x.tn, x.ns, x.nt, x.types[0], x.types[1], x.types[2],
-                    x.types[3], x.types[4], x.types[5], x.types[6], x.types[7], x.rowWords, x.tpWords);
+                    x.types[3], x.types[4], x.types[5], x.types[6], x.types[7], x.rowWords, x.tpWords, x.rowForm, x.rowShade, x.rowQuiet);
   };
   return t(a) == t(b);
 }
@@ -70,7 +70,7 @@ struct Key {
   bool operator<(const Key& o) const {
     const auto t = [](const SailJitSpec& x) {
       return std::tie(x.ks, x.km, x.kt, x.kl, x.mode, x.waves, x.rows, x.ldsFit, x.tn, x.ns, x.nt, x.types[0], x.types[1], x.types[2],
-                      x.types[3], x.types[4], x.types[5], x.types[6], x.types[7], x.rowWords, x.tpWords);
+                      x.types[3], x.types[4], x.types[5], x.types[6], x.types[7], x.rowWords, x.tpWords, x.rowForm, x.rowShade, x.rowQuiet);
     };
     return t(s) < t(o.s);
   }
@@ -114,7 +114,9 @@ std::string defsFor(const SailJitSpec& sp) {
       for (size_t i = 0; i < w.size(); i++) { snprintf(b, sizeof b, i ? ", 0x%08xu" : "0x%08xu", w[i]); s += b; }
       return s.empty() ? std::string("0u") : s;
     };
-    vals = "#define SAIL_JIT_ROWVALS 1\n#define SAIL_JIT_TPN " + std::to_string(sp.tpWords.size() / 16) +
+    vals = (sp.rowForm ? "#define SAIL_JIT_ROWSHADE " + std::to_string(sp.rowShade) + "\n#define SAIL_JIT_ROWQUIET " +
+                             std::to_string(sp.rowQuiet) + "\n"
+                       : std::string()) + "#define SAIL_JIT_ROWVALS 1\n#define SAIL_JIT_TPN " + std::to_string(sp.tpWords.size() / 16) +
            "\n#define SAIL_JIT_ROW_WORDS " + list(sp.rowWords) + "\n#define SAIL_JIT_TP_WORDS " + list(sp.tpWords) + "\n";
   }
   char defs[768];

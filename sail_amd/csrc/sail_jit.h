@@ -7,6 +7,7 @@
 
 constexpr int kSailJitMaxRows = 8;  // scenes of at most this many rows can be compiled for their rows (flat path)
 constexpr int kSailJitMaxFlatTp = 32;  // flat forms copy texParams tables of at most this many rows into LDS
+constexpr int kSailJitRowRecordMax = 3;  // value kernels of at most this many rows: a hit record per row (sail_trace.hip kRowRecordMax)
 struct SailJitSpec {
   uint32_t ks = 0, km = 0, kt = 0, kl = 0;  // plugin masks: shapes, materials, textures, lights
   int mode = 0;                             // sail_jit_mode (include/sail_hip.h): 0 flat, 1 pre-cull, 2 room family
@@ -22,6 +23,12 @@ struct SailJitSpec {
   // rows; may be none). Both empty: the types kernel. Compared and keyed as words, never as floats: +0 / -0 and two NaN
   // payloads are different kernels.
   std::vector<uint32_t> rowWords, tpWords;
+  // rowForm 1: a value kernel of at most kSailJitRowRecordMax rows in the row-shading form (SAIL_JIT_ROWSHADE in
+  // sail_trace.hip; SAIL_DEBUG_JIT bit 32). rowShade: the rows (bit i: row i) whose row-uniform waves run the rest of the
+  // bounce in their row's branch, on the row's material constants; rowQuiet: those of them whose copy leaves the
+  // radiance alone (quiet rows, sail_capi.cpp lastBounceRows). Both 0: the kernel is the plain value kernel's code.
+  // All 0 in every types spec.
+  int rowForm = 0, rowShade = 0, rowQuiet = 0;
 };
 bool sailJitSpecEqual(const SailJitSpec& a, const SailJitSpec& b);
 int sailJitThreads(const SailJitSpec& s);  // threads per workgroup of the spec's kernels

@@ -212,6 +212,17 @@ constexpr TpTabC kTpTab = __builtin_bit_cast(TpTabC, kTpW);
 #define SAIL_ROWVALS 0
 #define PRIM(c, i) constRow<SailPrim>((c).prims, (i))
 #endif
+// Row shading (SAIL_JIT_ROWSHADE = a mask of rows, in a value kernel of at most kRowRecordMax rows; SAIL_DEBUG_JIT bit
+// 32): a row-uniform wave of a row in the mask runs the rest of its bounce -- AOV store, radiance update, BSDF sample,
+// next ray -- inside its row's branch of the hit record (bounceU), so that the row's material category, matRow,
+// texParams values, rev and emission words are constants of that copy of the shading too. Mixed waves and the other
+// rows' waves keep the one generic body. The host names the quiet rows (sail_capi.cpp valueSpecFor: a copy for every
+// row measured -4.8 % on C2, copies for the quiet rows +6.7 %); a mask of 0 is the plain value kernel's text.
+#if SAIL_ROWVALS && defined(SAIL_JIT_ROWSHADE) && SAIL_JIT_ROWSHADE
+#define SAIL_ROWSHADE 1
+#else
+#define SAIL_ROWSHADE 0
+#endif
 
 D V3 P3(const SailPrim& p, int k) { return v3(p.a[k], p.a[k + 1], p.a[k + 2]); }
 D float TP(const Ctx& c, int row, int col) {
@@ -1210,6 +1221,52 @@ D Hit hitRecordU(const Ctx& c, const Ray& r, const Sweep& sw) {
   }
   return hitRecord<RECOMP_HL, BOXU>(c, r, sw);
 }
+#if SAIL_ROWSHADE
+static_assert(kRows <= kRowRecordMax, "row shading rides on the per-row hit records");
+// rest(hit record): the remainder of the bounce. A row-uniform wave whose row is in kRowShadeMask runs it in the branch
+// of its row, behind that row's record (the same functions on the same operands in the same order: only operands become
+// constants); every other wave runs the one generic copy behind its record(s), as after hitRecordU.
+constexpr unsigned kRowShadeMask = SAIL_JIT_ROWSHADE;  // bit i: row i has a shading copy of its own
+// Quiet rows (SAIL_JIT_ROWQUIET, the host's lastBounceRows class for a kernel without a light plugin): the emission words
+// are +0 and the row is not a matte, or a Lambertian one of constant colour(s) with finite f = (kd * sc) / pi. A hit on
+// such a row updates the radiance by e + (emission + direct) * throughput with emission + direct = +0 + fma(f, 0, 0)
+// = +0 exactly, at every bounce (shadeBounce and shadeLast make the same update). That sum is e, bit for bit:
+//  * the throughput is finite: it starts at 1 and is only ever multiplied by vclamp01 results, which lie in [0, 1]
+//    (clamp_ of a NaN is 0), so +0 * throughput is +0 or -0, never NaN;
+//  * e is never -0: it starts at +0, every later value is a sum, and a sum is -0 only if both terms are -0;
+//  * x + (+-0) = x for every x but -0 (NaN payloads pass through the add unchanged: the operand is already quiet, being
+//    a sum itself).
+// So the row's own copy neither loads nor stores the radiance: its update runs on a dummy and is dead code.
+constexpr unsigned kRowQuietMask = SAIL_JIT_ROWQUIET;
+static_assert(kRowQuietMask == 0u || SAIL_JIT_KL == 0u, "quiet rows: no light plugin compiled in");
+static_assert((kRowQuietMask & ~kRowShadeMask) == 0u, "quiet rows are rows with a copy of their own");
+template <bool Q> struct QuietTag { static constexpr bool value = Q; };
+template <int I, bool RECOMP_HL, bool BOXU, class Rest>
+D bool bounceRows(const Ctx& c, const Ray& r, const Sweep& sw, int b0, Hit& h, Rest&& rest) {
+  if constexpr (I + 1 < kRows) {
+    if (b0 != I) return bounceRows<I + 1, RECOMP_HL, BOXU>(c, r, sw, b0, h, rest);
+  }
+  Sweep su = sw;
+  su.bi = I;
+  h = hitRecord<RECOMP_HL, BOXU>(c, r, su);
+  if constexpr (((kRowShadeMask >> I) & 1u) != 0u) {
+    rest(h, QuietTag<((kRowQuietMask >> I) & 1u) != 0u>{});
+    return true;
+  }
+  return false;
+}
+template <bool RECOMP_HL, bool BOXU, class Rest>
+D void bounceU(const Ctx& c, const Ray& r, const Sweep& sw, Rest&& rest) {
+  const int b0 = __builtin_amdgcn_readfirstlane(sw.bi);
+  Hit h;
+  if (__all(sw.bi == b0)) {
+    if (bounceRows<0, RECOMP_HL, BOXU>(c, r, sw, b0, h, rest)) return;
+  } else {
+    hitRecordRows<0, false, RECOMP_HL, BOXU>(c, r, sw, b0, h);
+  }
+  rest(h, QuietTag<false>{});
+}
+#endif
 
 // ---- sampleGeometry for area lights (shader.shape.js:53-67) -----------------------------------------------------
 D V3 sampleGeometry(const Ctx& c, V2 u, int row, V3& normal, float& pdf) {
@@ -2125,24 +2182,36 @@ __device__ __forceinline__ void traceTileCompact(const SailTraceArgs& A) {
         c.fcx = (float)homeX(pixel) + 0.5f;
         c.fcy = (float)homeY(pixel) + 0.5f;
         const float seed = pathSeed(pixel) + (float)depth;
+        // the rest of the bounce behind the hit record `ins` (one text for both forms below: no arithmetic restated)
+#define SAIL_BOUNCE_REST(ins, Q)                                                                   \
+        PHASE_MARK(pc, 1);                                                                         \
+        if (depth == 1 && aovs && k + pixel / kPX == A.spp - 1) {                                  \
+          const size_t g = (size_t)homeY(pixel) * A.W + homeX(pixel);                              \
+          const V3 qn = ins.normal / 2.0f + 0.5f, qp = normalize(ins.hit);                         \
+          if (A.aovN) A.aovN[g] = make_float4(qn.x, qn.y, qn.z, 1.0f);                             \
+          if (A.aovP) A.aovP[g] = make_float4(qp.x, qp.y, qp.z, 1.0f);                             \
+        }                                                                                          \
+        V3 e = (Q) ? v3s(0.0f) : E_LOAD(pixel); /* Q: a quiet row's copy (kRowQuietMask) */        \
+        if (!(!CULL && depth == A.maxBounces && shadeLast(c, ins, seed, fpdf, e))) {               \
+          if constexpr (kShCompact) {                                                              \
+            shadeBounceP(c, ins, ray, seed, fpdf, e, pc, sp); /* e: the dark outcome */            \
+            eLit = sp.eLit;                                                                        \
+          } else {                                                                                 \
+            shadeBounce(c, ins, ray, seed, fpdf, e, pc);                                           \
+          }                                                                                        \
+        }                                                                                          \
+        if constexpr (!(Q)) E_STORE(pixel, e);
+#if SAIL_ROWSHADE
+        // a row-uniform wave runs it in its row's branch, on that row's constants (bounceU)
+        bounceU<true, FAM && !CULL>(c, ray, sw,
+                                    [&](const Hit& ins, auto quiet) __attribute__((always_inline)) {
+          SAIL_BOUNCE_REST(ins, decltype(quiet)::value)
+        });
+#else
         const Hit ins = hitRecordU<true, FAM && !CULL>(c, ray, sw);
-        PHASE_MARK(pc, 1);
-        if (depth == 1 && aovs && k + pixel / kPX == A.spp - 1) {
-          const size_t g = (size_t)homeY(pixel) * A.W + homeX(pixel);
-          const V3 qn = ins.normal / 2.0f + 0.5f, qp = normalize(ins.hit);
-          if (A.aovN) A.aovN[g] = make_float4(qn.x, qn.y, qn.z, 1.0f);
-          if (A.aovP) A.aovP[g] = make_float4(qp.x, qp.y, qp.z, 1.0f);
-        }
-        V3 e = E_LOAD(pixel);
-        if (!(!CULL && depth == A.maxBounces && shadeLast(c, ins, seed, fpdf, e))) {
-          if constexpr (kShCompact) {
-            shadeBounceP(c, ins, ray, seed, fpdf, e, pc, sp);  // e: the dark outcome
-            eLit = sp.eLit;
-          } else {
-            shadeBounce(c, ins, ray, seed, fpdf, e, pc);
-          }
-        }
-        E_STORE(pixel, e);
+        SAIL_BOUNCE_REST(ins, false)
+#endif
+#undef SAIL_BOUNCE_REST
       }
       if constexpr (kShCompact) {
         if (c.ln > 0) {  // uniform

@@ -87,7 +87,24 @@ def cls(op):
 
 
 def part(names, line):
-    """names: inline stack outermost first, below traceTileCompact"""
+    """names: inline stack outermost first, below traceTileCompact. In the row-shading form (SAIL_JIT_ROWSHADE) the hit
+    record and the rest of the bounce sit under bounceU: the rest is a lambda, once per row with a copy of its own
+    (under that row's bounceRows<I, ...>) and once for every other wave; its parts are named as ever, with the copy."""
+    if names and names[0].startswith("bounceU"):
+        names, copy = names[1:], "generic copy"
+        while names and names[0].startswith("bounceRows"):
+            copy = "row %s copy" % re.match(r"bounceRows<(\d+)", names[0]).group(1)
+            names = names[1:]
+        if names and names[0].startswith("operator()"):  # the rest of the bounce
+            rest = names[1:]
+            if not rest or rest[0].startswith("operator()"):
+                return "radiance slots, AOV stores [%s]" % copy
+            if rest[0].startswith(("operator+", "operator/", "normalize")):  # fstrace.glsl:15-16 on the record
+                return "AOVs (first hit) [%s]" % copy
+            return "%s [%s]" % (part(rest, line), copy)
+        if not names or names[0].startswith("__all"):  # the dispatch on the wave's row
+            return "hit record"
+        # else: the hit record in front of it
     if not names:
         return "kernel body (sort, gather, sample loop)" if 1929 <= line <= 2100 else "kernel body (setup, sample end)"
     top = names[0]

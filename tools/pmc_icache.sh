@@ -1,6 +1,7 @@
 #!/bin/bash
 # Instruction-cache / issue-wait PMC pass (PMC_SET=icache) or LDS / scalar-memory pass (PMC_SET=lds) for the
-# trace kernel of each workload (one run of 8 SQ counters per config; kernel-trace only).
+# trace kernel of each workload (one run of 8 SQ counters per config; kernel-trace only). PMC_SPP and PMC_BENCH_ARGS as in
+# tools/pmc.sh (a value kernel needs "--debug 13=0", or at least 256 samples and a warm-up step).
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 ROOT=$(pwd)
 OUT=${PMC_OUT:-gpurun_out/pmc_icache}
@@ -15,5 +16,5 @@ for cfg in ${PMC_CONFIGS:-C2 C3 C4}; do
       SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU
   fi
   timeout -k 10 300 rocprofv3 --pmc "$@" -d $ROOT/$OUT/$cfg -o run --output-format csv -- \
-    python3 $ROOT/bench.py --config $cfg --full --steps 1 --warmup 0 --spp 32 --no-cpu-baseline > $ROOT/$OUT/$cfg.log 2>&1 || exit 1
+    python3 $ROOT/bench.py --config $cfg --full --steps 1 --warmup 0 --spp ${PMC_SPP:-32} --no-cpu-baseline ${PMC_BENCH_ARGS:-} > $ROOT/$OUT/$cfg.log 2>&1 || exit 1
 done
