@@ -221,6 +221,80 @@ int sail_render_until(sail_ctx* ctx, const double mvp_rowmajor[16], const float 
                       uint64_t min_spp, uint64_t max_spp, sail_noise_info* out, int* converged,
                       sail_until_step* history, int capacity, int* looks);
 
+/* ---- adaptive sampling: a mask over the 64x64 partition tiles, and render-until-every-tile-converged (the use progressive
+ * tracers such as Cycles and pbrt-v4 make of the estimate above; no reference counterpart) ----
+ * Tiles are sail_partition_tiles': (W+63)/64 x (H+63)/64 of them, index t = ty * tilesX + tx, row 0 = bottom. With a mask
+ * set, a launch traces the active tiles of the context's share and nothing else: an inactive tile's accumulator texels
+ * (their sample count in .w included) and AOV texels keep what they held. Sample k has one seed and one jitter whatever the
+ * mask, so a tile rendered for samples 0..k-1 and then left alone holds the bits of the uniform k-sample frame.
+ *   which tiles a device traces: one device, the active tiles; SAIL_PART_TILES, its own tiles that are active;
+ *     SAIL_PART_SAMPLES, the active tiles for its samples; sail_comm_init ranks likewise, each with its own intersection.
+ *     A launch without an active tile of its own launches nothing; the sample index advances all the same.
+ *   sail_set_active_tiles launches queued samples first, then copies `active` (count = the number of tiles; a byte != 0 is
+ *     active). (NULL, 0) removes the mask. An all-ones mask is a mask (the table path) and gives the bits of none.
+ *   everything that restarts the accumulator removes the mask: sail_reset, sail_set_scene, sail_update_objects,
+ *     sail_move_objects, sail_set_accum_mode, sail_set_partition, sail_load_accum (a host resuming a checkpoint sets it
+ *     again: checkpoints do not hold it).
+ *   refused, nothing changed: SAIL_E_STATE in SAIL_ACCUM_MIX and SAIL_ACCUM_COMPAT8 (no per-pixel count) and on a
+ *     half-loaded checkpoint; SAIL_E_INVALID for a count that is not the number of tiles (or active == NULL with count != 0).
+ *     On a multi-device context a device that fails while the mask is set (memory, a HIP error) gives the devices
+ *     before it their previous mask back: the devices never trace under different masks.
+ *   sail_get_active_tiles: the mask as bytes 0 / 1 (all 1 without one), *n_active (may be NULL) the number of active tiles.
+ *   sail_stats.nominal_segments counts a masked launch's active in-frame pixels x samples x bounces (pixels not traced
+ *     earn no rate); sail_stats.samples stays the sample index.
+ *   AOV maps: an inactive tile keeps its last rendered sample's values (one device, tile partitions). Under a sample
+ *     partition the shown maps are those of the rank that rendered the frame's last sample, so an inactive tile shows
+ *     that rank's last sample of it.
+ *   the mark with a mask: sail_noise_mark and the remark of sail_noise_estimate write P only in the 16x16 tiles of active
+ *     64x64 tiles. A frozen tile therefore keeps the pair (P of the look before it froze, S of the look it froze at): its
+ *     error reads the same bits at every later look and sail_denoise still finds two halves there. The estimate itself does
+ *     not read the mask. A context without a mark yet marks the whole frame. */
+int sail_set_active_tiles(sail_ctx* ctx, const uint8_t* active, int count);
+int sail_get_active_tiles(sail_ctx* ctx, uint8_t* active, int count, int* n_active);
+/* host only: the next mask from sail_noise_estimate's tile_err map (16x16 tiles, row 0 = bottom). Per 64x64 tile t
+ *   e64[t] = (sum of (double)tile_err16[i] * px_i) / (sum of px_i)  over its in-frame 16x16 tiles i, rows outer, in index
+ *            order, px_i the in-frame pixels of i (the tile's mean pixel error, as max_tile is a 16x16 tile's)
+ *   noisy[t] = !(e64[t] <= target)          (a NaN error is noisy)
+ *   active[t] = prev_active[t] && (noisy[t] || (dilate && one of t's up to 8 neighbours is noisy))
+ * prev_active == NULL: all ones. A frozen tile never returns, so the active set only shrinks and every active tile holds
+ * exactly the samples 0..k-1. dilate (0 or 1) keeps a converged tile beside a noisy one rendering, which avoids a visible
+ * seam. active may be prev_active; tile_err64 (doubles, one per tile) and n_active may be NULL. SAIL_E_INVALID: a size < 1,
+ * a NaN target, a dilate outside 0..1, tile_err16 or active NULL. */
+int sail_plan_adaptive(int width, int height, const float* tile_err16, double target, int dilate,
+                       const uint8_t* prev_active, uint8_t* active, double* tile_err64, int* n_active);
+typedef struct sail_adaptive_params {
+  double target;               /* every tile's e64 <= target ends the render */
+  uint64_t min_spp, max_spp;   /* as sail_render_until */
+  int dilate;                  /* 0 or 1 */
+} sail_adaptive_params;
+typedef struct sail_adaptive_info {
+  sail_noise_info noise;       /* the last estimate (mean = max_tile = +inf when no look estimated) */
+  int converged;               /* 1: no tile is active */
+  int active_tiles;            /* tiles still active at the end */
+  int tiles_x, tiles_y;        /* 64x64 tiles */
+  uint64_t pixel_samples;      /* traced by this call: sum over its launches of active in-frame pixels x samples */
+  uint64_t frame_pixel_samples;  /* W H x the samples this call advanced the index by: what sail_render_until traces */
+  double kernel_ms;            /* trace kernel time of this call (sail_stats.kernel_ms after - before) */
+} sail_adaptive_info;
+/* target +inf, min_spp 16, max_spp 1024, dilate 1 */
+int sail_adaptive_defaults(sail_adaptive_params* p);
+/* sail_render_until with a mask: the frozen schedule from the context's sample index on, looks at sail_plan_until's
+ * indices. The first look marks. Each later look estimates (no remark in the pass), plans the mask from the estimate's
+ * tile_err with the context's mask as prev_active, sets it, and, while a tile is active and k < max_spp, marks (masked)
+ * and goes on. It stops when no tile is active (converged = 1) or at k == max_spp (converged = 0 unless nothing is
+ * active); the look it stops at does not re-mark. The mask stays set afterwards (sail_get_active_tiles shows it) until the
+ * next restart removes it, so a later call on the same context continues under it: frozen tiles stay frozen, and a call
+ * that finds no tile active renders nothing. tile_samples (one per tile, may be NULL): the sample index at which the tile
+ * was frozen, or k at the end for an active one. Every tile's texels equal the uniform frame's at that index, bit for bit.
+ * That holds for masks this call produced: a tile switched off by hand before the call reports the sample index it was
+ * switched off at (0 on a fresh accumulator) and keeps what it held, and a tile switched back on by hand reports k
+ * although it lacks the samples it sat out; tile_samples means nothing for such tiles.
+ * Refusals are sail_render_until's and the mask's (SAIL_ACCUM_MIX too), before anything is rendered; params == NULL: the
+ * defaults. */
+int sail_render_adaptive(sail_ctx* ctx, const double mvp_rowmajor[16], const float eye[3], int max_bounces,
+                         const sail_adaptive_params* params, sail_adaptive_info* out, sail_until_step* history,
+                         int capacity, int* looks, uint32_t* tile_samples);
+
 /* ---- variance-guided a-trous denoiser of a progressive frame (no reference counterpart: the reference's only denoiser is
  * the `wavelet` display filter, whose edge stops are constants; the edge-avoiding a-trous wavelet of SVGF, Schied et al.
  * 2017, without its temporal part) ----

@@ -51,6 +51,7 @@ EXPORTS = (
     "sail_jit_value_key", "sail_jit_spec_key", "sail_plan_settle", "sail_jit_resident",
     "sail_plan_reduce", "sail_plan_keep", "sail_plan_load_part", "sail_plan_last_bounce",
     "sail_noise_mark", "sail_noise_estimate", "sail_plan_until", "sail_render_until",
+    "sail_set_active_tiles", "sail_get_active_tiles", "sail_plan_adaptive", "sail_adaptive_defaults", "sail_render_adaptive",
     "sail_denoise_defaults", "sail_denoise",
     "sail_temporal_defaults", "sail_gbuffer", "sail_temporal_begin", "sail_temporal_resolve", "sail_temporal_read",
     "sail_temporal_load_history",
@@ -95,6 +96,17 @@ class NoiseInfo(ctypes.Structure):
 
 class UntilStep(ctypes.Structure):
     _fields_ = [("k", ctypes.c_uint64), ("mean", ctypes.c_double), ("max_tile", ctypes.c_double)]
+
+
+class AdaptiveParams(ctypes.Structure):
+    _fields_ = [("target", ctypes.c_double), ("min_spp", ctypes.c_uint64), ("max_spp", ctypes.c_uint64),
+                ("dilate", ctypes.c_int)]
+
+
+class AdaptiveInfo(ctypes.Structure):
+    _fields_ = [("noise", NoiseInfo), ("converged", ctypes.c_int), ("active_tiles", ctypes.c_int),
+                ("tiles_x", ctypes.c_int), ("tiles_y", ctypes.c_int), ("pixel_samples", ctypes.c_uint64),
+                ("frame_pixel_samples", ctypes.c_uint64), ("kernel_ms", ctypes.c_double)]
 
 
 class DenoiseParams(ctypes.Structure):
@@ -238,6 +250,15 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
         "sail_noise_mark": (ctypes.c_int, [vp]),
         "sail_noise_estimate": (ctypes.c_int, [vp, ctypes.POINTER(NoiseInfo), f32p, f32p, ctypes.c_int]),
         "sail_plan_until": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+        "sail_set_active_tiles": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int]),
+        "sail_get_active_tiles": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+        "sail_plan_adaptive": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, f32p, ctypes.c_double, ctypes.c_int,
+                                              ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint8), f64p,
+                                              ctypes.POINTER(ctypes.c_int)]),
+        "sail_adaptive_defaults": (ctypes.c_int, [ctypes.POINTER(AdaptiveParams)]),
+        "sail_render_adaptive": (ctypes.c_int, [vp, f64p, f32p, ctypes.c_int, ctypes.POINTER(AdaptiveParams),
+                                                ctypes.POINTER(AdaptiveInfo), ctypes.POINTER(UntilStep), ctypes.c_int,
+                                                ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint32)]),
         "sail_render_until": (ctypes.c_int, [vp, f64p, f32p, ctypes.c_int, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint64,
                                              ctypes.POINTER(NoiseInfo), ctypes.POINTER(ctypes.c_int),
                                              ctypes.POINTER(UntilStep), ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
@@ -387,6 +408,40 @@ def plan_until(k: int, min_spp: int, max_spp: int) -> int:
     if rc:
         raise SailError(f"sail_plan_until: {rc}: {lib.sail_last_error(None).decode()}")
     return int(nxt.value)
+
+
+def plan_adaptive(width: int, height: int, tile_err16, target: float, dilate: int = 1, prev_active=None):
+    """The next tile mask from a noise estimate's "tile_err" map (sail_plan_adaptive, host-only): per 64x64 tile the
+    pixel-weighted mean e64 of its 16x16 tiles' errors; a tile stays active while it was active and it, or with dilate one
+    of its neighbours, is not <= target. Returns (active (tilesY, tilesX) uint8, e64 (tilesY, tilesX) f64, n_active)."""
+    lib = load()
+    tx, ty = (int(width) + 63) // 64, (int(height) + 63) // 64
+    e16 = _f32(tile_err16)
+    if width < 1 or height < 1 or e16.size != ((int(width) + 15) // 16) * ((int(height) + 15) // 16):
+        raise SailError(f"plan_adaptive: tile_err16 has {e16.size} entries for {width} x {height}")
+    prev = None
+    if prev_active is not None:
+        prev = np.ascontiguousarray(np.asarray(prev_active, dtype=np.uint8).reshape(-1))
+        if prev.size != tx * ty:
+            raise SailError(f"plan_adaptive: prev_active has {prev.size} entries, the frame {tx * ty} tiles")
+    active = np.zeros((ty, tx), dtype=np.uint8)
+    e64 = np.zeros((ty, tx), dtype=np.float64)
+    n = ctypes.c_int(0)
+    rc = lib.sail_plan_adaptive(int(width), int(height), _ptr(e16), float(target), int(dilate), _ptr(prev, ctypes.c_uint8),
+                                _ptr(active, ctypes.c_uint8), _ptr(e64, ctypes.c_double), ctypes.byref(n))
+    if rc:
+        raise SailError(f"sail_plan_adaptive: {rc}: {lib.sail_last_error(None).decode()}")
+    return active, e64, int(n.value)
+
+
+def adaptive_defaults() -> dict:
+    """sail_render_adaptive's default parameters (sail_adaptive_defaults, host-only): target, min_spp, max_spp, dilate."""
+    lib = load()
+    p = AdaptiveParams()
+    rc = lib.sail_adaptive_defaults(ctypes.byref(p))
+    if rc:
+        raise SailError(f"sail_adaptive_defaults: {rc}")
+    return {"target": p.target, "min_spp": int(p.min_spp), "max_spp": int(p.max_spp), "dilate": p.dilate}
 
 
 def _noise_dict(n: NoiseInfo) -> dict:
@@ -734,6 +789,56 @@ class Context:
                                                ctypes.byref(looks)), "sail_render_until")
         out = _noise_dict(n)
         out["converged"] = bool(conv.value)
+        out["history"] = [{"k": int(s.k), "mean": s.mean, "max_tile": s.max_tile} for s in hist[:min(looks.value, cap)]]
+        return out
+
+    def set_active_tiles(self, active=None):
+        """The mask over the frame's 64x64 tiles (sail_set_active_tiles): `active` holds one entry per tile, row 0 =
+        bottom, nonzero = traced; None removes the mask."""
+        if active is None:
+            self._check(self.lib.sail_set_active_tiles(self.h, None, 0), "sail_set_active_tiles")
+            return
+        a = np.ascontiguousarray((np.asarray(active).reshape(-1) != 0).astype(np.uint8))
+        self._check(self.lib.sail_set_active_tiles(self.h, _ptr(a, ctypes.c_uint8), int(a.size)), "sail_set_active_tiles")
+
+    def get_active_tiles(self) -> np.ndarray:
+        """The mask as a (tilesY, tilesX) uint8 array of 0 / 1 (all ones without a mask; sail_get_active_tiles)."""
+        tx, ty = (self.W + 63) // 64, (self.H + 63) // 64
+        a = np.zeros((ty, tx), dtype=np.uint8)
+        n = ctypes.c_int(0)
+        self._check(self.lib.sail_get_active_tiles(self.h, _ptr(a, ctypes.c_uint8), tx * ty, ctypes.byref(n)),
+                    "sail_get_active_tiles")
+        return a
+
+    def render_adaptive(self, mvp, eye, max_bounces: int, target: Optional[float] = None, min_spp: Optional[int] = None,
+                        max_spp: Optional[int] = None, dilate: Optional[int] = None) -> dict:
+        """Render the frozen schedule, freezing the 64x64 tiles whose error is <= target at a look, until none is active
+        or max_spp samples are in (sail_render_adaptive). Returns the last estimate's fields plus "converged",
+        "active_tiles", "pixel_samples", "frame_pixel_samples", "trace_ms", "history" as render_until, and
+        "tile_samples", the (tilesY, tilesX) uint32 sample count each tile holds. Unset parameters are
+        adaptive_defaults()."""
+        m = np.ascontiguousarray(np.asarray(mvp, dtype=np.float64).reshape(16))
+        e = _f32(eye)
+        d = adaptive_defaults()
+        for key, v in (("target", target), ("min_spp", min_spp), ("max_spp", max_spp), ("dilate", dilate)):
+            if v is not None:
+                d[key] = v
+        for v in (d["min_spp"], d["max_spp"]):
+            if not 0 <= int(v) < 1 << 64:
+                raise SailError(f"render_adaptive: {v} is not an unsigned 64-bit count")
+        p = AdaptiveParams(float(d["target"]), int(d["min_spp"]), int(d["max_spp"]), int(d["dilate"]))
+        info, looks = AdaptiveInfo(), ctypes.c_int(0)
+        cap = 64  # looks double k: more cannot happen below 2^31 samples
+        hist = (UntilStep * cap)()
+        tx, ty = (self.W + 63) // 64, (self.H + 63) // 64
+        ts = np.zeros((ty, tx), dtype=np.uint32)
+        self._check(self.lib.sail_render_adaptive(self.h, _ptr(m, ctypes.c_double), _ptr(e), int(max_bounces), ctypes.byref(p),
+                                                  ctypes.byref(info), hist, cap, ctypes.byref(looks),
+                                                  _ptr(ts, ctypes.c_uint32)), "sail_render_adaptive")
+        out = _noise_dict(info.noise)
+        out.update(converged=bool(info.converged), active_tiles=info.active_tiles, tiles64_x=info.tiles_x,
+                   tiles64_y=info.tiles_y, pixel_samples=int(info.pixel_samples),
+                   frame_pixel_samples=int(info.frame_pixel_samples), trace_ms=info.kernel_ms, tile_samples=ts)
         out["history"] = [{"k": int(s.k), "mean": s.mean, "max_tile": s.max_tile} for s in hist[:min(looks.value, cap)]]
         return out
 

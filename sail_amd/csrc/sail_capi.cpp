@@ -29,6 +29,7 @@ hipError_t sail_launch_pick(const SailPrim* prims, int n, const float* rays, int
 // sail_noise.hip: the noise estimate's per-tile pass
 #include "sail_noise.h"
 hipError_t sail_launch_noise(const SailNoiseArgs& A, hipStream_t s);
+hipError_t sail_launch_noise_copy(const SailNoiseArgs& A, hipStream_t s);
 // sail_denoise.hip: the denoiser's prepare pass and one a-trous pass
 #include "sail_denoise.h"
 hipError_t sail_launch_denoise_prepare(const SailDenoisePrepareArgs& A, hipStream_t s);
@@ -197,6 +198,16 @@ struct sail_ctx {
   SailJitSpec valSpec;
   int valState = SAIL_KERNEL_JIT_NONE;
   SailJitKernel valK;
+  bool lastMasked = false;  // the last trace launch ran a _masked instance (a tile mask was set)
+  // The MASKED instances of the scene's run-time kernels (SailJitSpec.masked), asked for at the first launch under a tile
+  // mask: slot 0 follows the types spec, slot 1 the value spec. Built in the background like their unmasked twins; until
+  // one is loaded a masked launch runs the precompiled _masked kernel of the scene's set, with the same results.
+  struct MaskedJit {
+    bool have = false;
+    SailJitSpec spec;
+    int state = SAIL_KERNEL_JIT_NONE;
+    SailJitKernel k;
+  } maskedJit[2];
   bool lastJit = false;  // the last trace launch ran a run-time compiled kernel (sail_kernel_name)
   int lastJitMode = 0;
   uint64_t lastBuildId = 0;  // the run-time kernel's build identity (sail_get_kernel_info)
@@ -227,6 +238,19 @@ struct sail_ctx {
   uint64_t noiseK = 0;
   float* noiseOut = nullptr;
   float* noisePix = nullptr;  // the optional per-pixel map, allocated on first use
+  // Tile mask (sail_set_active_tiles), on every context that traces or holds the mark (each sub-context of a multi-device
+  // one keeps the whole mask: device 0's masks the mark, every device intersects it with its share). maskSet: a launch
+  // walks tileMap, the ascending table of this rank's active tiles (maskTiles of them, maskPixels in-frame pixels);
+  // maskBytes is the whole mask, a byte per 64x64 tile, for the noise kernels. Both device arrays hold one entry per tile
+  // of the frame, allocated on first use and rewritten only with the stream idle. frozenAt[t]: the sample index at
+  // which the inactive tile t was switched off. resetAccum removes the mask.
+  bool maskSet = false;
+  std::vector<uint8_t> mask;
+  std::vector<uint32_t> frozenAt;
+  int32_t* tileMap = nullptr;
+  uint8_t* maskBytes = nullptr;
+  int maskTiles = 0;
+  long long maskPixels = 0;
   // Denoiser (sail_denoise): one block of work buffers, allocated on first use: two (c, v) float4 maps, the guides as a
   // float4 and a float2 map, the variance map, the RGBA8 map and the per-tile non-finite counts
   void* denoiseWork = nullptr;
@@ -351,10 +375,11 @@ int jitWaves(int mode, int kernelSet) {
 // small share (a rank of 8 or more, one eighth of 1080p) it holds 1 sample and the launch is split into staged sample
 // groups instead (C2 per GPU at N = 8: 95.4 Gseg/s against 92.1 with 16 samples and no groups, 91.4 with both; at
 // N = 4 95.2 against 94.9; profiles/r05_scale_ns_c2.jsonl, tools/scale_groups.sh).
-int ownedTiles(const sail_ctx* c, int* tilesX, int* tilesY);
+// (the share is the partition's, whatever tile mask is set: a mask must not swap the scene's kernel for another build)
+int partitionTiles(const sail_ctx* c, int* tilesX, int* tilesY);
 bool cornellShareLarge(const sail_ctx* c) {
   int tx, ty;
-  const int owned = ownedTiles(c, &tx, &ty);
+  const int owned = partitionTiles(c, &tx, &ty);
   // residency rounds of 512-thread workgroups at 8 waves per SIMD (4,096 / 32 pixels = 128 workgroups per tile)
   const double rounds = (double)owned * 128.0 / ((double)c->numCUs * 4.0);
   return rounds >= 12.0;
@@ -415,7 +440,45 @@ bool jitSpecFor(const sail_ctx* c, SailJitSpec* out, int* mode) {
 // The rows changed, or the spec their value kernel was derived from: the hold on the value spec goes (a queued build of it
 // is skipped, a finished one stays in the caches for a scene that returns to this pose), launches run the types kernel
 // again, and the settle count restarts.
+// the hold on a masked twin goes with the spec it follows (dropValues, refreshJit, sail_destroy)
+void dropMaskedJit(sail_ctx* c, int slot) {
+  sail_ctx::MaskedJit& m = c->maskedJit[slot];
+  if (m.have) {
+    // the last hold unloads the module (sail_jit_hold): no launch of it may still be running on this context's stream
+    if (m.state == SAIL_KERNEL_JIT_READY && c->stream) {
+      (void)hipSetDevice(c->device);
+      (void)hipStreamSynchronize(c->stream);
+    }
+    sail_jit_hold(c->device, m.spec, -1);
+  }
+  m = sail_ctx::MaskedJit{};
+}
+// The loaded masked twin of `base` in `slot`, waiting up to wait_ms for its build; false while it is being built or when
+// it failed
+bool maskedKernels(sail_ctx* c, int slot, const SailJitSpec& base, int wait_ms, SailJitKernel* k) {
+  sail_ctx::MaskedJit& m = c->maskedJit[slot];
+  SailJitSpec want = base;
+  want.masked = 1;
+  if (m.have && !sailJitSpecEqual(m.spec, want)) dropMaskedJit(c, slot);
+  if (!m.have) {
+    sail_jit_hold(c->device, want, +1);
+    m.have = true;
+    m.spec = want;
+    m.state = SAIL_KERNEL_JIT_PENDING;
+  }
+  if (m.state == SAIL_KERNEL_JIT_FAILED) return false;
+  if (m.state != SAIL_KERNEL_JIT_READY) {
+    std::string err;
+    const int r = sail_jit_kernels(c->device, m.spec, wait_ms, &m.k, &err);
+    if (r == 1) return false;
+    if (r < 0) { m.state = SAIL_KERNEL_JIT_FAILED; return false; }
+    m.state = SAIL_KERNEL_JIT_READY;
+  }
+  *k = m.k;
+  return true;
+}
 void dropValues(sail_ctx* c) {
+  dropMaskedJit(c, 1);
   if (c->valHave) {
     // the last hold unloads the module (sail_jit_hold): no launch of it may still be running on this context's stream
     if (c->valState == SAIL_KERNEL_JIT_READY && c->stream) {
@@ -509,6 +572,7 @@ void refreshJit(sail_ctx* c) {
   const bool have = jitSpecFor(c, &spec, &mode);
   if (have == c->jitHave && (!have || sailJitSpecEqual(spec, c->jitSpec))) return;
   dropValues(c);  // the value kernel is the old spec's
+  dropMaskedJit(c, 0);  // and so is the types kernel's masked twin
   // hold the new spec before dropping the old one: a build both share is never skipped in between
   if (have) sail_jit_hold(c->device, spec, +1);
   if (c->jitHave) sail_jit_hold(c->device, c->jitSpec, -1);
@@ -549,16 +613,23 @@ int launchSamples(const sail_ctx* c) {
   if (c->launchSpp > 0) return c->launchSpp;
   return (c->jitHave && c->jitState != SAIL_KERNEL_JIT_FAILED && c->jitSpec.ns >= 16) ? 1024 : 64;
 }
-int ownedTiles(const sail_ctx* c, int* tilesX, int* tilesY) {
+// the tiles of this rank's share of the partition
+int partitionTiles(const sail_ctx* c, int* tilesX, int* tilesY) {
   const int tx = (c->W + 63) / 64, ty = (c->H + 63) / 64;
   *tilesX = tx; *tilesY = ty;
   if (c->partMode == SAIL_PART_SAMPLES) return tx * ty;
   const int total = tx * ty;
   return c->rank < total ? (total - c->rank + c->world - 1) / c->world : 0;
 }
+// the tiles a launch traces, and their in-frame pixels: the share, or with a tile mask its active tiles (tileMap)
+int ownedTiles(const sail_ctx* c, int* tilesX, int* tilesY) {
+  const int part = partitionTiles(c, tilesX, tilesY);
+  return c->maskSet ? c->maskTiles : part;
+}
 long long ownedPixels(const sail_ctx* c) {
+  if (c->maskSet) return c->maskPixels;
   int tx, ty;
-  const int owned = ownedTiles(c, &tx, &ty);
+  const int owned = partitionTiles(c, &tx, &ty);
   long long px = 0;
   const int w = (c->partMode == SAIL_PART_SAMPLES) ? 1 : c->world, r = (c->partMode == SAIL_PART_SAMPLES) ? 0 : c->rank;
   for (int j = 0; j < owned; j++) {
@@ -620,6 +691,9 @@ int resetAccum(sail_ctx* c) {
   c->reduced = false;
   c->queued.clear();  // queued one-sample frames belong to the accumulation being discarded
   c->noiseHave = false;  // so does the noise estimate's mark (sail_load_accum puts it back: it continues a render)
+  c->maskSet = false;    // and the tile mask: every tile of the new accumulation starts at sample 0
+  c->mask.clear();
+  c->frozenAt.clear();
   c->tpResolved = false;  // Out no longer belongs to this accumulator: sail_temporal_filter wants a resolve of the new one
   const size_t bytes = (size_t)c->W * c->H * sizeof(float4);
   HIPCHK(c, hipMemsetAsync(c->accum, 0, bytes, c->stream));
@@ -1022,6 +1096,7 @@ int launchTrace(sail_ctx* c, const SailSample* hs, int count, int maxBounces) {
     A.world = (c->partMode == SAIL_PART_SAMPLES) ? 1 : c->world;
     A.rank = (c->partMode == SAIL_PART_SAMPLES) ? 0 : c->rank;
     A.ownedTiles = owned;
+    A.tileMap = c->maskSet ? c->tileMap : nullptr;
     A.shadowAnyHit = c->shadowAnyHit;
     A.cullPrims = c->n >= c->cullMinPrims ? (cullFmaOk(c) ? 2 : 1) : 0;
     A.cullPrimary = eyeNearScene(c);
@@ -1034,7 +1109,16 @@ int launchTrace(sail_ctx* c, const SailSample* hs, int count, int maxBounces) {
     SailJitKernel jk;
     int jmode = 0;
     refreshValues(c);  // the settle count may have crossed its threshold with the launch before
-    const bool jit = !wavefront && (valueKernels(c, 0, &jk, &jmode) || jitKernels(c, c->jitWait, &jk, &jmode));
+    bool jit = false;
+    if (!wavefront && A.tileMap) {
+      // under a tile mask: the masked twin of the value kernel when that kernel serves, else of the types kernel (never
+      // waited for unless launches wait, SAIL_DEBUG_JIT_WAIT), else the precompiled _masked kernel
+      SailJitKernel base;
+      if (valueKernels(c, 0, &base, &jmode) && maskedKernels(c, 1, c->valSpec, c->jitWait, &jk)) jit = true;
+      else if (jitKernels(c, c->jitWait, &base, &jmode) && maskedKernels(c, 0, c->jitSpec, c->jitWait, &jk)) jit = true;
+    } else if (!wavefront) {
+      jit = valueKernels(c, 0, &jk, &jmode) || jitKernels(c, c->jitWait, &jk, &jmode);
+    }
     // samples of each pixel in flight per workgroup (the run-time kernels' spec; the precompiled kernels hold one):
     // NS times the workgroups of one sample in flight, each NS times shorter
     const int ns = jit ? c->jitSpec.ns : 1;
@@ -1064,7 +1148,10 @@ int launchTrace(sail_ctx* c, const SailSample* hs, int count, int maxBounces) {
       G = (int)((target + waves - 1) / waves);
       // the Cornell form holds 16 samples in flight only while its share queues enough workgroups (jitNsFor), and then
       // runs unsplit: staged groups lost 2-3 % per GPU at N = 4 and 8 (profiles/r05_scale_groups_c2.jsonl)
-      if (ns >= 16) G = 1;
+      // (under a tile mask that leaves too few active tiles for that, the kernel still holds its 16 samples, so the launch
+      // is split after all: rate_by_active_tiles against rate_by_active_tiles_unsplit in profiles/adaptive_1080p.json)
+      const bool fewActive = c->maskSet && (double)owned * 128.0 / ((double)c->numCUs * 4.0) < 12.0;
+      if (ns >= 16 && !fewActive) G = 1;
     }
     if (G > nspp) G = nspp;
     if (G < 1) G = 1;
@@ -1127,6 +1214,7 @@ int launchTrace(sail_ctx* c, const SailSample* hs, int count, int maxBounces) {
     HIPCHK(c, hipEventRecord(e1, c->stream));
     c->pending.emplace_back(e0, e1);
     c->lastGroups = A.sampleGroups;
+    c->lastMasked = A.tileMap != nullptr;
     c->lastWavefront = wavefront;
     c->launches++;
     c->nominalSegments += (uint64_t)px * (uint64_t)nspp * (uint64_t)maxBounces;
@@ -1413,7 +1501,8 @@ int sail_kernel_name(sail_ctx* c, char* name, int len) {
   // the last launch's form: sample groups run the _grouped kernel followed by sail_accum_kernel
   if (c->lastWavefront) k = "sail_wf_*";
   else if (c->lastJit) k = c->lastJitMode == SAIL_JIT_MODE_CULL ? "sail_trace_kernel_cull_jit" : "sail_trace_kernel_jit";
-  snprintf(name, (size_t)len, "%s%s", k, (!c->lastWavefront && c->lastGroups > 1) ? "_grouped" : "");
+  snprintf(name, (size_t)len, "%s%s%s", k, (!c->lastWavefront && c->lastMasked) ? "_masked" : "",
+           (!c->lastWavefront && c->lastGroups > 1) ? "_grouped" : "");
   return SAIL_OK;
 }
 
@@ -1537,13 +1626,15 @@ void sail_destroy(sail_ctx* c) {
   }
   if (c->device >= 0) (void)hipSetDevice(c->device);
   dropValues(c);
+  dropMaskedJit(c, 0);
   if (c->jitHave) sail_jit_hold(c->device, c->jitSpec, -1);  // its queued build, if any, is no longer needed
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->comm && g_rccl.commDestroy) g_rccl.commDestroy(c->comm);
   for (auto& pr : c->pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
   for (auto e : c->evPool) (void)hipEventDestroy(e);
   void* bufs[] = {c->accum, c->frame, c->frameN, c->frameP, c->aovN, c->aovP, c->filterOut, c->filterOut8, c->stage, c->segCounter, c->prims, c->tp, c->lt, c->lightObjRow, c->samples, c->wf,
-                  c->noiseMark, c->noiseOut, c->noisePix, c->denoiseWork, c->tpWork, c->tpMom, c->tpMotionDev, c->albMap};
+                  c->noiseMark, c->noiseOut, c->noisePix, c->denoiseWork, c->tpWork, c->tpMom, c->tpMotionDev, c->albMap,
+                  c->tileMap, c->maskBytes};
   for (void* b : bufs) if (b) (void)hipFree(b);
   if (c->samplesPinned) (void)hipHostFree(c->samplesPinned);
   if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -2161,7 +2252,16 @@ int sail_noise_mark(sail_ctx* c) {
     c->noiseMark = nullptr;
     return fail(c, SAIL_E_OOM, "noise mark");
   }
-  HIPCHK(c, hipMemcpyAsync(c->noiseMark, shownAccum(c), bytes, hipMemcpyDeviceToDevice, c->stream));
+  if (c->maskSet && c->noiseHave) {  // frozen tiles keep the mark they froze with
+    SailNoiseArgs A;
+    memset(&A, 0, sizeof A);
+    A.S = shownAccum(c); A.P = c->noiseMark;
+    A.W = c->W; A.H = c->H;
+    A.active64 = c->maskBytes; A.tiles64X = (c->W + 63) / 64;
+    HIPCHK(c, sail_launch_noise_copy(A, c->stream));
+  } else {
+    HIPCHK(c, hipMemcpyAsync(c->noiseMark, shownAccum(c), bytes, hipMemcpyDeviceToDevice, c->stream));
+  }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->noiseHave = true;
   c->noiseK = c->k;
@@ -2203,6 +2303,7 @@ int sail_noise_estimate(sail_ctx* c, sail_noise_info* out, float* tile_err, floa
   A.mix = c->accumMode == SAIL_ACCUM_MIX;
   A.kf = (float)c->k; A.hf = (float)c->noiseK;
   A.remark = remark != 0;
+  if (c->maskSet) { A.active64 = c->maskBytes; A.tiles64X = (c->W + 63) / 64; }
   std::vector<float> host(nt * 2);
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (int rc = getEvent(c, &e0)) return rc;
@@ -2308,6 +2409,234 @@ int sail_render_until(sail_ctx* c, const double mvp[16], const float eye[3], int
     if (conv) break;
   }
   if (converged) *converged = conv;
+  if (looks) *looks = nlooks;
+  return SAIL_OK;
+}
+
+// ---- adaptive sampling: the tile mask and render-until-every-tile-converged (include/sail_hip.h) ---------------------------
+int sail_set_active_tiles(sail_ctx* c, const uint8_t* active, int count) {
+  if (!c) return SAIL_E_INVALID;
+  const int tx = (c->W + 63) / 64, ty = (c->H + 63) / 64, tiles = tx * ty;
+  const bool clear = !active && count == 0;
+  // everything is checked before anything changes
+  if (!clear && (!active || count != tiles))
+    return fail(c, SAIL_E_INVALID, "sail_set_active_tiles: count %d, the frame has %d x %d = %d tiles (NULL, 0 removes the mask)",
+                count, tx, ty, tiles);
+  if (c->accumMode != SAIL_ACCUM_SUM)
+    return fail(c, SAIL_E_STATE, "sail_set_active_tiles: SAIL_ACCUM_MIX and SAIL_ACCUM_COMPAT8 keep no per-pixel sample count");
+  if (int rc = loadIncomplete(c, "sail_set_active_tiles")) return rc;
+  if (!c->subs.empty()) {
+    // a device that fails (memory, a HIP error) must not leave the devices before it under another mask than the rest:
+    // they get the mask they had back, with the sample indices their tiles were switched off at
+    const bool hadMask = c->subs[0]->maskSet;
+    const std::vector<uint8_t> before = c->subs[0]->mask;
+    std::vector<std::vector<uint32_t>> frozenBefore;
+    for (sail_ctx* s : c->subs) frozenBefore.push_back(s->frozenAt);
+    for (size_t i = 0; i < c->subs.size(); i++) {
+      const int rc = sail_set_active_tiles(c->subs[i], active, count);
+      if (rc == SAIL_OK) continue;
+      relay(c, rc, c->subs[i]);
+      for (size_t j = 0; j < i; j++) {
+        (void)sail_set_active_tiles(c->subs[j], hadMask ? before.data() : nullptr, hadMask ? tiles : 0);
+        c->subs[j]->frozenAt = frozenBefore[j];
+      }
+      return rc;
+    }
+    return SAIL_OK;
+  }
+  if (int rc = flushQueued(c)) return rc;  // queued samples were asked for under the mask as it was
+  if (clear) {
+    c->maskSet = false;
+    c->mask.clear();
+    c->frozenAt.clear();
+    return SAIL_OK;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // launches in flight read the tables
+  if (!c->tileMap && hipMalloc(&c->tileMap, sizeof(int32_t) * (size_t)tiles) != hipSuccess) {
+    c->tileMap = nullptr;
+    return fail(c, SAIL_E_OOM, "tile table");
+  }
+  if (!c->maskBytes && hipMalloc(&c->maskBytes, (size_t)tiles) != hipSuccess) {
+    c->maskBytes = nullptr;
+    return fail(c, SAIL_E_OOM, "tile mask");
+  }
+  std::vector<uint8_t> m((size_t)tiles);
+  for (int t = 0; t < tiles; t++) m[(size_t)t] = active[t] ? 1 : 0;
+  // this rank's active tiles, ascending, and their in-frame pixels
+  const int w = (c->partMode == SAIL_PART_SAMPLES) ? 1 : c->world, r = (c->partMode == SAIL_PART_SAMPLES) ? 0 : c->rank;
+  std::vector<int32_t> table;
+  long long px = 0;
+  for (int t = r; t < tiles; t += w) {
+    if (!m[(size_t)t]) continue;
+    table.push_back(t);
+    const int x0 = (t % tx) * 64, y0 = (t / tx) * 64;
+    const int cw = (c->W - x0) < 64 ? (c->W - x0) : 64, ch = (c->H - y0) < 64 ? (c->H - y0) : 64;
+    px += (long long)cw * ch;
+  }
+  if (!table.empty())
+    HIPCHK(c, hipMemcpy(c->tileMap, table.data(), sizeof(int32_t) * table.size(), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->maskBytes, m.data(), (size_t)tiles, hipMemcpyHostToDevice));
+  if (c->frozenAt.size() != (size_t)tiles) c->frozenAt.assign((size_t)tiles, 0u);
+  for (int t = 0; t < tiles; t++) {
+    const bool was = !c->maskSet || c->mask[(size_t)t];
+    if (was && !m[(size_t)t]) c->frozenAt[(size_t)t] = (uint32_t)c->k;
+  }
+  c->mask.swap(m);
+  c->maskSet = true;
+  c->maskTiles = (int)table.size();
+  c->maskPixels = px;
+  return SAIL_OK;
+}
+
+int sail_get_active_tiles(sail_ctx* c, uint8_t* active, int count, int* n_active) {
+  if (!c) return SAIL_E_INVALID;
+  const int tiles = ((c->W + 63) / 64) * ((c->H + 63) / 64);
+  if (!active || count != tiles)
+    return fail(c, SAIL_E_INVALID, "sail_get_active_tiles: count %d, the frame has %d tiles", count, tiles);
+  const sail_ctx* h = c->subs.empty() ? c : c->subs[0];  // every device of a multi-device context holds the whole mask
+  int n = 0;
+  for (int t = 0; t < tiles; t++) {
+    active[t] = (!h->maskSet || h->mask[(size_t)t]) ? 1 : 0;
+    n += active[t];
+  }
+  if (n_active) *n_active = n;
+  return SAIL_OK;
+}
+
+int sail_plan_adaptive(int width, int height, const float* tile_err16, double target, int dilate, const uint8_t* prev_active,
+                       uint8_t* active, double* tile_err64, int* n_active) {
+  if (width < 1 || height < 1 || !tile_err16 || !active || target != target || dilate < 0 || dilate > 1)
+    return fail(nullptr, SAIL_E_INVALID, "sail_plan_adaptive: bad arguments (%d x %d, target %g, dilate %d)", width, height,
+                target, dilate);
+  const int tx16 = (width + 15) / 16, ty16 = (height + 15) / 16, tx = (width + 63) / 64, ty = (height + 63) / 64;
+  std::vector<uint8_t> noisy((size_t)tx * ty);
+  for (int j = 0; j < ty; j++)
+    for (int i = 0; i < tx; i++) {
+      double sum = 0.0, px = 0.0;
+      for (int v = j * 4; v < j * 4 + 4 && v < ty16; v++)
+        for (int u = i * 4; u < i * 4 + 4 && u < tx16; u++) {
+          const int w = width - u * 16 < 16 ? width - u * 16 : 16, h = height - v * 16 < 16 ? height - v * 16 : 16;
+          sum += (double)tile_err16[(size_t)v * tx16 + u] * (double)(w * h);
+          px += (double)(w * h);
+        }
+      const double e64 = sum / px;
+      const size_t t = (size_t)j * tx + i;
+      if (tile_err64) tile_err64[t] = e64;
+      noisy[t] = !(e64 <= target);
+    }
+  int n = 0;
+  for (int j = 0; j < ty; j++)
+    for (int i = 0; i < tx; i++) {
+      const size_t t = (size_t)j * tx + i;
+      bool keep = noisy[t] != 0;
+      for (int dj = -1; dilate && !keep && dj <= 1; dj++)
+        for (int di = -1; !keep && di <= 1; di++) {
+          const int a = i + di, b = j + dj;
+          if (a >= 0 && a < tx && b >= 0 && b < ty && noisy[(size_t)b * tx + a]) keep = true;
+        }
+      const bool prev = !prev_active || prev_active[t];
+      active[t] = (prev && keep) ? 1 : 0;
+      n += active[t];
+    }
+  if (n_active) *n_active = n;
+  return SAIL_OK;
+}
+
+int sail_adaptive_defaults(sail_adaptive_params* p) {
+  if (!p) return SAIL_E_INVALID;
+  p->target = INFINITY;
+  p->min_spp = 16;
+  p->max_spp = 1024;
+  p->dilate = 1;
+  return SAIL_OK;
+}
+
+int sail_render_adaptive(sail_ctx* c, const double mvp[16], const float eye[3], int maxBounces, const sail_adaptive_params* params,
+                         sail_adaptive_info* out, sail_until_step* history, int capacity, int* looks, uint32_t* tile_samples) {
+  if (!c) return SAIL_E_INVALID;
+  sail_adaptive_params p;
+  sail_adaptive_defaults(&p);
+  if (params) p = *params;
+  if (!mvp || !eye || !out || p.min_spp < 1 || p.max_spp < p.min_spp || p.max_spp > 2147483647ull || p.target != p.target ||
+      p.dilate < 0 || p.dilate > 1 || capacity < 0)
+    return fail(c, SAIL_E_INVALID, "sail_render_adaptive: bad arguments (min_spp %llu, max_spp %llu, target %g, dilate %d)",
+                (unsigned long long)p.min_spp, (unsigned long long)p.max_spp, p.target, p.dilate);
+  // what the looks and the mask would refuse is refused before anything is rendered
+  if (c->accumMode != SAIL_ACCUM_SUM)
+    return fail(c, SAIL_E_STATE, "sail_render_adaptive: SAIL_ACCUM_MIX and SAIL_ACCUM_COMPAT8 keep no per-pixel sample count");
+  if (!c->haveScene) return fail(c, SAIL_E_STATE, "sail_render_adaptive before sail_set_scene");
+  if (int rc = loadIncomplete(c, "sail_render_adaptive")) return rc;
+  const sail_ctx* h = c->subs.empty() ? c : c->subs[0];  // holds the sample index, the whole mask and the mark
+  const int tx = (c->W + 63) / 64, ty = (c->H + 63) / 64, tiles = tx * ty;
+  const int tx16 = (c->W + 15) / 16, ty16 = (c->H + 15) / 16;
+  auto tilePixels = [&](int t) {
+    const int x0 = (t % tx) * 64, y0 = (t / tx) * 64;
+    return (uint64_t)((c->W - x0) < 64 ? (c->W - x0) : 64) * (uint64_t)((c->H - y0) < 64 ? (c->H - y0) : 64);
+  };
+  std::vector<uint8_t> active((size_t)tiles);
+  int nActive = 0;
+  if (int rc = sail_get_active_tiles(c, active.data(), tiles, &nActive)) return rc;
+  auto activePixels = [&]() {
+    uint64_t px = 0;
+    for (int t = 0; t < tiles; t++) if (active[(size_t)t]) px += tilePixels(t);
+    return px;
+  };
+  sail_stats st0;
+  if (int rc = sail_get_stats(c, &st0)) return rc;
+  uint64_t k = h->k;
+  const uint64_t k0 = k;
+  memset(out, 0, sizeof *out);
+  out->noise.mean = out->noise.max_tile = INFINITY;  // until the first estimate
+  out->noise.k = out->noise.k_mark = k;
+  out->noise.tiles_x = tx16; out->noise.tiles_y = ty16;
+  out->tiles_x = tx; out->tiles_y = ty;
+  int nlooks = 0;
+  bool marked = false;
+  constexpr uint64_t kChunk = 4096;  // as sail_render_until
+  std::vector<float> inv, seeds, err16((size_t)tx16 * ty16);
+  while (nActive > 0) {
+    uint64_t next = k;
+    if (int rc = sail_plan_until(k, p.min_spp, p.max_spp, &next)) return fail(c, rc, "sail_render_adaptive: %s", sail_last_error(nullptr));
+    if (next == k) break;  // at max_spp
+    out->pixel_samples += activePixels() * (next - k);
+    while (k < next) {
+      const int spp = (int)(next - k < kChunk ? next - k : kChunk);
+      inv.resize((size_t)spp * 16);
+      seeds.resize((size_t)spp);
+      if (int rc = sail_schedule(mvp, c->W, c->H, (int)k, spp, inv.data(), seeds.data()))
+        return fail(c, rc, "sail_render_adaptive: sail_schedule failed (a singular camera matrix?)");
+      if (int rc = sail_render_schedule(c, inv.data(), seeds.data(), eye, spp, maxBounces)) return rc;
+      k += (uint64_t)spp;
+    }
+    sail_until_step step{k, INFINITY, INFINITY};
+    if (!marked) {  // the first look only marks: no estimate yet
+      if (int rc = sail_noise_mark(c)) return rc;
+      marked = true;
+      out->noise.k = out->noise.k_mark = k;
+    } else {
+      if (int rc = sail_noise_estimate(c, &out->noise, err16.data(), nullptr, 0)) return rc;
+      step.mean = out->noise.mean; step.max_tile = out->noise.max_tile;
+      if (int rc = sail_plan_adaptive(c->W, c->H, err16.data(), p.target, p.dilate, active.data(), active.data(), nullptr, &nActive))
+        return fail(c, rc, "sail_render_adaptive: %s", sail_last_error(nullptr));
+      if (int rc = sail_set_active_tiles(c, active.data(), tiles)) return rc;
+      // the look it stops at leaves the mark at the look before, for sail_denoise; every other look moves the active
+      // tiles' mark to now
+      if (nActive > 0 && k < p.max_spp)
+        if (int rc = sail_noise_mark(c)) return rc;
+    }
+    if (history && nlooks < capacity) history[nlooks] = step;
+    nlooks++;
+  }
+  sail_stats st1;
+  if (int rc = sail_get_stats(c, &st1)) return rc;
+  out->converged = nActive == 0;
+  out->active_tiles = nActive;
+  out->frame_pixel_samples = (uint64_t)c->W * (uint64_t)c->H * (k - k0);
+  out->kernel_ms = st1.kernel_ms - st0.kernel_ms;
+  if (tile_samples)
+    for (int t = 0; t < tiles; t++)
+      tile_samples[t] = (!h->maskSet || h->mask[(size_t)t]) ? (uint32_t)k : h->frozenAt[(size_t)t];
   if (looks) *looks = nlooks;
   return SAIL_OK;
 }
@@ -3073,6 +3402,9 @@ int sail_load_accum(sail_ctx* c, int part, const float* sums, uint64_t k) {
         if (int rc = sail_load_accum(c->subs[i], part == -1 ? -1 : 0, sums, k)) return relay(c, rc, c->subs[i]);
       } else {
         c->subs[i]->k = k;
+        c->subs[i]->maskSet = false;  // the tile mask goes on every device, as on the ones that load
+        c->subs[i]->mask.clear();
+        c->subs[i]->frozenAt.clear();
       }
     }
     c->loadMissing = missing;

@@ -88,6 +88,9 @@ struct SailTraceArgs {
   // last bounce runs like any other. The room form reads neither.
   uint32_t lastQuietRows;
   int lastSkipSort;
+  // Tile mask (sail_set_active_tiles): ownedTiles global tile indices of this rank's active tiles, ascending; NULL: no
+  // mask, owned tile j is tile rank + j * world
+  const int32_t* tileMap;
 };
 
 // Wavefront split of the pre-cull path (study switch SAIL_DEBUG_WAVEFRONT): the path state of one sample of every

@@ -56,7 +56,7 @@ int sailJitThreads(const SailJitSpec& s) { return s.nt ? s.nt : (s.mode == 1 ? 1
 bool sailJitSpecEqual(const SailJitSpec& a, const SailJitSpec& b) {
   const auto t = [](const SailJitSpec& x) {
     return std::tie(x.ks, x.km, x.kt, x.kl, x.mode, x.waves, x.rows, x.ldsFit, x.tn, x.ns, x.nt, x.types[0], x.types[1], x.types[2],
-                    x.types[3], x.types[4], x.types[5], x.types[6], x.types[7], x.rowWords, x.tpWords, x.rowForm, x.rowShade, x.rowQuiet);
+                    x.types[3], x.types[4], x.types[5], x.types[6], x.types[7], x.rowWords, x.tpWords, x.rowForm, x.rowShade, x.rowQuiet, x.masked);
   };
   return t(a) == t(b);
 }
@@ -70,7 +70,7 @@ struct Key {
   bool operator<(const Key& o) const {
     const auto t = [](const SailJitSpec& x) {
       return std::tie(x.ks, x.km, x.kt, x.kl, x.mode, x.waves, x.rows, x.ldsFit, x.tn, x.ns, x.nt, x.types[0], x.types[1], x.types[2],
-                      x.types[3], x.types[4], x.types[5], x.types[6], x.types[7], x.rowWords, x.tpWords, x.rowForm, x.rowShade, x.rowQuiet);
+                      x.types[3], x.types[4], x.types[5], x.types[6], x.types[7], x.rowWords, x.tpWords, x.rowForm, x.rowShade, x.rowQuiet, x.masked);
     };
     return t(s) < t(o.s);
   }
@@ -128,7 +128,9 @@ std::string defsFor(const SailJitSpec& sp) {
            sp.waves, sp.mode == 1, sp.mode == 2, sp.ks, sp.km, sp.kt, sp.kl, sailJitThreads(sp), sp.rows,
            sp.rows ? types.c_str() : "0", sp.ldsFit, sp.tn, sp.ns);
   // the phase-timing build compiles its run-time kernels instrumented as well (their own g_sailPhase)
-  return (sail_trace_phase_timing ? std::string("#define SAIL_PHASE_TIMING 1\n") : std::string()) + vals + defs;
+  // (an unmasked spec's text is what it was before masks existed)
+  return (sail_trace_phase_timing ? std::string("#define SAIL_PHASE_TIMING 1\n") : std::string()) +
+         (sp.masked ? std::string("#define SAIL_JIT_MASKED 1\n") : std::string()) + vals + defs;
 }
 
 // hipRTC entry points from the toolchain's library (SAIL_HIPRTC, else $ROCM_PATH or /opt/rocm, lib/libhiprtc.so.7)

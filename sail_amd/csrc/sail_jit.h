@@ -29,6 +29,9 @@ struct SailJitSpec {
   // radiance alone (quiet rows, sail_capi.cpp lastBounceRows). Both 0: the kernel is the plain value kernel's code.
   // All 0 in every types spec.
   int rowForm = 0, rowShade = 0, rowQuiet = 0;
+  // 1: the MASKED instances of the spec's kernel pair (sail_trace.hip ownedTileIndex), which a launch under a tile mask
+  // runs: a module of its own, built when a context first launches under a mask
+  int masked = 0;
 };
 bool sailJitSpecEqual(const SailJitSpec& a, const SailJitSpec& b);
 int sailJitThreads(const SailJitSpec& s);  // threads per workgroup of the spec's kernels

@@ -13,4 +13,8 @@ struct SailNoiseArgs {
   int mix;             // 1: S and P hold running means over kf and hf samples (SAIL_ACCUM_MIX); 0: sums with counts in .w
   float kf, hf;        // the context's sample index now and at the mark (MIX)
   int remark;          // 1: P = S in the same pass
+  // optional tile mask (sail_set_active_tiles): one byte per 64x64 tile, tiles64X a row; with it the remark and
+  // sail_noise_copy_kernel write P only in 16x16 tiles whose 64x64 tile is active
+  const uint8_t* active64;
+  int tiles64X;
 };

@@ -12,6 +12,8 @@
 //    LDS as (w0 + w1) + (w2 + w3): a fixed tree of depth 8 and no atomics, so equal data give equal bits;
 //  * lanes outside the frame (ragged tiles) load nothing and add +0;
 //  * with remark each lane stores the float4 of S it just read into P: a doubling schedule costs one pass per look;
+//  * with a tile mask (active64) the workgroup tests its 64x64 tile's byte, uniformly, and the remark store (and
+//    sail_noise_copy_kernel, the masked sail_noise_mark) leaves the P of a frozen tile alone; the estimate reads no mask;
 //  * plain vector stores only.
 // The finite test and the wave count are sail_post.h's; the reduction stays here, since the sum and the count share its
 // one barrier. Lives in its own file: the text of sail_trace.hip is embedded in the library and hashed into every
@@ -45,19 +47,25 @@ __device__ __forceinline__ float noiseError(const float4 s, const float4 p, int 
   return (0.5f * d) / (1e-4f + __builtin_sqrtf(__builtin_fmaxf(l, 0.0f) / 3.0f));
 }
 
+// whether the workgroup's 16x16 tile may write P: no mask, or its 64x64 tile (4 x 4 of these) is active
+__device__ __forceinline__ bool tileWritesMark(const SailNoiseArgs& A) {
+  return !A.active64 || A.active64[(size_t)(blockIdx.y >> 2) * A.tiles64X + (blockIdx.x >> 2)] != 0;
+}
+
 }  // namespace
 
 extern "C" __global__ void __launch_bounds__(256) sail_noise_kernel(SailNoiseArgs A) {
   const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
   float e = 0.0f;
   bool bad = false;
+  const bool remark = A.remark && tileWritesMark(A);
   if (x < A.W && y < A.H) {
     const size_t pix = (size_t)y * A.W + x;
     const float4 s = A.S[pix], p = A.P[pix];
     e = noiseError(s, p, A.mix, A.kf, A.hf);
     if (!sp::finite(e)) { bad = true; e = 0.0f; }  // NaN or Inf: counted, adds nothing
     if (A.pixErr) A.pixErr[pix] = e;
-    if (A.remark) A.P[pix] = s;
+    if (remark) A.P[pix] = s;
   }
   // within the wave: a butterfly, every lane ends with the same sum; the count is a ballot
   float v = e;
@@ -74,6 +82,21 @@ extern "C" __global__ void __launch_bounds__(256) sail_noise_kernel(SailNoiseArg
     A.tileSum[tile] = (sSum[0] + sSum[1]) + (sSum[2] + sSum[3]);
     A.tileBad[tile] = (sBad[0] + sBad[1]) + (sBad[2] + sBad[3]);
   }
+}
+
+// sail_noise_mark under a tile mask: P = S in the 16x16 tiles of active 64x64 tiles, the others keep their P
+extern "C" __global__ void __launch_bounds__(256) sail_noise_copy_kernel(SailNoiseArgs A) {
+  if (!tileWritesMark(A)) return;  // uniform over the workgroup
+  const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
+  if (x < A.W && y < A.H) {
+    const size_t pix = (size_t)y * A.W + x;
+    A.P[pix] = A.S[pix];
+  }
+}
+
+hipError_t sail_launch_noise_copy(const SailNoiseArgs& A, hipStream_t s) {
+  hipLaunchKernelGGL(sail_noise_copy_kernel, dim3((A.W + 15) / 16, (A.H + 15) / 16), dim3(256), 0, s, A);
+  return hipGetLastError();
 }
 
 hipError_t sail_launch_noise(const SailNoiseArgs& A, hipStream_t s) {

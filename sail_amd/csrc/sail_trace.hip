@@ -1746,6 +1746,17 @@ D void accumulateSample(float4& acc, V3 e, const SailSample& S, int mode) {
 // launches (one workgroup per block, every sample) are a separate compile-time instance, so they carry none of
 // the group bookkeeping in registers (sample groups add VGPR/SGPR spills to the flat kernels otherwise).
 struct TileWork { int ownedTile, sub, kBeg, kEnd, bid; };
+// The global 64x64 tile of the launch's owned tile `ownedTile` (< A.ownedTiles): the partition's, or in a MASKED instance
+// (a launch under sail_set_active_tiles' tile mask) the entry of the ascending table of the rank's active tiles.
+// Workgroup-uniform: one scalar load where the tile is computed, nothing of it lives on. Slots (stage, wavefront state)
+// stay indexed by ownedTile. MASKED is a compile-time instance like GROUPED: the unmasked kernels never read
+// A.tileMap, so their text is what it was without masks (a run-time select moved C2 by -0.1 % through register
+// allocation alone).
+template <bool MASKED>
+D int ownedTileIndex(const SailTraceArgs& A, int ownedTile) {
+  if constexpr (MASKED) return A.tileMap[ownedTile];
+  else return A.rank + ownedTile * A.world;
+}
 // A workgroup's pixel block: PX pixels (NT threads / NS samples in flight per pixel), BW x BH, 4096 / PX per 64x64 tile:
 // 16 x NT/16 strips with one sample in flight (NT = 256: 16 x 16; the pre-cull kernels' 1,024: 16 x 64), square blocks
 // otherwise (8 x 8 or 4 x 4 pixels x 4 or 16 samples)
@@ -1853,7 +1864,7 @@ constexpr int kPrioMixed = 2;
 // sooner. The short units end a launch with a short tail without splitting the samples over workgroups (sample groups:
 // every sample's radiance staged in HBM and added in order by sail_accum_kernel); each pixel's NS radiances of a step
 // wait in LDS and its lane adds them in sample order, so the sums are those of one sample at a time, bit for bit.
-template <bool CULL, bool GROUPED, uint32_t KS, uint32_t KM, uint32_t KT, uint32_t KL, int NT, bool FAM, int NS = 1>
+template <bool CULL, bool GROUPED, uint32_t KS, uint32_t KM, uint32_t KT, uint32_t KL, int NT, bool FAM, int NS = 1, bool MASKED = false>
 __device__ __forceinline__ void traceTileCompact(const SailTraceArgs& A) {
   static_assert(NT == 128 || NT == 256 || NT == 512 || NT == 1024, "workgroups of 2, 4, 8 or 16 waves");
   static_assert(NS == 1 || NS == 4 || NS == 16, "samples in flight");
@@ -1889,7 +1900,7 @@ __device__ __forceinline__ void traceTileCompact(const SailTraceArgs& A) {
   const int ownedTile = tw.ownedTile;
   if (ownedTile >= A.ownedTiles) return;  // uniform over the workgroup
   const int sub = tw.sub;
-  const int tile = A.rank + ownedTile * A.world;
+  const int tile = ownedTileIndex<MASKED>(A, ownedTile);
   const int tx = tile % A.tilesX, ty = tile / A.tilesX;
   const int li = threadIdx.x, lane = li & 63, wave = li >> 6;
   const int x0 = tx * 64 + (sub % G::kPerRow) * G::kBW, y0 = ty * 64 + (sub / G::kPerRow) * G::kBH;
@@ -2300,19 +2311,22 @@ __device__ __forceinline__ void traceTileCompact(const SailTraceArgs& A) {
 // Path compaction (traceTileCompact) in every plugin-set kernel: C2 +6 %, C3 +12 %, C4 +10 % (measured;
 // earlier builds with more live state lost to spills in the flat kernels).
 // Each plugin set has an ungrouped kernel (one workgroup per 16 x NT/16 block, every sample) and a _grouped one
-// (sample groups: G workgroups per block, staged radiance added by sail_accum_kernel). Launch bounds: waves per SIMD
+// (sample groups: G workgroups per block, staged radiance added by sail_accum_kernel), and a _masked instance of each
+// for launches under a tile mask (ownedTileIndex). Launch bounds: waves per SIMD
 // and threads per workgroup, chosen by the occupancy sweeps of DESIGN.md §5 (sail_launch_trace sizes the grids).
 // fam: the room family's choices for a flat kernel -- the two-barrier sort, the first sample group accumulating its
 // samples itself (SailTraceArgs.groupHome) and one box record for Cube and Cornellbox.
-#define SAIL_TRACE_KERNELS_NS(name, waves, cull, ks, km, kt, kl, nt, gnt, fam, ns)                                 \
+#define SAIL_TRACE_KERNELS_NS(name, waves, cull, ks, km, kt, kl, nt, gnt, fam, ns, masked)                         \
   extern "C" __global__ void __launch_bounds__(nt, waves) name(SailTraceArgs A) {                                \
-    traceTileCompact<cull, false, ks, km, kt, kl, nt, fam, ns>(A);                                               \
+    traceTileCompact<cull, false, ks, km, kt, kl, nt, fam, ns, masked>(A);                                       \
   }                                                                                                              \
   extern "C" __global__ void __launch_bounds__(gnt, waves) name##_grouped(SailTraceArgs A) {                     \
-    traceTileCompact<cull, true, ks, km, kt, kl, gnt, fam, ns>(A);                                               \
+    traceTileCompact<cull, true, ks, km, kt, kl, gnt, fam, ns, masked>(A);                                       \
   }
-#define SAIL_TRACE_KERNELS(name, waves, cull, ks, km, kt, kl, nt, gnt, fam) \
-  SAIL_TRACE_KERNELS_NS(name, waves, cull, ks, km, kt, kl, nt, gnt, fam, 1)
+// the precompiled pair and its _masked pair
+#define SAIL_TRACE_KERNELS(name, waves, cull, ks, km, kt, kl, nt, gnt, fam)              \
+  SAIL_TRACE_KERNELS_NS(name, waves, cull, ks, km, kt, kl, nt, gnt, fam, 1, false)       \
+  SAIL_TRACE_KERNELS_NS(name##_masked, waves, cull, ks, km, kt, kl, nt, gnt, fam, 1, true)
 #if defined(SAIL_JIT)
 // A per-plugin-set kernel compiled at run time by hipRTC (sail_jit.cpp), like the reference's per-scene program
 // (tracerConfig -> Generator.generate, src/scene/scene.js:70-112, src/shader/generator.js:107-123): the plugin masks,
@@ -2320,12 +2334,16 @@ __device__ __forceinline__ void traceTileCompact(const SailTraceArgs& A) {
 #ifndef SAIL_JIT_NS
 #define SAIL_JIT_NS 1
 #endif
+// SAIL_JIT_MASKED 1: the pair a launch under a tile mask runs, a module of its own under the same kernel names
+#ifndef SAIL_JIT_MASKED
+#define SAIL_JIT_MASKED 0
+#endif
 #if SAIL_JIT_CULL
 SAIL_TRACE_KERNELS_NS(sail_trace_kernel_cull_jit, SAIL_JIT_WAVES, true, SAIL_JIT_KS, SAIL_JIT_KM, SAIL_JIT_KT, SAIL_JIT_KL,
-                      SAIL_JIT_NT, SAIL_JIT_NT, false, SAIL_JIT_NS)
+                      SAIL_JIT_NT, SAIL_JIT_NT, false, SAIL_JIT_NS, SAIL_JIT_MASKED != 0)
 #else
 SAIL_TRACE_KERNELS_NS(sail_trace_kernel_jit, SAIL_JIT_WAVES, false, SAIL_JIT_KS, SAIL_JIT_KM, SAIL_JIT_KT, SAIL_JIT_KL,
-                      SAIL_JIT_NT, SAIL_JIT_NT, SAIL_JIT_FAM != 0, SAIL_JIT_NS)
+                      SAIL_JIT_NT, SAIL_JIT_NT, SAIL_JIT_FAM != 0, SAIL_JIT_NS, SAIL_JIT_MASKED != 0)
 #endif
 #else
 // every plugin (any scene of fewer than 8 primitives outside the two sets below)
@@ -2359,11 +2377,15 @@ namespace {
 struct WfPix { int x, y; bool valid; };
 D WfPix wfPixel(const SailTraceArgs& A, long long slot) {
   const int ownedTile = (int)(slot >> 12), local = (int)(slot & 4095);
-  const int tile = A.rank + ownedTile * A.world;
   WfPix q;
+  q.x = q.y = 0;
+  q.valid = false;
+  if (ownedTile >= A.ownedTiles) return q;  // never past the tile table
+  // (the study path selects at run time: its fifteen kernels per sample have no masked instances)
+  const int tile = A.tileMap ? ownedTileIndex<true>(A, ownedTile) : ownedTileIndex<false>(A, ownedTile);
   q.x = (tile % A.tilesX) * 64 + (local & 63);
   q.y = (tile / A.tilesX) * 64 + (local >> 6);
-  q.valid = ownedTile < A.ownedTiles && q.x < A.W && q.y < A.H;
+  q.valid = q.x < A.W && q.y < A.H;
   return q;
 }
 D Ctx wfCtx(const SailTraceArgs& A) {
@@ -2500,10 +2522,12 @@ hipError_t sail_launch_wavefront(const SailTraceArgs& A, const SailWfState& S, h
 }
 
 // ---- sample groups: add the staged per-sample radiance to the accumulator in sample order ---------------------
-extern "C" __global__ void __launch_bounds__(256) sail_accum_kernel(SailTraceArgs A) {
+namespace {
+template <bool MASKED>
+D void accumStaged(const SailTraceArgs& A) {
   const int bid = (int)blockIdx.x;
   const int ownedTile = bid >> 4, sub = bid & 15;
-  const int tile = A.rank + ownedTile * A.world;
+  const int tile = ownedTileIndex<MASKED>(A, ownedTile);
   const int tx = tile % A.tilesX, ty = tile / A.tilesX;
   const int li = threadIdx.x;
   const int x = tx * 64 + (sub & 3) * 16 + (li & 15), y = ty * 64 + (sub >> 2) * 16 + (li >> 4);
@@ -2532,6 +2556,9 @@ extern "C" __global__ void __launch_bounds__(256) sail_accum_kernel(SailTraceArg
   }
   A.accum[pix] = acc;
 }
+}  // namespace
+extern "C" __global__ void __launch_bounds__(256) sail_accum_kernel(SailTraceArgs A) { accumStaged<false>(A); }
+extern "C" __global__ void __launch_bounds__(256) sail_accum_kernel_masked(SailTraceArgs A) { accumStaged<true>(A); }
 
 // ---- multi-device frame reduction without RCCL (a multi-device context whose devices are all one GPU) ----------
 // dst = ((src0 + src1) + src2) + ...: the sum of the ranks' frames in rank order
@@ -2775,13 +2802,14 @@ extern "C" int sail_phase_read(unsigned long long out[12], int reset) {
 
 // ---- host launch wrappers (called by sail_capi.cpp) ----------------------------------------------------------------
 hipError_t sail_launch_trace(const SailTraceArgs& A, int blocks, hipStream_t s) {
-  const bool g = A.sampleGroups > 1;
-#define SAIL_LAUNCH(k) hipLaunchKernelGGL(g ? k##_grouped : k, dim3(blocks), dim3(256), 0, s, A)
+  const bool g = A.sampleGroups > 1, m = A.tileMap != nullptr;
+#define SAIL_LAUNCH(k) \
+  hipLaunchKernelGGL(m ? (g ? k##_masked##_grouped : k##_masked) : (g ? k##_grouped : k), dim3(blocks), dim3(256), 0, s, A)
   // ungrouped launches of an NT-thread kernel: blocks = ownedTiles * 16 of 256 threads -> ownedTiles * 4096 / NT
 #define SAIL_LAUNCH_NT(k, nt, gnt)                                                              \
   do {                                                                                          \
-    if (g) hipLaunchKernelGGL(k##_grouped, dim3(blocks * 256 / (gnt)), dim3(gnt), 0, s, A);     \
-    else hipLaunchKernelGGL(k, dim3(blocks * 256 / (nt)), dim3(nt), 0, s, A);                     \
+    if (g) hipLaunchKernelGGL(m ? k##_masked##_grouped : k##_grouped, dim3(blocks * 256 / (gnt)), dim3(gnt), 0, s, A); \
+    else hipLaunchKernelGGL(m ? k##_masked : k, dim3(blocks * 256 / (nt)), dim3(nt), 0, s, A);                     \
   } while (0)
   if (A.kernelSet == SAIL_KSET_CORNELL) SAIL_LAUNCH_NT(sail_trace_kernel_cornell, SAIL_CORNELL_NT, SAIL_CORNELL_GROUP_NT);
   else if (A.kernelSet == SAIL_KSET_ROOM) SAIL_LAUNCH_NT(sail_trace_kernel_room, SAIL_ROOM_NT, SAIL_ROOM_GROUP_NT);
@@ -2792,7 +2820,7 @@ hipError_t sail_launch_trace(const SailTraceArgs& A, int blocks, hipStream_t s) 
   return hipGetLastError();
 }
 hipError_t sail_launch_accum(const SailTraceArgs& A, int blocks, hipStream_t s) {
-  hipLaunchKernelGGL(sail_accum_kernel, dim3(blocks), dim3(256), 0, s, A);
+  hipLaunchKernelGGL(A.tileMap ? sail_accum_kernel_masked : sail_accum_kernel, dim3(blocks), dim3(256), 0, s, A);
   return hipGetLastError();
 }
 hipError_t sail_launch_sum(const SailSumArgs& A, hipStream_t s) {

@@ -4,12 +4,14 @@
 // assigns `scene`, then Renderer.update(scene)), render N samples on the GPU and write the frame to disk.
 //
 //   node sail_amd/js/cli.js scene.js [--width 512] [--height 512] [--spp 64] [--bounces 5] [--device -1]
-//        [--noise X [--min-spp 16] [--max-spp 65536]] [--denoise [--denoise-iterations 4] [--albedo [--albedo-grid 2]]]
+//        [--noise X [--adaptive] [--min-spp 16] [--max-spp 65536]] [--denoise [--denoise-iterations 4] [--albedo [--albedo-grid 2]]]
 //        [--filter <name>] [--filter-r 'vec2(2.0,2.0)'] [--gamma 2.2] [--deterministic]
 //        [--png out.png] [--pfm out.pfm] [--exr out.exr] [--stats]
 //
 // --noise X (instead of --spp) renders until the frame's noise estimate is at most X: it looks at --min-spp samples and at
 // every doubling, up to --max-spp. --stats then also prints the spp reached, the noise and whether it converged.
+// --adaptive stops rendering each 64x64 tile once its own error is at most X (and no tile beside it is noisier) and ends
+// when every tile has stopped; --stats then also prints pixel_samples (traced) and frame_pixel_samples (the frame's).
 // --denoise writes the variance-guided a-trous denoiser's image instead of the frame: with --spp N it marks the frame at
 // floor(N/2) samples, with --noise X it uses the mark of the look before the last. --stats then also prints denoise_ms.
 // --albedo divides the frame by the albedo map of the view before the denoiser and multiplies it back afterwards, so that
@@ -34,6 +36,7 @@ function parse(argv) {
       case '--height': opt.height = parseInt(val(), 10); break;
       case '--spp': opt.spp = parseInt(val(), 10); opt.sppGiven = true; break;
       case '--noise': opt.noise = parseFloat(val()); break;
+      case '--adaptive': opt.adaptive = true; break;
       case '--min-spp': opt.minSpp = parseInt(val(), 10); opt.untilGiven = a; break;
       case '--max-spp': opt.maxSpp = parseInt(val(), 10); opt.untilGiven = a; break;
       case '--denoise': opt.denoise = true; break;
@@ -59,6 +62,7 @@ function parse(argv) {
   if (opt.noise !== undefined && opt.sppGiven) throw new Error('--noise and --spp exclude each other');
   if (opt.noise !== undefined && Number.isNaN(opt.noise)) throw new Error('--noise needs a number');
   if (opt.noise === undefined && opt.untilGiven) throw new Error(`${opt.untilGiven} needs --noise`);
+  if (opt.adaptive && opt.noise === undefined) throw new Error('--adaptive needs --noise');
   if (opt.denoiseIterations !== undefined && !opt.denoise) throw new Error('--denoise-iterations needs --denoise');
   if (opt.denoiseIterations !== undefined && !(opt.denoiseIterations >= 1 && opt.denoiseIterations <= 6))
     throw new Error('--denoise-iterations needs a number from 1 to 6');
@@ -84,7 +88,7 @@ function loadScene(file) {
 function main() {
   const opt = parse(process.argv.slice(2));
   if (opt.help || !opt.script) {
-    process.stdout.write(fs.readFileSync(__filename, 'utf8').split('\n').slice(2, 19).map((l) => l.replace(/^\/\/ ?/, '')).join('\n') + '\n');
+    process.stdout.write(fs.readFileSync(__filename, 'utf8').split('\n').slice(2, 21).map((l) => l.replace(/^\/\/ ?/, '')).join('\n') + '\n');
     return opt.help ? 0 : 2;
   }
   const scene = loadScene(opt.script);
@@ -100,7 +104,8 @@ function main() {
   r.update(scene);
   const t0 = process.hrtime.bigint();
   let until = null;
-  if (opt.noise !== undefined) until = r.renderUntil(scene, { noise: opt.noise, minSpp: opt.minSpp, maxSpp: opt.maxSpp });
+  if (opt.adaptive) until = r.renderAdaptive(scene, { noise: opt.noise, minSpp: opt.minSpp, maxSpp: opt.maxSpp });
+  else if (opt.noise !== undefined) until = r.renderUntil(scene, { noise: opt.noise, minSpp: opt.minSpp, maxSpp: opt.maxSpp });
   else if (opt.denoise) {  // the two halves the denoiser compares
     r.renderSamples(scene, Math.floor(opt.spp / 2));
     r.noiseMark();
@@ -125,6 +130,7 @@ function main() {
       ms, segments: st.segments, kernelMs: st.kernelMs, filter: scene.filter.name };
     // (a frame that never reached a second look has no estimate: its noise is infinite, null in JSON)
     if (until) Object.assign(out, { noise: until.mean, converged: until.converged });
+    if (opt.adaptive) Object.assign(out, { pixel_samples: until.pixelSamples, frame_pixel_samples: until.framePixelSamples, active_tiles: until.activeTiles });
     if (den) out.denoise_ms = den.info.kernelMs;
     if (alb) Object.assign(out, { albedo_ms: alb.kernelMs, albedo_grid: alb.grid });
     process.stdout.write(JSON.stringify(out) + '\n');

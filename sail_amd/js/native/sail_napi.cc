@@ -490,6 +490,101 @@ napi_value RenderUntil(napi_env env, napi_callback_info info) {
   NAPI_OK(napi_set_named_property(env, out, "history", list));
   return out;
 }
+// adaptive sampling (sail_set_active_tiles, sail_get_active_tiles, sail_render_adaptive)
+// (ctx, Uint8Array of one byte per 64x64 tile | null: no mask)
+napi_value SetActiveTiles(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  if (!args(env, info, 2, a)) return nullptr;
+  Handle* h;
+  if (!getHandle(env, a[0], &h)) return nullptr;
+  napi_valuetype vt;
+  napi_typeof(env, a[1], &vt);
+  uint8_t* m = nullptr;
+  size_t n = 0;
+  if (!(vt == napi_undefined || vt == napi_null) && !getArray(env, a[1], napi_uint8_array, &m, &n)) return nullptr;
+  if (n > 2147483647u) { napi_throw_range_error(env, nullptr, "too many tiles"); return nullptr; }
+  const int rc = sail_set_active_tiles(h->ctx, m, (int)n);
+  if (rc) return throwSail(env, "sail_set_active_tiles", rc, h->ctx);
+  return nullptr;
+}
+// (ctx) -> Uint8Array, one byte (0 / 1) per 64x64 tile
+napi_value GetActiveTiles(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  if (!args(env, info, 1, a)) return nullptr;
+  Handle* h;
+  if (!getHandle(env, a[0], &h)) return nullptr;
+  const size_t tiles = (size_t)((h->W + 63) / 64) * (size_t)((h->H + 63) / 64);
+  void* p = nullptr;
+  napi_value out = makeTyped(env, napi_uint8_array, tiles, 1, &p);
+  if (!out) return nullptr;
+  const int rc = sail_get_active_tiles(h->ctx, (uint8_t*)p, (int)tiles, nullptr);
+  if (rc) return throwSail(env, "sail_get_active_tiles", rc, h->ctx);
+  return out;
+}
+// (ctx, mvp f64[16] row-major, eye f32[3], bounces, target, minSpp, maxSpp, dilate; undefined or null keeps
+// sail_adaptive_defaults' value) -> {k, mean, maxTile, ..., converged, activeTiles, tiles64X, tiles64Y, pixelSamples,
+// framePixelSamples, traceMs, history, tileSamples: Uint32Array}
+napi_value RenderAdaptive(napi_env env, napi_callback_info info) {
+  napi_value a[8];
+  if (!args(env, info, 8, a)) return nullptr;
+  Handle* h;
+  double* m;
+  float* eye;
+  size_t nm, ne;
+  int b;
+  if (!getHandle(env, a[0], &h) || !getArray(env, a[1], napi_float64_array, &m, &nm) ||
+      !getArray(env, a[2], napi_float32_array, &eye, &ne) || !getInt(env, a[3], &b))
+    return nullptr;
+  if (nm < 16 || ne < 3) { napi_throw_range_error(env, nullptr, "mvp needs 16 doubles and eye 3 floats"); return nullptr; }
+  sail_adaptive_params p;
+  sail_adaptive_defaults(&p);
+  double v[4] = {p.target, (double)p.min_spp, (double)p.max_spp, (double)p.dilate};
+  for (int i = 0; i < 4; i++) {
+    napi_valuetype vt;
+    napi_typeof(env, a[4 + i], &vt);
+    if (vt == napi_undefined || vt == napi_null) continue;
+    if (!getDouble(env, a[4 + i], &v[i])) return nullptr;
+  }
+  if (!(v[1] >= 0.0 && v[1] <= 2147483647.0 && v[2] >= 0.0 && v[2] <= 2147483647.0) || v[1] != (double)(uint64_t)v[1] ||
+      v[2] != (double)(uint64_t)v[2] || !(v[3] == 0.0 || v[3] == 1.0)) {
+    napi_throw_range_error(env, nullptr, "minSpp and maxSpp must be non-negative integers below 2^31, dilate 0 or 1");
+    return nullptr;
+  }
+  p.target = v[0]; p.min_spp = (uint64_t)v[1]; p.max_spp = (uint64_t)v[2]; p.dilate = (int)v[3];
+  const size_t tiles = (size_t)((h->W + 63) / 64) * (size_t)((h->H + 63) / 64);
+  void* pt = nullptr;
+  napi_value tileSamples = makeTyped(env, napi_uint32_array, tiles, 4, &pt);
+  if (!tileSamples) return nullptr;
+  sail_adaptive_info ai;
+  sail_until_step hist[64];
+  int looks = 0;
+  const int rc = sail_render_adaptive(h->ctx, m, eye, b, &p, &ai, hist, 64, &looks, (uint32_t*)pt);
+  if (rc) return throwSail(env, "sail_render_adaptive", rc, h->ctx);
+  napi_value out = noiseObject(env, ai.noise);
+  if (!out) return nullptr;
+  napi_value cv, list;
+  NAPI_OK(napi_get_boolean(env, ai.converged != 0, &cv));
+  NAPI_OK(napi_set_named_property(env, out, "converged", cv));
+  napi_set_named_property(env, out, "activeTiles", num(env, ai.active_tiles));
+  napi_set_named_property(env, out, "tiles64X", num(env, ai.tiles_x));
+  napi_set_named_property(env, out, "tiles64Y", num(env, ai.tiles_y));
+  napi_set_named_property(env, out, "pixelSamples", num(env, (double)ai.pixel_samples));
+  napi_set_named_property(env, out, "framePixelSamples", num(env, (double)ai.frame_pixel_samples));
+  napi_set_named_property(env, out, "traceMs", num(env, ai.kernel_ms));
+  const int nl = looks < 64 ? looks : 64;
+  NAPI_OK(napi_create_array_with_length(env, (size_t)nl, &list));
+  for (int i = 0; i < nl; i++) {
+    napi_value s;
+    NAPI_OK(napi_create_object(env, &s));
+    napi_set_named_property(env, s, "k", num(env, (double)hist[i].k));
+    napi_set_named_property(env, s, "mean", num(env, hist[i].mean));
+    napi_set_named_property(env, s, "maxTile", num(env, hist[i].max_tile));
+    napi_set_element(env, list, (uint32_t)i, s);
+  }
+  NAPI_OK(napi_set_named_property(env, out, "history", list));
+  NAPI_OK(napi_set_named_property(env, out, "tileSamples", tileSamples));
+  return out;
+}
 // an optional amin: undefined or null is the plain call (*have = false)
 bool optionalAmin(napi_env env, napi_value v, bool* have, float* amin) {
   napi_valuetype vt;
@@ -1001,6 +1096,9 @@ napi_value Init(napi_env env, napi_value exports) {
       {"noiseMark", 0, NoiseMark, 0, 0, 0, napi_enumerable, 0},
       {"noise", 0, Noise, 0, 0, 0, napi_enumerable, 0},
       {"renderUntil", 0, RenderUntil, 0, 0, 0, napi_enumerable, 0},
+      {"setActiveTiles", 0, SetActiveTiles, 0, 0, 0, napi_enumerable, 0},
+      {"getActiveTiles", 0, GetActiveTiles, 0, 0, 0, napi_enumerable, 0},
+      {"renderAdaptive", 0, RenderAdaptive, 0, 0, 0, napi_enumerable, 0},
       {"denoise", 0, Denoise, 0, 0, 0, napi_enumerable, 0},
       {"gbuffer", 0, Gbuffer, 0, 0, 0, napi_enumerable, 0},
       {"temporalBegin", 0, TemporalBegin, 0, 0, 0, napi_enumerable, 0},

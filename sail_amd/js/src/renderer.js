@@ -192,6 +192,40 @@ class Renderer {
     if (this.display) this.present();
     return { k: r.k, mean: r.mean, maxTile: r.maxTile, converged: r.converged, history: r.history };
   }
+  // renderUntil with adaptive sampling (sail_render_adaptive): at every look the 64x64 tiles whose own error is at most
+  // `noise` are frozen (with dilate, the default, only when no tile beside them is still noisy) and the rest renders on,
+  // until no tile is active or maxSpp samples are in. Options left out keep the library's defaults (minSpp 16, maxSpp
+  // 1024, dilate true). Returns {k, mean, maxTile, converged, history, activeTiles, tilesX, tilesY (64x64 tiles),
+  // pixelSamples (traced), framePixelSamples (what renderUntil would have traced), traceMs, tileSamples: Uint32Array (the
+  // sample count each tile holds, row 0 = bottom)}. The mask stays set until the frame restarts: see getActiveTiles().
+  renderAdaptive(scene, { noise, minSpp, maxSpp, dilate } = {}) {
+    if (typeof noise !== 'number' || Number.isNaN(noise)) throw new Error('Renderer.renderAdaptive: noise (the target) must be a number');
+    if (this.accumulation !== 'sum')
+      throw new Error("Renderer.renderAdaptive needs accumulation 'sum': the tiles of its frame hold different sample counts");
+    if (scene.moving) { scene.sampleCount = 0; this.updateObjects(scene); }
+    if (scene.sampleCount === 0) this._restart(scene);
+    let r;
+    try {
+      r = this.lib.renderAdaptive(this.ctx, this._mvp(scene), Float32Array.from(scene.eye.elements), this.maxBounces,
+        noise, minSpp, maxSpp, dilate === undefined ? undefined : (dilate ? 1 : 0));
+    } catch (e) {
+      // as renderUntil: the looks rendered before the failure stay in the frame
+      try { scene.sampleCount = this.lib.stats(this.ctx).samples; } catch (e2) { /* the first error is the one to report */ }
+      throw e;
+    }
+    scene.sampleCount = this.lib.stats(this.ctx).samples;
+    if (this.display) this.present();
+    return { k: scene.sampleCount, mean: r.mean, maxTile: r.maxTile, converged: r.converged, history: r.history,
+      activeTiles: r.activeTiles, tilesX: r.tiles64X, tilesY: r.tiles64Y, pixelSamples: r.pixelSamples,
+      framePixelSamples: r.framePixelSamples, traceMs: r.traceMs, tileSamples: r.tileSamples };
+  }
+  // The mask over the frame's 64x64 tiles (sail_set_active_tiles): one entry per tile, row 0 = bottom, truthy = traced;
+  // null or undefined removes it. Everything that restarts the frame removes it too.
+  setActiveTiles(active) {
+    if (active === null || active === undefined) { this.lib.setActiveTiles(this.ctx, null); return; }
+    this.lib.setActiveTiles(this.ctx, Uint8Array.from(active, (v) => (v ? 1 : 0)));
+  }
+  getActiveTiles() { return this.lib.getActiveTiles(this.ctx); }
   // the noise estimate by hand: noiseMark() snapshots the frame, noise() compares the frame with the snapshot
   // ({mean, maxTile, k, kMark, nonfinite, tilesX, tilesY, kernelMs, tileErr?}); remark moves the mark to now
   noiseMark() { this.lib.noiseMark(this.ctx); }
