@@ -131,6 +131,55 @@ struct TexView {
 // union of the primitives' finite bounds and its diagonal (sceneBox)
 struct SceneBox { double lo[3], hi[3]; double diag; };
 
+// One run-time kernel of a context: the spec it holds (sail_jit_hold), whether its code object is still being built, is
+// loaded or failed, the loaded pair, and why a build failed. The hold is what keeps the build worker from skipping the
+// spec's queued build and, for a value spec, what keeps its module loaded: it is taken, polled and released here only.
+struct JitSlot {
+  bool have = false;
+  SailJitSpec spec;
+  int state = SAIL_KERNEL_JIT_NONE;
+  SailJitKernel k;
+  std::string error;
+
+  // The loaded pair, waiting up to wait_ms for its build (-1: until it is done); false while nothing is held, while the
+  // build is still running, and once it has failed (the caller's next tier then runs, with the same results)
+  bool poll(int device, int wait_ms, SailJitKernel* out = nullptr) {
+    if (!have || state == SAIL_KERNEL_JIT_FAILED) return false;
+    if (state != SAIL_KERNEL_JIT_READY) {
+      std::string err;
+      const int r = sail_jit_kernels(device, spec, wait_ms, &k, &err);
+      if (r == 1) return false;
+      if (r < 0) { state = SAIL_KERNEL_JIT_FAILED; error = err; return false; }
+      state = SAIL_KERNEL_JIT_READY;
+    }
+    if (out) *out = k;
+    return true;
+  }
+  // Release the hold and clear the slot. The last hold on a value spec unloads the module (sail_jit_hold): no launch of
+  // a loaded kernel may still be running on the context's stream.
+  void drop(int device, hipStream_t stream) {
+    if (have) {
+      if (state == SAIL_KERNEL_JIT_READY && stream) {
+        (void)hipSetDevice(device);
+        (void)hipStreamSynchronize(stream);
+      }
+      sail_jit_hold(device, spec, -1);
+    }
+    *this = JitSlot{};
+  }
+  // Hold `s` (not a reference into this slot) and ask for it once without waiting: the build starts in the background,
+  // or the object loads here when a disk cache has it. A spec held before goes as in drop, but only after the new one is
+  // held: a build both share is never skipped in between.
+  void adopt(int device, hipStream_t stream, const SailJitSpec& s) {
+    sail_jit_hold(device, s, +1);
+    drop(device, stream);
+    have = true;
+    spec = s;
+    state = SAIL_KERNEL_JIT_PENDING;
+    (void)poll(device, 0);
+  }
+};
+
 struct sail_ctx {
   int device = 0, W = 0, H = 0;
   uint32_t flags = 0;
@@ -173,16 +222,11 @@ struct sail_ctx {
   int forceGeneric = 0;  // SAIL_FORCE_GENERIC=1: always launch the all-plugin kernel (tests)
   int forceGroups = 0;   // SAIL_SAMPLE_GROUPS=g: fixed sample-group count (tests); 0 = by occupancy
   int wavefront = 0;     // SAIL_DEBUG_WAVEFRONT: the pre-cull path by the wavefront split (study)
-  int jit = 59;  // SAIL_DEBUG_JIT bits: which scenes get a run-time kernel (jitKernels; instrumented in the phase build)
-  // The scene's run-time kernel (refreshJit): its spec, and whether it is still being built, loaded or failed. Until it
-  // is loaded the precompiled kernel of the scene's set serves (same results); a launch waits up to jitWait ms for it
-  // (SAIL_DEBUG_JIT_WAIT; -1 until it is built).
-  bool jitHave = false;
-  SailJitSpec jitSpec;
-  int jitMode = 0;
-  int jitState = SAIL_KERNEL_JIT_NONE;
-  SailJitKernel jitK;
-  std::string jitError;  // why the scene's run-time kernel failed (sail_get_kernel_info)
+  int jit = 59;  // SAIL_DEBUG_JIT bits: which scenes get a run-time kernel (jitSpecFor; instrumented in the phase build)
+  // The scene's run-time kernel (refreshJit), compiled for its plugin set and its rows' types. Until it is loaded the
+  // precompiled kernel of the scene's set serves (same results); a launch waits up to jitWait ms for it
+  // (SAIL_DEBUG_JIT_WAIT; -1 until it is built). Its error is the one sail_get_kernel_info reports.
+  JitSlot typesSlot;
   int jitWait = 0;
   int jitNt = 0;  // SAIL_DEBUG_JIT_NT: threads per workgroup of the run-time kernels (0: the form's own)
   int jitNs = 0;  // SAIL_DEBUG_JIT_NS: samples in flight of the run-time kernels (0: the form's default, jitNsFor)
@@ -194,20 +238,13 @@ struct sail_ctx {
   int jitValuesAfter = 256;
   uint64_t settled = 0;
   std::vector<uint32_t> rowWords;  // the decoded rows as uploaded (uploadPrims), 32 words each
-  bool valHave = false;
-  SailJitSpec valSpec;
-  int valState = SAIL_KERNEL_JIT_NONE;
-  SailJitKernel valK;
+  JitSlot valueSlot;
   bool lastMasked = false;  // the last trace launch ran a _masked instance (a tile mask was set)
   // The MASKED instances of the scene's run-time kernels (SailJitSpec.masked), asked for at the first launch under a tile
-  // mask: slot 0 follows the types spec, slot 1 the value spec. Built in the background like their unmasked twins; until
-  // one is loaded a masked launch runs the precompiled _masked kernel of the scene's set, with the same results.
-  struct MaskedJit {
-    bool have = false;
-    SailJitSpec spec;
-    int state = SAIL_KERNEL_JIT_NONE;
-    SailJitKernel k;
-  } maskedJit[2];
+  // mask (maskedTwin): one follows the types spec, one the value spec, and each goes before the slot it follows. Built in
+  // the background like their unmasked twins; until one is loaded a masked launch runs the precompiled _masked kernel of
+  // the scene's set, with the same results.
+  JitSlot typesTwin, valueTwin;
   bool lastJit = false;  // the last trace launch ran a run-time compiled kernel (sail_kernel_name)
   int lastJitMode = 0;
   uint64_t lastBuildId = 0;  // the run-time kernel's build identity (sail_get_kernel_info)
@@ -342,6 +379,25 @@ int loadIncomplete(sail_ctx* c, const char* what) {
     if (e_ != hipSuccess) return fail((ctx), SAIL_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
   } while (0)
 
+// A device buffer allocated on first use and kept for the context's life (sail_destroy frees it)
+template <class T>
+int allocOnce(sail_ctx* c, T** p, size_t bytes, const char* what) {
+  if (*p) return SAIL_OK;
+  if (hipMalloc(p, bytes) != hipSuccess) { *p = nullptr; return fail(c, SAIL_E_OOM, "%s", what); }
+  return SAIL_OK;
+}
+// A grow-only device buffer of *size units: a request for more waits for the stream (launches in flight read the old
+// one), frees it and allocates `bytes` anew
+template <class T, class N>
+int growBuffer(sail_ctx* c, T** p, N* size, N need, size_t bytes, const char* what) {
+  if (need <= *size) return SAIL_OK;
+  if (*p) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(*p)); *p = nullptr; }
+  *size = 0;
+  if (hipMalloc(p, bytes) != hipSuccess) { *p = nullptr; return fail(c, SAIL_E_OOM, "%s", what); }
+  *size = need;
+  return SAIL_OK;
+}
+
 // the smallest precompiled plugin-set kernel that covers the scene (sail_device.h SAIL_KSET_*)
 int kernelSetFor(const sail_ctx* c) {
   if (c->forceGeneric || c->n >= c->cullMinPrims) return SAIL_KSET_GENERIC;
@@ -365,6 +421,14 @@ int jitWaves(int mode, int kernelSet) {
   if (mode == SAIL_JIT_MODE_ROOM) return kernelSet == SAIL_KSET_ROOM ? 7 : 8;
   return kernelSet == SAIL_KSET_CORNELL ? 8 : 6;
 }
+// the tiles of this rank's share of the partition
+int partitionTiles(const sail_ctx* c, int* tilesX, int* tilesY) {
+  const int tx = (c->W + 63) / 64, ty = (c->H + 63) / 64;
+  *tilesX = tx; *tilesY = ty;
+  if (c->partMode == SAIL_PART_SAMPLES) return tx * ty;
+  const int total = tx * ty;
+  return c->rank < total ? (total - c->rank + c->world - 1) / c->world : 0;
+}
 // Workgroup shape of a run-time kernel by form (profiles/r05_ns_*.jsonl, r05_nt*_C1.jsonl; 1080p / 4K, 64-sample
 // launches, bit-identical): the Cornell form at 512 threads holding 16 samples of 32 pixels (C1 98.6 Gseg/s against 97.5-98.1
 // at 256 threads x 1 sample with 8 staged sample groups: no stage and no sail_accum_kernel at full frame; 512 x 1 sample,
@@ -376,7 +440,6 @@ int jitWaves(int mode, int kernelSet) {
 // groups instead (C2 per GPU at N = 8: 95.4 Gseg/s against 92.1 with 16 samples and no groups, 91.4 with both; at
 // N = 4 95.2 against 94.9; profiles/r05_scale_ns_c2.jsonl, tools/scale_groups.sh).
 // (the share is the partition's, whatever tile mask is set: a mask must not swap the scene's kernel for another build)
-int partitionTiles(const sail_ctx* c, int* tilesX, int* tilesY);
 bool cornellShareLarge(const sail_ctx* c) {
   int tx, ty;
   const int owned = partitionTiles(c, &tx, &ty);
@@ -438,66 +501,75 @@ bool jitSpecFor(const sail_ctx* c, SailJitSpec* out, int* mode) {
   return true;
 }
 // The rows changed, or the spec their value kernel was derived from: the hold on the value spec goes (a queued build of it
-// is skipped, a finished one stays in the caches for a scene that returns to this pose), launches run the types kernel
-// again, and the settle count restarts.
-// the hold on a masked twin goes with the spec it follows (dropValues, refreshJit, sail_destroy)
-void dropMaskedJit(sail_ctx* c, int slot) {
-  sail_ctx::MaskedJit& m = c->maskedJit[slot];
-  if (m.have) {
-    // the last hold unloads the module (sail_jit_hold): no launch of it may still be running on this context's stream
-    if (m.state == SAIL_KERNEL_JIT_READY && c->stream) {
-      (void)hipSetDevice(c->device);
-      (void)hipStreamSynchronize(c->stream);
-    }
-    sail_jit_hold(c->device, m.spec, -1);
-  }
-  m = sail_ctx::MaskedJit{};
-}
-// The loaded masked twin of `base` in `slot`, waiting up to wait_ms for its build; false while it is being built or when
-// it failed
-bool maskedKernels(sail_ctx* c, int slot, const SailJitSpec& base, int wait_ms, SailJitKernel* k) {
-  sail_ctx::MaskedJit& m = c->maskedJit[slot];
-  SailJitSpec want = base;
-  want.masked = 1;
-  if (m.have && !sailJitSpecEqual(m.spec, want)) dropMaskedJit(c, slot);
-  if (!m.have) {
-    sail_jit_hold(c->device, want, +1);
-    m.have = true;
-    m.spec = want;
-    m.state = SAIL_KERNEL_JIT_PENDING;
-  }
-  if (m.state == SAIL_KERNEL_JIT_FAILED) return false;
-  if (m.state != SAIL_KERNEL_JIT_READY) {
-    std::string err;
-    const int r = sail_jit_kernels(c->device, m.spec, wait_ms, &m.k, &err);
-    if (r == 1) return false;
-    if (r < 0) { m.state = SAIL_KERNEL_JIT_FAILED; return false; }
-    m.state = SAIL_KERNEL_JIT_READY;
-  }
-  *k = m.k;
-  return true;
-}
+// is skipped, a finished one stays in the caches for a scene that returns to this pose), its masked twin's first, launches
+// run the types kernel again, and the settle count restarts.
 void dropValues(sail_ctx* c) {
-  dropMaskedJit(c, 1);
-  if (c->valHave) {
-    // the last hold unloads the module (sail_jit_hold): no launch of it may still be running on this context's stream
-    if (c->valState == SAIL_KERNEL_JIT_READY && c->stream) {
-      (void)hipSetDevice(c->device);
-      (void)hipStreamSynchronize(c->stream);
-    }
-    sail_jit_hold(c->device, c->valSpec, -1);
-  }
-  c->valHave = false;
-  c->valSpec = SailJitSpec{};
-  c->valState = SAIL_KERNEL_JIT_NONE;
-  c->valK = SailJitKernel{};
+  c->valueTwin.drop(c->device, c->stream);
+  c->valueSlot.drop(c->device, c->stream);
   c->settled = 0;
 }
 // Whether the value kernel of a scene that rendered `settled` samples since its rows changed is asked for now
 // (sail_plan_settle; after: SAIL_DEBUG_JIT_VALUES_AFTER)
 bool settledFor(uint64_t settled, int after) { return after >= 0 && settled >= (uint64_t)after; }
+// What a path's last bounce can add at a hit on each row (SailTraceArgs.lastQuietRows / lastSkipSort), decided with
+// the kernel's own tests and f32 operations on the values it reads (sail_trace.hip shadeLast: emission, matCat,
+// matRow -> kd, sigma, the Cornellbox wall constants or the uniform texture's colour). `lights`: the kernel that will
+// run has a light plugin compiled in (shadeLast then declines every lit matte hit).
+//   quiet: the emission words are +0.0f bit for bit (the facing test can only zero them again), and the row is not a
+//     matte, or it is one whose light term is fma(f, 0, 0) with f = (kd * sc) * (1 / pi) finite for every colour sc the
+//     record can give it: +0. Its update is e + (+0) * throughput whatever the record says.
+//   record-only: shadeLast accepts every hit on the row, but the value depends on the record (an emitter's facing test,
+//     a non-finite f).
+//   full: shadeLast can decline (a light plugin, Oren-Nayar), or the matte's colour is not a per-scene constant.
+// Rows of more than 32-row scenes are not classified (the pre-cull kernels take none of this); a row no ray can hit
+// (type 0) has no class. skipSort: no full row, and every record-only row emits (a black one is a matte whose light
+// term is not +0: those keep the sort). Anything this cannot decide is full.
 void lastBounceRows(const std::vector<SailPrim>& prims, const float* tp, int tn, uint32_t matMask, bool lights,
-                    uint32_t* quietRows, int* skipSort);  // below
+                    uint32_t* quietRows, int* skipSort) {
+  *quietRows = 0;
+  *skipSort = 0;
+  const int n = (int)prims.size();
+  if (n < 1 || n > 32 || tn < 1 || !tp) return;
+  constexpr float kEps = 1e-5f, kInvPI = 0.3183098861837907f;  // sail_trace.hip
+  bool skip = true, any = false;
+  for (int i = 0; i < n; i++) {
+    const SailPrim& p = prims[(size_t)i];
+    if (p.type == 0) continue;
+    any = true;
+    uint32_t eb[3];
+    memcpy(eb, p.em, sizeof eb);
+    const bool emPosZero = (eb[0] | eb[1] | eb[2]) == 0u;
+    const bool emBlack = p.em[0] == 0.0f && p.em[1] == 0.0f && p.em[2] == 0.0f;  // isBlack: -0 too, never NaN
+    const bool matte = (int)(short)(p.cats & 0xffff) == SAIL_MATTE;
+    bool matteOk = true;  // a lit matte hit on the row adds exactly +0
+    if (matte) {
+      const bool rowsOk = p.matRow >= 0 && p.matRow < tn && p.texRow >= 0 && p.texRow < tn;
+      if (lights || !rowsOk) {
+        matteOk = false;
+      } else if ((matMask >> SAIL_MATTE) & 1u) {  // material()'s matte branch; without the plugin f stays +0
+        const float kd = tp[(size_t)p.matRow * 16 + 1], sigma = tp[(size_t)p.matRow * 16 + 2];
+        float sc[4][3] = {{0.25f, 0.75f, 0.25f}, {0.25f, 0.25f, 0.75f}, {1.0f, 1.0f, 1.0f}, {0.0f, 0.0f, 0.0f}};
+        int ncol = 0;
+        if (p.type == SAIL_CORNELLBOX) {
+          ncol = 4;
+        } else if ((p.cats >> 16) == SAIL_TEX_UNIFORM) {
+          for (int k = 0; k < 3; k++) sc[0][k] = tp[(size_t)p.texRow * 16 + 1 + k];
+          ncol = 1;
+        }
+        matteOk = sigma < kEps && ncol > 0;
+        for (int q = 0; q < ncol; q++)
+          for (int k = 0; k < 3; k++) {
+            volatile float f = kd * sc[q][k];  // two roundings, as the kernel's (kd * sc) * kInvPI
+            f = f * kInvPI;
+            if (!std::isfinite((float)f)) matteOk = false;
+          }
+      }
+    }
+    if (emPosZero && matteOk) *quietRows |= 1u << i;
+    else if (!(matteOk && !emBlack)) skip = false;
+  }
+  *skipSort = (any && skip) ? 1 : 0;
+}
 // The value spec of a types spec: the flat form compiled for rows, with a texParams table small enough to compile in.
 // Scenes of the Cornell plugin set only (cubes, spheres, the box; matte and mirror; no textures, no lights): the form
 // that was measured and that the parity tests run with constant rows. A flat-form kernel of a wider set (SAIL_DEBUG_JIT
@@ -534,32 +606,12 @@ bool valueSpecFor(const SailJitSpec& types, const std::vector<uint32_t>& rowWord
 }
 // Ask for the scene's value kernel once it has settled (after every refreshJit, and between and after launches): the build
 // starts in the background, or the object loads here when a disk cache has it, as refreshJit does for the types kernel.
+// When it fails the types kernel serves.
 void refreshValues(sail_ctx* c) {
-  if (!c->subs.empty() || c->valHave || !c->jitHave || !settledFor(c->settled, c->jitValuesAfter)) return;
+  if (!c->subs.empty() || c->valueSlot.have || !c->typesSlot.have || !settledFor(c->settled, c->jitValuesAfter)) return;
   SailJitSpec spec;
-  if (!valueSpecFor(c->jitSpec, c->rowWords, c->tpRows.data(), c->tn, c->jit, &spec)) return;
-  sail_jit_hold(c->device, spec, +1);
-  c->valHave = true;
-  c->valSpec = spec;
-  c->valState = SAIL_KERNEL_JIT_PENDING;
-  std::string err;
-  const int r = sail_jit_kernels(c->device, spec, 0, &c->valK, &err);
-  if (r == 0) c->valState = SAIL_KERNEL_JIT_READY;
-  else if (r < 0) c->valState = SAIL_KERNEL_JIT_FAILED;  // the types kernel serves
-}
-// The loaded value kernel, waiting up to wait_ms for its build (launches pass 0: none waits for it)
-bool valueKernels(sail_ctx* c, int wait_ms, SailJitKernel* k, int* mode) {
-  if (!c->valHave || c->valState == SAIL_KERNEL_JIT_FAILED) return false;
-  if (c->valState != SAIL_KERNEL_JIT_READY) {
-    std::string err;
-    const int r = sail_jit_kernels(c->device, c->valSpec, wait_ms, &c->valK, &err);
-    if (r == 1) return false;
-    if (r < 0) { c->valState = SAIL_KERNEL_JIT_FAILED; return false; }
-    c->valState = SAIL_KERNEL_JIT_READY;
-  }
-  *k = c->valK;
-  *mode = c->jitMode;
-  return true;
+  if (!valueSpecFor(c->typesSlot.spec, c->rowWords, c->tpRows.data(), c->tn, c->jit, &spec)) return;
+  c->valueSlot.adopt(c->device, c->stream, spec);
 }
 // Re-derive the scene's run-time kernel after anything it depends on changed (scene, rows, switches). A new spec starts
 // its background build now (Tracer.update links the scene's program, tracer.js:42-90), so the caller never waits for it.
@@ -570,39 +622,34 @@ void refreshJit(sail_ctx* c) {
   SailJitSpec spec;
   int mode = 0;
   const bool have = jitSpecFor(c, &spec, &mode);
-  if (have == c->jitHave && (!have || sailJitSpecEqual(spec, c->jitSpec))) return;
+  if (have == c->typesSlot.have && (!have || sailJitSpecEqual(spec, c->typesSlot.spec))) return;
   dropValues(c);  // the value kernel is the old spec's
-  dropMaskedJit(c, 0);  // and so is the types kernel's masked twin
-  // hold the new spec before dropping the old one: a build both share is never skipped in between
-  if (have) sail_jit_hold(c->device, spec, +1);
-  if (c->jitHave) sail_jit_hold(c->device, c->jitSpec, -1);
-  c->jitHave = have;
-  c->jitSpec = spec;
-  c->jitMode = mode;
-  c->jitK = SailJitKernel{};
-  c->jitError.clear();
-  c->jitState = have ? SAIL_KERNEL_JIT_PENDING : SAIL_KERNEL_JIT_NONE;
-  if (!have) return;
-  std::string err;
-  const int r = sail_jit_kernels(c->device, spec, 0, &c->jitK, &err);  // starts the build; loads it if it is cached
-  if (r == 0) c->jitState = SAIL_KERNEL_JIT_READY;
-  else if (r < 0) { c->jitState = SAIL_KERNEL_JIT_FAILED; c->jitError = err; }
+  c->typesTwin.drop(c->device, c->stream);  // and so is the types kernel's masked twin
+  if (have) c->typesSlot.adopt(c->device, c->stream, spec);
+  else c->typesSlot.drop(c->device, c->stream);
 }
-// The run-time compiled kernel of the scene's plugin set (sail_jit.cpp), waiting up to wait_ms for its build; false when
-// none applies, it is still being built or it failed (the precompiled kernel of the scene's set then runs, with the same
-// results). *mode: SAIL_JIT_MODE_*.
-bool jitKernels(sail_ctx* c, int wait_ms, SailJitKernel* k, int* mode) {
-  if (!c->jitHave || c->jitState == SAIL_KERNEL_JIT_FAILED) return false;
-  if (c->jitState != SAIL_KERNEL_JIT_READY) {
-    std::string err;
-    const int r = sail_jit_kernels(c->device, c->jitSpec, wait_ms, &c->jitK, &err);
-    if (r == 1) return false;
-    if (r < 0) { c->jitState = SAIL_KERNEL_JIT_FAILED; c->jitError = err; return false; }
-    c->jitState = SAIL_KERNEL_JIT_READY;
+// The masked twin of the loaded kernel in `base`, held in `twin`: asked for at the first launch under a tile mask, and
+// anew when the base's spec changed. Launches wait up to jitWait for it, as for the types kernel; null while it is being
+// built or when it failed.
+JitSlot* maskedTwin(sail_ctx* c, JitSlot& twin, const JitSlot& base) {
+  SailJitSpec want = base.spec;
+  want.masked = 1;
+  if (!twin.have || !sailJitSpecEqual(twin.spec, want)) twin.adopt(c->device, c->stream, want);
+  return twin.poll(c->device, c->jitWait) ? &twin : nullptr;
+}
+// The slot whose kernel a launch runs, or null: the precompiled kernel of the scene's set then runs (its _masked instance
+// under a tile mask), with the same results. The value kernel when it is loaded, else the types kernel, waited for up to
+// jitWait; under a tile mask the masked twin of the first of the two that is loaded and whose twin is. No launch waits
+// for the value kernel itself: it is a bonus of a scene at rest, and its build may take longer than the render. None
+// under the wavefront switch.
+JitSlot* runningSlot(sail_ctx* c, bool masked, bool wavefront) {
+  if (wavefront) return nullptr;
+  if (c->valueSlot.poll(c->device, 0)) {
+    JitSlot* s = masked ? maskedTwin(c, c->valueTwin, c->valueSlot) : &c->valueSlot;
+    if (s) return s;
   }
-  *k = c->jitK;
-  *mode = c->jitMode;
-  return true;
+  if (c->typesSlot.poll(c->device, c->jitWait)) return masked ? maskedTwin(c, c->typesTwin, c->typesSlot) : &c->typesSlot;
+  return nullptr;
 }
 // Samples per launch when the host has not fixed them: the Cornell form holding 16 samples in flight runs a whole
 // 1,024-sample frame in one launch (its waves live 16 times longer, so their per-wave start -- the spill stores of the
@@ -611,15 +658,8 @@ bool jitKernels(sail_ctx* c, int wait_ms, SailJitKernel* k, int* mode) {
 // samples, which a larger launch would push past the stage's cap).
 int launchSamples(const sail_ctx* c) {
   if (c->launchSpp > 0) return c->launchSpp;
-  return (c->jitHave && c->jitState != SAIL_KERNEL_JIT_FAILED && c->jitSpec.ns >= 16) ? 1024 : 64;
-}
-// the tiles of this rank's share of the partition
-int partitionTiles(const sail_ctx* c, int* tilesX, int* tilesY) {
-  const int tx = (c->W + 63) / 64, ty = (c->H + 63) / 64;
-  *tilesX = tx; *tilesY = ty;
-  if (c->partMode == SAIL_PART_SAMPLES) return tx * ty;
-  const int total = tx * ty;
-  return c->rank < total ? (total - c->rank + c->world - 1) / c->world : 0;
+  const JitSlot& t = c->typesSlot;
+  return (t.have && t.state != SAIL_KERNEL_JIT_FAILED && t.spec.ns >= 16) ? 1024 : 64;
 }
 // the tiles a launch traces, and their in-frame pixels: the share, or with a tile mask its active tiles (tileMap)
 int ownedTiles(const sail_ctx* c, int* tilesX, int* tilesY) {
@@ -910,66 +950,6 @@ void fillCats(std::vector<SailPrim>& prims, const float* texparams, int tn) {
     p.cats = (int32_t)(((uint32_t)(uint16_t)(int16_t)cat(p.matRow)) | ((uint32_t)(uint16_t)(int16_t)cat(p.texRow) << 16));
 }
 
-// What a path's last bounce can add at a hit on each row (SailTraceArgs.lastQuietRows / lastSkipSort), decided with
-// the kernel's own tests and f32 operations on the values it reads (sail_trace.hip shadeLast: emission, matCat,
-// matRow -> kd, sigma, the Cornellbox wall constants or the uniform texture's colour). `lights`: the kernel that will
-// run has a light plugin compiled in (shadeLast then declines every lit matte hit).
-//   quiet: the emission words are +0.0f bit for bit (the facing test can only zero them again), and the row is not a
-//     matte, or it is one whose light term is fma(f, 0, 0) with f = (kd * sc) * (1 / pi) finite for every colour sc the
-//     record can give it: +0. Its update is e + (+0) * throughput whatever the record says.
-//   record-only: shadeLast accepts every hit on the row, but the value depends on the record (an emitter's facing test,
-//     a non-finite f).
-//   full: shadeLast can decline (a light plugin, Oren-Nayar), or the matte's colour is not a per-scene constant.
-// Rows of more than 32-row scenes are not classified (the pre-cull kernels take none of this); a row no ray can hit
-// (type 0) has no class. skipSort: no full row, and every record-only row emits (a black one is a matte whose light
-// term is not +0: those keep the sort). Anything this cannot decide is full.
-void lastBounceRows(const std::vector<SailPrim>& prims, const float* tp, int tn, uint32_t matMask, bool lights,
-                    uint32_t* quietRows, int* skipSort) {
-  *quietRows = 0;
-  *skipSort = 0;
-  const int n = (int)prims.size();
-  if (n < 1 || n > 32 || tn < 1 || !tp) return;
-  constexpr float kEps = 1e-5f, kInvPI = 0.3183098861837907f;  // sail_trace.hip
-  bool skip = true, any = false;
-  for (int i = 0; i < n; i++) {
-    const SailPrim& p = prims[(size_t)i];
-    if (p.type == 0) continue;
-    any = true;
-    uint32_t eb[3];
-    memcpy(eb, p.em, sizeof eb);
-    const bool emPosZero = (eb[0] | eb[1] | eb[2]) == 0u;
-    const bool emBlack = p.em[0] == 0.0f && p.em[1] == 0.0f && p.em[2] == 0.0f;  // isBlack: -0 too, never NaN
-    const bool matte = (int)(short)(p.cats & 0xffff) == SAIL_MATTE;
-    bool matteOk = true;  // a lit matte hit on the row adds exactly +0
-    if (matte) {
-      const bool rowsOk = p.matRow >= 0 && p.matRow < tn && p.texRow >= 0 && p.texRow < tn;
-      if (lights || !rowsOk) {
-        matteOk = false;
-      } else if ((matMask >> SAIL_MATTE) & 1u) {  // material()'s matte branch; without the plugin f stays +0
-        const float kd = tp[(size_t)p.matRow * 16 + 1], sigma = tp[(size_t)p.matRow * 16 + 2];
-        float sc[4][3] = {{0.25f, 0.75f, 0.25f}, {0.25f, 0.25f, 0.75f}, {1.0f, 1.0f, 1.0f}, {0.0f, 0.0f, 0.0f}};
-        int ncol = 0;
-        if (p.type == SAIL_CORNELLBOX) {
-          ncol = 4;
-        } else if ((p.cats >> 16) == SAIL_TEX_UNIFORM) {
-          for (int k = 0; k < 3; k++) sc[0][k] = tp[(size_t)p.texRow * 16 + 1 + k];
-          ncol = 1;
-        }
-        matteOk = sigma < kEps && ncol > 0;
-        for (int q = 0; q < ncol; q++)
-          for (int k = 0; k < 3; k++) {
-            volatile float f = kd * sc[q][k];  // two roundings, as the kernel's (kd * sc) * kInvPI
-            f = f * kInvPI;
-            if (!std::isfinite((float)f)) matteOk = false;
-          }
-      }
-    }
-    if (emPosZero && matteOk) *quietRows |= 1u << i;
-    else if (!(matteOk && !emBlack)) skip = false;
-  }
-  *skipSort = (any && skip) ? 1 : 0;
-}
-
 void decodePrims(const float* objects, int n, int tn, uint32_t shapeMask, std::vector<SailPrim>& out, int* anyHitOk,
                  SceneBox* sbOut) {
   std::vector<PrimBox> raw((size_t)n);
@@ -1044,13 +1024,11 @@ void decodePrims(const float* objects, int n, int tn, uint32_t shapeMask, std::v
 int ensureSamples(sail_ctx* c, int count) {
   if (count <= c->samplesCap) return SAIL_OK;
   c->samplesPos = 0;
-  if (c->samples) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(c->samples)); c->samples = nullptr; }
   int cap = 4096;  // 256 KB: thousands of one-sample frames before the ring wraps
   while (cap < count) cap *= 2;
+  if (int rc = growBuffer(c, &c->samples, &c->samplesCap, cap, sizeof(SailSample) * cap, "sample buffer")) return rc;
   if (c->samplesPinned) { (void)hipHostFree(c->samplesPinned); c->samplesPinned = nullptr; }
-  if (hipMalloc(&c->samples, sizeof(SailSample) * cap) != hipSuccess) return fail(c, SAIL_E_OOM, "sample buffer");
   if (hipHostMalloc(&c->samplesPinned, sizeof(SailSample) * cap) != hipSuccess) c->samplesPinned = nullptr;
-  c->samplesCap = cap;
   return SAIL_OK;
 }
 
@@ -1106,24 +1084,13 @@ int launchTrace(sail_ctx* c, const SailSample* hs, int count, int maxBounces) {
     // = 1,016 workgroups = 4 waves per SIMD); split the launch's samples over G workgroups per block so
     // that about 4 rounds of 7-wave-per-SIMD residency are queued, and add the staged samples in order.
     const bool wavefront = c->wavefront && A.kernelSet == SAIL_KSET_GENERIC && A.cullPrims;
-    SailJitKernel jk;
-    int jmode = 0;
     refreshValues(c);  // the settle count may have crossed its threshold with the launch before
-    bool jit = false;
-    if (!wavefront && A.tileMap) {
-      // under a tile mask: the masked twin of the value kernel when that kernel serves, else of the types kernel (never
-      // waited for unless launches wait, SAIL_DEBUG_JIT_WAIT), else the precompiled _masked kernel
-      SailJitKernel base;
-      if (valueKernels(c, 0, &base, &jmode) && maskedKernels(c, 1, c->valSpec, c->jitWait, &jk)) jit = true;
-      else if (jitKernels(c, c->jitWait, &base, &jmode) && maskedKernels(c, 0, c->jitSpec, c->jitWait, &jk)) jit = true;
-    } else if (!wavefront) {
-      jit = valueKernels(c, 0, &jk, &jmode) || jitKernels(c, c->jitWait, &jk, &jmode);
-    }
+    const JitSlot* run = runningSlot(c, A.tileMap != nullptr, wavefront);
     // samples of each pixel in flight per workgroup (the run-time kernels' spec; the precompiled kernels hold one):
     // NS times the workgroups of one sample in flight, each NS times shorter
-    const int ns = jit ? c->jitSpec.ns : 1;
+    const int ns = run ? run->spec.ns : 1;
     {  // the last bounce's row classes for the light plugins compiled into the kernel that runs (shadeLast's kLights)
-      const bool kl = jit ? c->jitSpec.kl != 0u : A.kernelSet != SAIL_KSET_CORNELL;
+      const bool kl = run ? run->spec.kl != 0u : A.kernelSet != SAIL_KSET_CORNELL;
       A.lastQuietRows = A.cullPrims ? 0u : c->lastQuietRows[kl];
       A.lastSkipSort = A.cullPrims ? 0 : c->lastSkipSort[kl];
     }
@@ -1161,17 +1128,12 @@ int launchTrace(sail_ctx* c, const SailSample* hs, int count, int maxBounces) {
     // the lanes in its last step (C4 per GPU at N = 2 and 4: 12.6 Gseg/s against 13.4, profiles/r05_scale_groups_c4.jsonl)
     if (ns > 1 && A.groupSpp < nspp && c->forceGroups <= 0) A.groupSpp = ((A.groupSpp + ns - 1) / ns) * ns;
     A.sampleGroups = (nspp + A.groupSpp - 1) / A.groupSpp;
-    A.groupHome = (jit ? jmode == SAIL_JIT_MODE_ROOM : SAIL_GROUP_HOME_FOR(A.kernelSet)) ? 1 : 0;
+    A.groupHome = (run ? run->spec.mode == SAIL_JIT_MODE_ROOM : SAIL_GROUP_HOME_FOR(A.kernelSet)) ? 1 : 0;
     A.stageStride = stageStride;
     const bool staged = A.sampleGroups > 1;
     if (staged) {  // sized for this launch's samples (it grows to the largest launch seen)
       const size_t need = (size_t)A.stageStride * (size_t)nspp * 3 * sizeof(float);
-      if (need > c->stageBytes) {
-        if (c->stage) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(c->stage)); c->stage = nullptr; }
-        c->stageBytes = 0;
-        if (hipMalloc(&c->stage, need) != hipSuccess) { c->stage = nullptr; return fail(c, SAIL_E_OOM, "sample-group stage"); }
-        c->stageBytes = need;
-      }
+      if ((rc = growBuffer(c, &c->stage, &c->stageBytes, need, need, "sample-group stage"))) return rc;
       A.stage = c->stage;
     }
     SailWfState WS;
@@ -1179,12 +1141,7 @@ int launchTrace(sail_ctx* c, const SailSample* hs, int count, int maxBounces) {
     if (wavefront) {
       A.sampleGroups = 1; A.groupSpp = nspp; A.stage = nullptr;
       const size_t slots = (size_t)owned * 4096;
-      if (slots > c->wfSlots) {
-        if (c->wf) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(c->wf)); c->wf = nullptr; }
-        c->wfSlots = 0;
-        if (hipMalloc(&c->wf, slots * 11 * sizeof(float4)) != hipSuccess) { c->wf = nullptr; return fail(c, SAIL_E_OOM, "wavefront state"); }
-        c->wfSlots = slots;
-      }
+      if ((rc = growBuffer(c, &c->wf, &c->wfSlots, slots, slots * 11 * sizeof(float4), "wavefront state"))) return rc;
       float4* b = c->wf;
       WS.o = b; WS.d = b + c->wfSlots; WS.f = b + 2 * c->wfSlots; WS.e = b + 3 * c->wfSlots; WS.s = b + 4 * c->wfSlots;
       for (int i = 0; i < 6; i++) WS.sp[i] = b + (5 + i) * c->wfSlots;
@@ -1195,16 +1152,16 @@ int launchTrace(sail_ctx* c, const SailSample* hs, int count, int maxBounces) {
     if (wavefront) {
       HIPCHK(c, sail_launch_wavefront(A, WS, c->stream));
     } else {
-      if (jit) {
+      if (run) {
         void* args[] = {&A};
-        const unsigned nt = (unsigned)sailJitThreads(c->jitSpec);
+        const unsigned nt = (unsigned)sailJitThreads(run->spec);
         const unsigned px = nt / (unsigned)ns;                            // pixels per workgroup
-        HIPCHK(c, hipModuleLaunchKernel(A.sampleGroups > 1 ? jk.grouped : jk.plain,
+        HIPCHK(c, hipModuleLaunchKernel(A.sampleGroups > 1 ? run->k.grouped : run->k.plain,
                                         (unsigned)owned * (4096u / px) * (unsigned)A.sampleGroups, 1, 1, nt, 1, 1, 0,
                                         c->stream, args, nullptr));
         c->lastJit = true;
-        c->lastJitMode = jmode;
-        c->lastBuildId = jk.buildId;
+        c->lastJitMode = run->spec.mode;
+        c->lastBuildId = run->k.buildId;
       } else {
         HIPCHK(c, sail_launch_trace(A, owned * 16 * A.sampleGroups, c->stream));
         c->lastJit = false;
@@ -1239,8 +1196,8 @@ int ensureFrame(sail_ctx* c) {
   const size_t bytes = (size_t)c->W * c->H * sizeof(float4);
   float4** bufs[3] = {&c->frame, c->aovN ? &c->frameN : nullptr, c->aovP ? &c->frameP : nullptr};
   for (float4** b : bufs) {
-    if (!b || *b) continue;
-    if (hipMalloc(b, bytes) != hipSuccess) { *b = nullptr; return fail(c, SAIL_E_OOM, "reduced frame"); }
+    if (!b) continue;
+    if (int rc = allocOnce(c, b, bytes, "reduced frame")) return rc;
   }
   return SAIL_OK;
 }
@@ -1252,13 +1209,8 @@ const float4* shownAovP(const sail_ctx* c) { return c->reduced && c->frameP ? c-
 // the a-trous passes' work buffers (sail_denoise and sail_temporal_filter share them), allocated on first use:
 // cvA | cvB | g0 (16 B each) | g1 (8 B) | var (4 B) | rgba8 (4 B) per pixel, then a count per 16x16 tile
 int ensureDenoiseWork(sail_ctx* c) {
-  if (c->denoiseWork) return SAIL_OK;
   const size_t nt = (size_t)((c->W + 15) / 16) * (size_t)((c->H + 15) / 16), np = (size_t)c->W * c->H;
-  if (hipMalloc(&c->denoiseWork, np * 64 + nt * 4) != hipSuccess) {
-    c->denoiseWork = nullptr;
-    return fail(c, SAIL_E_OOM, "denoise work buffers");
-  }
-  return SAIL_OK;
+  return allocOnce(c, &c->denoiseWork, np * 64 + nt * 4, "denoise work buffers");
 }
 
 struct DenoiseWork {
@@ -1512,23 +1464,15 @@ int sail_get_kernel_info(sail_ctx* c, sail_kernel_info* out) {
   memset(out, 0, sizeof *out);
   if (int rc = sail_kernel_name(c, out->name, (int)sizeof out->name)) return rc;
   out->build_id = c->lastJit ? c->lastBuildId : sail_precompiled_build_id(out->name);
-  if (c->jitState == SAIL_KERNEL_JIT_PENDING) {  // poll the background build (loads the module when it is done)
-    SailJitKernel k;
-    int m;
-    (void)jitKernels(c, 0, &k, &m);
-  }
-  {  // the same for the value kernel: once it is loaded it is the scene's run-time kernel (the next launch uses it)
-    SailJitKernel k;
-    int m;
-    if (c->valState == SAIL_KERNEL_JIT_PENDING) (void)valueKernels(c, 0, &k, &m);
-  }
-  const bool val = c->valHave && c->valState == SAIL_KERNEL_JIT_READY;
-  const SailJitKernel& jk = val ? c->valK : c->jitK;
-  out->jit_state = val ? SAIL_KERNEL_JIT_READY : c->jitState;
-  out->jit_build_id = (val || c->jitState == SAIL_KERNEL_JIT_READY) ? jk.buildId : 0;
-  out->jit_compile_ms = jk.compileMs;
-  out->jit_from_cache = jk.fromCache;
-  snprintf(out->jit_error, sizeof out->jit_error, "%s", c->jitError.c_str());
+  // poll the background builds (a finished one loads its module); once the value kernel is loaded it is the scene's
+  // run-time kernel (the next launch uses it)
+  (void)c->typesSlot.poll(c->device, 0);
+  const JitSlot& s = c->valueSlot.poll(c->device, 0) ? c->valueSlot : c->typesSlot;
+  out->jit_state = s.state;
+  out->jit_build_id = s.state == SAIL_KERNEL_JIT_READY ? s.k.buildId : 0;
+  out->jit_compile_ms = s.k.compileMs;
+  out->jit_from_cache = s.k.fromCache;
+  snprintf(out->jit_error, sizeof out->jit_error, "%s", c->typesSlot.error.c_str());
   return SAIL_OK;
 }
 
@@ -1546,11 +1490,9 @@ int sail_kernel_ready(sail_ctx* c, int timeout_ms, int* ready) {
     return SAIL_OK;
   }
   if (!c->haveScene) return fail(c, SAIL_E_STATE, "sail_kernel_ready: no scene");
-  SailJitKernel k;
-  int m;
   // the best tier asked for so far: the value kernel once the scene has settled, else the types kernel
-  if (c->valHave && c->valState != SAIL_KERNEL_JIT_FAILED) *ready = valueKernels(c, timeout_ms, &k, &m) ? 1 : 0;
-  else *ready = jitKernels(c, timeout_ms, &k, &m) ? 1 : 0;
+  JitSlot& best = (c->valueSlot.have && c->valueSlot.state != SAIL_KERNEL_JIT_FAILED) ? c->valueSlot : c->typesSlot;
+  *ready = best.poll(c->device, timeout_ms) ? 1 : 0;
   return SAIL_OK;
 }
 
@@ -1626,8 +1568,8 @@ void sail_destroy(sail_ctx* c) {
   }
   if (c->device >= 0) (void)hipSetDevice(c->device);
   dropValues(c);
-  dropMaskedJit(c, 0);
-  if (c->jitHave) sail_jit_hold(c->device, c->jitSpec, -1);  // its queued build, if any, is no longer needed
+  c->typesTwin.drop(c->device, c->stream);
+  c->typesSlot.drop(c->device, c->stream);  // its queued build, if any, is no longer needed
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->comm && g_rccl.commDestroy) g_rccl.commDestroy(c->comm);
   for (auto& pr : c->pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
@@ -1778,6 +1720,16 @@ static int uploadPrims(sail_ctx* c, const std::vector<SailPrim>& prims) {
   return SAIL_OK;
 }
 
+// Decode the rows for the context's plugin set (c->plugins) and derive what follows them: the category words, the
+// last-bounce classes for a kernel without and with a light plugin, and the scene's extent
+static void decodeRows(sail_ctx* c, const float* objects, int n, const float* texparams, int tn, std::vector<SailPrim>& prims) {
+  decodePrims(objects, n, tn, c->plugins.shape_mask, prims, &c->shadowAnyHit, &c->scene);
+  fillCats(prims, texparams, tn);
+  for (int l = 0; l < 2; l++)
+    lastBounceRows(prims, texparams, tn, c->plugins.material_mask, l != 0, &c->lastQuietRows[l], &c->lastSkipSort[l]);
+  c->primExtent = primExtent(prims);
+}
+
 int sail_set_scene(sail_ctx* c, const float* objects, int n, const float* texparams, int tn, const float* lights,
                    int ln, const sail_plugins* plugins) {
   if (!c) return SAIL_E_INVALID;
@@ -1798,11 +1750,7 @@ int sail_set_scene(sail_ctx* c, const float* objects, int n, const float* texpar
   c->lastWavefront = false;
   c->lastJit = false;
   std::vector<SailPrim> prims;
-  decodePrims(objects, n, tn, plugins->shape_mask, prims, &c->shadowAnyHit, &c->scene);
-  fillCats(prims, texparams, tn);
-  for (int l = 0; l < 2; l++)
-    lastBounceRows(prims, texparams, tn, plugins->material_mask, l != 0, &c->lastQuietRows[l], &c->lastSkipSort[l]);
-  c->primExtent = primExtent(prims);
+  decodeRows(c, objects, n, texparams, tn, prims);
   c->primTypes.clear();
   for (const SailPrim& q : prims) c->primTypes.push_back(q.type);
   // per light row: the geometry row an AreaLight samples (area.glsl:8 + shader.shape.js:56)
@@ -1849,12 +1797,7 @@ int sail_set_scene(sail_ctx* c, const float* objects, int n, const float* texpar
 static int updateRows(sail_ctx* c, const float* objects, int n, bool keepTemporal) {
   HIPCHK(c, hipSetDevice(c->device));
   std::vector<SailPrim> prims;
-  decodePrims(objects, n, c->tn, c->plugins.shape_mask, prims, &c->shadowAnyHit, &c->scene);
-  fillCats(prims, c->tpRows.data(), c->tn);
-  for (int l = 0; l < 2; l++)
-    lastBounceRows(prims, c->tpRows.data(), c->tn, c->plugins.material_mask, l != 0, &c->lastQuietRows[l],
-                   &c->lastSkipSort[l]);
-  c->primExtent = primExtent(prims);
+  decodeRows(c, objects, n, c->tpRows.data(), c->tn, prims);
   c->primTypes.clear();
   for (const SailPrim& q : prims) c->primTypes.push_back(q.type);  // a kernel compiled for the rows follows them
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2134,14 +2077,8 @@ int sail_filter(sail_ctx* c, int kind, const float* weights16, float rx, float r
   int rc = sail_sync(c);
   if (rc) return rc;
   const size_t np = (size_t)c->W * c->H;
-  if (out && !c->filterOut && hipMalloc(&c->filterOut, np * sizeof(float4)) != hipSuccess) {
-    c->filterOut = nullptr;
-    return fail(c, SAIL_E_OOM, "filter output");
-  }
-  if (out8 && !c->filterOut8 && hipMalloc(&c->filterOut8, np * 4) != hipSuccess) {
-    c->filterOut8 = nullptr;
-    return fail(c, SAIL_E_OOM, "filter output");
-  }
+  if (out && (rc = allocOnce(c, &c->filterOut, np * sizeof(float4), "filter output"))) return rc;
+  if (out8 && (rc = allocOnce(c, &c->filterOut8, np * 4, "filter output"))) return rc;
   float4* dOut = out ? c->filterOut : nullptr;
   uint8_t* dOut8 = out8 ? c->filterOut8 : nullptr;
   SailFilterArgs A;
@@ -2248,10 +2185,7 @@ int sail_noise_mark(sail_ctx* c) {
   HIPCHK(c, hipSetDevice(c->device));
   if (int rc = sail_sync(c)) return rc;
   const size_t bytes = (size_t)c->W * c->H * sizeof(float4);
-  if (!c->noiseMark && hipMalloc(&c->noiseMark, bytes) != hipSuccess) {
-    c->noiseMark = nullptr;
-    return fail(c, SAIL_E_OOM, "noise mark");
-  }
+  if (int rc = allocOnce(c, &c->noiseMark, bytes, "noise mark")) return rc;
   if (c->maskSet && c->noiseHave) {  // frozen tiles keep the mark they froze with
     SailNoiseArgs A;
     memset(&A, 0, sizeof A);
@@ -2286,14 +2220,9 @@ int sail_noise_estimate(sail_ctx* c, sail_noise_info* out, float* tile_err, floa
                 (unsigned long long)c->k, (unsigned long long)c->noiseK);
   const int tx = (c->W + 15) / 16, ty = (c->H + 15) / 16;
   const size_t nt = (size_t)tx * ty, np = (size_t)c->W * c->H;
-  if (!c->noiseOut && hipMalloc(&c->noiseOut, nt * 8) != hipSuccess) {
-    c->noiseOut = nullptr;
-    return fail(c, SAIL_E_OOM, "noise tiles");
-  }
-  if (pixel_err && !c->noisePix && hipMalloc(&c->noisePix, np * sizeof(float)) != hipSuccess) {
-    c->noisePix = nullptr;
-    return fail(c, SAIL_E_OOM, "noise map");
-  }
+  if (int rc = allocOnce(c, &c->noiseOut, nt * 8, "noise tiles")) return rc;
+  if (pixel_err)
+    if (int rc = allocOnce(c, &c->noisePix, np * sizeof(float), "noise map")) return rc;
   SailNoiseArgs A;
   memset(&A, 0, sizeof A);
   A.S = shownAccum(c); A.P = c->noiseMark;
@@ -2355,6 +2284,23 @@ int sail_plan_until(uint64_t k, uint64_t min_spp, uint64_t max_spp, uint64_t* ne
   return SAIL_OK;
 }
 
+// Render the frozen schedule's samples *k .. next (sail_render_until, sail_render_adaptive: `who` in the message)
+static int renderSamplesTo(sail_ctx* c, const char* who, const double mvp[16], const float eye[3], int maxBounces,
+                           uint64_t* k, uint64_t next) {
+  constexpr uint64_t kChunk = 4096;  // samples whose matrices are built at a time (launches split anywhere bit for bit)
+  std::vector<float> inv, seeds;
+  while (*k < next) {
+    const int spp = (int)(next - *k < kChunk ? next - *k : kChunk);
+    inv.resize((size_t)spp * 16);
+    seeds.resize((size_t)spp);
+    if (int rc = sail_schedule(mvp, c->W, c->H, (int)*k, spp, inv.data(), seeds.data()))
+      return fail(c, rc, "%s: sail_schedule failed (a singular camera matrix?)", who);
+    if (int rc = sail_render_schedule(c, inv.data(), seeds.data(), eye, spp, maxBounces)) return rc;
+    *k += (uint64_t)spp;
+  }
+  return SAIL_OK;
+}
+
 int sail_render_until(sail_ctx* c, const double mvp[16], const float eye[3], int maxBounces, double target,
                       uint64_t min_spp, uint64_t max_spp, sail_noise_info* out, int* converged, sail_until_step* history,
                       int capacity, int* looks) {
@@ -2375,21 +2321,11 @@ int sail_render_until(sail_ctx* c, const double mvp[16], const float eye[3], int
   out->tiles_x = (c->W + 15) / 16; out->tiles_y = (c->H + 15) / 16;
   int nlooks = 0, conv = 0;
   bool marked = false;
-  constexpr uint64_t kChunk = 4096;  // samples whose matrices are built at a time (launches split anywhere bit for bit)
-  std::vector<float> inv, seeds;
   for (;;) {
     uint64_t next = k;
     if (int rc = sail_plan_until(k, min_spp, max_spp, &next)) return fail(c, rc, "sail_render_until: %s", sail_last_error(nullptr));
     if (next == k) break;  // at max_spp
-    while (k < next) {
-      const int spp = (int)(next - k < kChunk ? next - k : kChunk);
-      inv.resize((size_t)spp * 16);
-      seeds.resize((size_t)spp);
-      if (int rc = sail_schedule(mvp, c->W, c->H, (int)k, spp, inv.data(), seeds.data()))
-        return fail(c, rc, "sail_render_until: sail_schedule failed (a singular camera matrix?)");
-      if (int rc = sail_render_schedule(c, inv.data(), seeds.data(), eye, spp, maxBounces)) return rc;
-      k += (uint64_t)spp;
-    }
+    if (int rc = renderSamplesTo(c, "sail_render_until", mvp, eye, maxBounces, &k, next)) return rc;
     sail_until_step step{k, INFINITY, INFINITY};
     if (!marked) {  // the first look only marks: no estimate yet
       if (int rc = sail_noise_mark(c)) return rc;
@@ -2453,14 +2389,8 @@ int sail_set_active_tiles(sail_ctx* c, const uint8_t* active, int count) {
   }
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));  // launches in flight read the tables
-  if (!c->tileMap && hipMalloc(&c->tileMap, sizeof(int32_t) * (size_t)tiles) != hipSuccess) {
-    c->tileMap = nullptr;
-    return fail(c, SAIL_E_OOM, "tile table");
-  }
-  if (!c->maskBytes && hipMalloc(&c->maskBytes, (size_t)tiles) != hipSuccess) {
-    c->maskBytes = nullptr;
-    return fail(c, SAIL_E_OOM, "tile mask");
-  }
+  if (int rc = allocOnce(c, &c->tileMap, sizeof(int32_t) * (size_t)tiles, "tile table")) return rc;
+  if (int rc = allocOnce(c, &c->maskBytes, (size_t)tiles, "tile mask")) return rc;
   std::vector<uint8_t> m((size_t)tiles);
   for (int t = 0; t < tiles; t++) m[(size_t)t] = active[t] ? 1 : 0;
   // this rank's active tiles, ascending, and their in-frame pixels
@@ -2593,22 +2523,13 @@ int sail_render_adaptive(sail_ctx* c, const double mvp[16], const float eye[3], 
   out->tiles_x = tx; out->tiles_y = ty;
   int nlooks = 0;
   bool marked = false;
-  constexpr uint64_t kChunk = 4096;  // as sail_render_until
-  std::vector<float> inv, seeds, err16((size_t)tx16 * ty16);
+  std::vector<float> err16((size_t)tx16 * ty16);
   while (nActive > 0) {
     uint64_t next = k;
     if (int rc = sail_plan_until(k, p.min_spp, p.max_spp, &next)) return fail(c, rc, "sail_render_adaptive: %s", sail_last_error(nullptr));
     if (next == k) break;  // at max_spp
     out->pixel_samples += activePixels() * (next - k);
-    while (k < next) {
-      const int spp = (int)(next - k < kChunk ? next - k : kChunk);
-      inv.resize((size_t)spp * 16);
-      seeds.resize((size_t)spp);
-      if (int rc = sail_schedule(mvp, c->W, c->H, (int)k, spp, inv.data(), seeds.data()))
-        return fail(c, rc, "sail_render_adaptive: sail_schedule failed (a singular camera matrix?)");
-      if (int rc = sail_render_schedule(c, inv.data(), seeds.data(), eye, spp, maxBounces)) return rc;
-      k += (uint64_t)spp;
-    }
+    if (int rc = renderSamplesTo(c, "sail_render_adaptive", mvp, eye, maxBounces, &k, next)) return rc;
     sail_until_step step{k, INFINITY, INFINITY};
     if (!marked) {  // the first look only marks: no estimate yet
       if (int rc = sail_noise_mark(c)) return rc;
@@ -2777,10 +2698,7 @@ int ensureTemporal(sail_ctx* c) {
   if (c->tpWork) return SAIL_OK;
   const size_t np = (size_t)c->W * c->H;
   // five float4 maps (16 B each) | rgba8 (4 B) per pixel, then three counts per tile
-  if (hipMalloc(&c->tpWork, np * 84 + temporalTiles(c) * 12) != hipSuccess) {
-    c->tpWork = nullptr;
-    return fail(c, SAIL_E_OOM, "temporal maps");
-  }
+  if (int rc = allocOnce(c, &c->tpWork, np * 84 + temporalTiles(c) * 12, "temporal maps")) return rc;
   float4* base = (float4*)c->tpWork;
   c->tpGcur = base; c->tpGprev = base + np; c->tpHist = base + 2 * np; c->tpR = base + 3 * np; c->tpOut = base + 4 * np;
   return SAIL_OK;
@@ -2857,16 +2775,10 @@ int sail_temporal_begin(sail_ctx* c, const double mvp[16], const float eye[3], c
   if (int rc = sail_sync(c)) return rc;
   if (int rc = ensureTemporal(c)) return rc;
   const bool moved = c->tpMotionPending;
-  if (moved && c->tpMotionDevRows < (c->n > 0 ? c->n : 1)) {  // before anything is committed: a begin that fails keeps it all
-    if (c->tpMotionDev) HIPCHK(c, hipFree(c->tpMotionDev));
-    c->tpMotionDev = nullptr;
-    c->tpMotionDevRows = 0;
+  if (moved) {  // before anything is committed: a begin that fails keeps it all
     const int rows = c->n > 0 ? c->n : 1;
-    if (hipMalloc(&c->tpMotionDev, sizeof(float4) * (size_t)rows) != hipSuccess) {
-      c->tpMotionDev = nullptr;
-      return fail(c, SAIL_E_OOM, "object motion table");
-    }
-    c->tpMotionDevRows = rows;
+    if (int rc = growBuffer(c, &c->tpMotionDev, &c->tpMotionDevRows, rows, sizeof(float4) * (size_t)rows, "object motion table"))
+      return rc;
   }
   if (c->tpHaveCur) {  // commit the view that was current
     std::swap(c->tpHist, c->tpOut);
@@ -3052,10 +2964,7 @@ int sail_temporal_moments(sail_ctx* c, int on) {
   if (c->tpMom) return SAIL_OK;
   const size_t np = (size_t)c->W * c->H;
   // three float4 maps (16 B each) per pixel, then the filter's count of temporal pixels per tile
-  if (hipMalloc(&c->tpMom, np * 48 + temporalTiles(c) * 4) != hipSuccess) {
-    c->tpMom = nullptr;
-    return fail(c, SAIL_E_OOM, "moment maps");
-  }
+  if (int rc = allocOnce(c, &c->tpMom, np * 48 + temporalTiles(c) * 4, "moment maps")) return rc;
   float4* base = (float4*)c->tpMom;
   c->tpMhist = base; c->tpMR = base + np; c->tpMout = base + 2 * np;
   HIPCHK(c, zeroMoments(c));
@@ -3192,12 +3101,7 @@ uint32_t* albedoCounts(const sail_ctx* c) { return (uint32_t*)(c->albMap + (size
 
 // the albedo map and its two counts per tile, allocated on first use
 int ensureAlbedo(sail_ctx* c) {
-  if (c->albMap) return SAIL_OK;
-  if (hipMalloc(&c->albMap, (size_t)c->W * c->H * 16 + temporalTiles(c) * 8) != hipSuccess) {
-    c->albMap = nullptr;
-    return fail(c, SAIL_E_OOM, "albedo map");
-  }
-  return SAIL_OK;
+  return allocOnce(c, &c->albMap, (size_t)c->W * c->H * 16 + temporalTiles(c) * 8, "albedo map");
 }
 
 void albedoView(sail_ctx* c, const double mvp[16], const float eye[3]) {

@@ -294,6 +294,51 @@ def test_update_objects_returns_to_the_types_kernel(gpu, fixtures):
 
 
 @pytest.mark.gpu
+def test_masked_twin_of_the_value_kernel_goes_with_it(gpu, fixtures, tmp_path):
+    """a launch under a tile mask runs the value kernel's masked twin, a module of its own (both specs carry the rows'
+    words: two value objects, two modules); new rows and the context's end release both holds, the twin's with the value
+    kernel's"""
+    from test_gpu_adaptive import K, check_tiles, frame, masks_for, render, uniform
+    sc = fixtures["scenes"]["C1"]
+    w, h, bounces = 160, 96, 4  # 3 x 2 tiles, ragged right and top
+    zero, first, both = uniform(fixtures, "C1", w, h, bounces)
+    mask = masks_for(w, h)["checker"]
+    assert mask.any() and not mask.all()
+    capi.set_jit_cache(str(tmp_path / "jit"))
+    try:
+        ctx = capi.Context(w, h, flags=capi.FLAG_AOV, debug={AFTER: 0, capi.DEBUG_SAMPLE_GROUPS: 1})
+        try:
+            ctx.set_scene_dict(sc)
+            render(ctx, sc, 0, K, bounces)
+            assert ctx.kernel_ready(-1)
+            ctx.set_active_tiles(mask)
+            render(ctx, sc, K, K, bounces)
+            name = ctx.kernel_name()
+            assert "jit" in name and "_masked" in name, name
+            check_tiles(frame(ctx), mask, both, first, "value kernel's masked twin")
+            assert capi.jit_resident() == (2, 2)
+            # The same rows: the value kernel and its twin go all the same. Under a threshold of 0 the update would ask for
+            # the rows' value kernel again before it returns, and the cache would load it at once ((1, 1) here): the
+            # threshold is out of reach while the rows change, so that the count shows what the update released.
+            ctx.set_debug(AFTER, 1 << 20)
+            _update(ctx, sc)
+            assert capi.jit_resident() == (0, 0)
+            ctx.set_debug(AFTER, 0)
+            assert ctx.kernel_ready(-1)
+            ctx.set_active_tiles(mask)  # the new rows' accumulation started without a mask
+            render(ctx, sc, 0, K, bounces)
+            name = ctx.kernel_name()
+            assert "jit" in name and "_masked" in name, name
+            check_tiles(frame(ctx), mask, first, zero, "masked twin after the update")
+            assert capi.jit_resident() == (2, 2)
+        finally:
+            ctx.close()
+        assert capi.jit_resident() == (0, 0)
+    finally:
+        capi.set_jit_cache(None)
+
+
+@pytest.mark.gpu
 def test_settle_count_restarts_with_the_scene_and_the_spec(gpu, fixtures):
     """the count of samples at rest (threshold 2 here) restarts at sail_set_scene and at a switch that changes the types
     spec, and a partition that leaves the spec alone leaves the value kernel: told by the build id of each launch"""
