@@ -1,0 +1,747 @@
+// sail_post.cpp — the passes over a rendered frame: the a-trous denoiser (sail_denoise.hip), camera- and object-motion
+// reprojection (sail_temporal.hip), moment tracking and the temporal filter (sail_tfilter.hip), the albedo map
+// (sail_albedo.hip). The context is sail_ctx.h's; sail_capi.cpp's rowsChanged says what of this new rows invalidate.
+#include <math.h>
+#include <string.h>
+#include <algorithm>
+#include <cmath>
+#include <vector>
+#include "sail_ctx.h"
+
+namespace {
+
+// the a-trous passes' work buffers (sail_denoise and sail_temporal_filter share them), allocated on first use:
+// cvA | cvB | g0 (16 B each) | g1 (8 B) | var (4 B) | rgba8 (4 B) per pixel, then a count per 16x16 tile
+int ensureDenoiseWork(sail_ctx* c) {
+  const size_t nt = tiles16(c), np = (size_t)c->W * c->H;
+  return allocOnce(c, &c->denoiseWork, np * 64 + nt * 4, "denoise work buffers");
+}
+
+struct DenoiseWork {
+  float4* cv[2];
+  float4* g0;
+  float2* g1;
+  float* var;
+  uint32_t* u8;
+  uint32_t* bad;
+};
+DenoiseWork denoiseWork(const sail_ctx* c) {
+  const size_t np = (size_t)c->W * c->H;
+  char* base = (char*)c->denoiseWork;
+  return {{(float4*)base, (float4*)(base + np * 16)}, (float4*)(base + np * 32), (float2*)(base + np * 48),
+          (float*)(base + np * 56), (uint32_t*)(base + np * 60), (uint32_t*)(base + np * 64)};
+}
+
+// What sail_denoise and sail_temporal_filter share: `prepare` launches the pass that fills (cv[0], g0, g1) and the
+// per-tile counts, then the a-trous passes run with steps 1, 2, 4, ..., an event round every pass (ms[0] = prepare,
+// ms[1..] = the passes); the stream is synchronised and the outputs that are asked for are copied back.
+// With a map `alb` (the demodulated calls) the last pass is the remodulating instance.
+template <class Prepare>
+hipError_t runAtrous(sail_ctx* c, const DenoiseWork& w, Prepare prepare, int iterations, float sigma_l, float sigma_x,
+                     int display, float gamma_c, float* out_rgba, float* out_var, uint8_t* out_rgba8, float ms[8],
+                     float* total, int* rc, const float4* alb = nullptr, float amin = 0.0f) {
+  const size_t np = (size_t)c->W * c->H;
+  const int nev = iterations + 2;  // before the prepare pass, then after every pass
+  PooledEvents ev(c, nev);
+  if ((*rc = ev.rc)) return hipSuccess;
+  hipError_t e = hipEventRecord(ev[0], c->stream);
+  if (e == hipSuccess) e = prepare();
+  if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
+  int cur = 0;
+  for (int it = 0; it < iterations && e == hipSuccess; it++) {
+    const bool last = it == iterations - 1;
+    SailDenoiseAtrousArgs B;
+    memset(&B, 0, sizeof B);
+    B.src = w.cv[cur];
+    B.dst = (last && !out_rgba) ? nullptr : w.cv[cur ^ 1];
+    B.g0 = w.g0; B.g1 = w.g1;
+    B.outVar = (last && out_var) ? w.var : nullptr;
+    B.out8 = (last && out_rgba8) ? w.u8 : nullptr;
+    B.W = c->W; B.H = c->H;
+    B.step = 1 << it;
+    B.last = last;
+    B.sl2 = sigma_l * sigma_l;
+    const float sx = sigma_x * (float)B.step;
+    B.sxs = sx * sx;
+    B.display = display; B.gammaC = gamma_c;
+    if (last && alb) {
+      SailDenoiseAtrousRemodArgs R;
+      memset(&R, 0, sizeof R);
+      R.P = B; R.alb = alb; R.amin = amin;
+      e = sail_launch_denoise_atrous_remod(R, c->stream);
+    } else {
+      e = sail_launch_denoise_atrous(B, c->stream);
+    }
+    if (e == hipSuccess) e = hipEventRecord(ev[it + 2], c->stream);
+    cur ^= 1;
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  for (int i = 0; i + 1 < nev && e == hipSuccess; i++) e = hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]);
+  if (e == hipSuccess) e = hipEventElapsedTime(total, ev[0], ev[nev - 1]);
+  if (e == hipSuccess && out_rgba) e = hipMemcpy(out_rgba, w.cv[cur], np * 16, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && out_var) e = hipMemcpy(out_var, w.var, np * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && out_rgba8) e = hipMemcpy(out_rgba8, w.u8, np * 4, hipMemcpyDeviceToHost);
+  return e;
+}
+
+}  // namespace
+
+// the three moment maps of a context that tracks them (sail_temporal_moments), zeroed on its stream
+hipError_t zeroMoments(sail_ctx* c) {
+  if (!c->tpMom) return hipSuccess;
+  return hipMemsetAsync(c->tpMom, 0, (size_t)c->W * c->H * 48, c->stream);
+}
+
+// nothing is pending for the next sail_temporal_begin any more (sail_move_objects)
+void clearMotion(sail_ctx* c) {
+  c->tpMotionPending = false;
+  c->tpMotion.clear();
+  c->tpMotionCap = INFINITY;
+}
+
+void freePost(sail_ctx* c) {
+  for (void* b : {c->denoiseWork, c->tpWork, c->tpMom, (void*)c->tpMotionDev, (void*)c->albMap}) if (b) (void)hipFree(b);
+}
+
+extern "C" {
+
+// ---- variance-guided a-trous denoiser (include/sail_hip.h; the kernels are sail_denoise.hip) --------------------------------
+int sail_denoise_defaults(sail_denoise_params* p) {
+  if (!p) return SAIL_E_INVALID;
+  p->iterations = 4;
+  p->sigma_l = 1.0f;
+  p->sigma_x = 0.2f;
+  p->display = SAIL_FILTER_COLOR;
+  p->gamma_c = 2.2f;
+  return SAIL_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+bool aminOk(float amin) { return std::isfinite(amin) && amin > 0.0f; }
+
+// sail_denoise (demod = false: amin is not read, no map is needed) and sail_denoise_albedo
+int denoiseCall(sail_ctx* c, const char* who, bool demod, const sail_denoise_params* params, float amin, float* out_rgba,
+                float* out_var, uint8_t* out_rgba8, sail_denoise_info* info) {
+  if (!c) return SAIL_E_INVALID;
+  sail_denoise_params p;
+  sail_denoise_defaults(&p);
+  if (params) p = *params;
+  if (p.iterations < 1 || p.iterations > 6 || !(p.sigma_l > 0.0f) || !std::isfinite(p.sigma_l) || !(p.sigma_x > 0.0f) ||
+      !std::isfinite(p.sigma_x) || p.display < SAIL_FILTER_COLOR || p.display > SAIL_FILTER_TONEMAPPING)
+    return fail(c, SAIL_E_INVALID, "%s: bad parameters (iterations %d of 1..6, sigma_l %g and sigma_x %g finite and > 0, display %d of 0..2)",
+                who, p.iterations, (double)p.sigma_l, (double)p.sigma_x, p.display);
+  if (demod && !aminOk(amin)) return fail(c, SAIL_E_INVALID, "%s: amin %g must be finite and > 0", who, (double)amin);
+  if (!c->subs.empty()) {  // device 0's reduced frame and AOV maps, like sail_filter
+    if (int rc = reducedFrame(c, who)) return rc;
+    return relay(c, denoiseCall(c->subs[0], who, demod, &p, amin, out_rgba, out_var, out_rgba8, info), c->subs[0]);
+  }
+  if (!c->aovN || !c->aovP)
+    return fail(c, SAIL_E_STATE, "%s: reads the normal and position AOVs (create with SAIL_FLAG_AOV)", who);
+  if (c->accumMode == SAIL_ACCUM_COMPAT8)
+    return fail(c, SAIL_E_STATE, "%s: SAIL_ACCUM_COMPAT8 stores 8-bit frames, whose halves cannot be compared", who);
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = sail_sync(c)) return rc;
+  if (!c->noiseHave || !c->noiseMark)
+    return fail(c, SAIL_E_STATE, "%s: no mark (sail_noise_mark first; a reset or a new scene drops it)", who);
+  if (c->k <= c->noiseK)
+    return fail(c, SAIL_E_STATE, "%s: no sample since the mark (k = %llu, marked at %llu)", who,
+                (unsigned long long)c->k, (unsigned long long)c->noiseK);
+  if (demod && (!c->albHave || !c->albMap))
+    return fail(c, SAIL_E_STATE, "%s: no albedo map (sail_albedo or sail_albedo_load first; new rows drop it)", who);
+  const size_t nt = tiles16(c);
+  if (int rc = ensureDenoiseWork(c)) return rc;
+  const DenoiseWork w = denoiseWork(c);
+  SailDenoisePrepareArgs A;
+  memset(&A, 0, sizeof A);
+  A.S = shownAccum(c); A.P = c->noiseMark; A.N = shownAovN(c); A.X = shownAovP(c);
+  A.cv = w.cv[0]; A.g0 = w.g0; A.g1 = w.g1; A.tileBad = w.bad;
+  A.W = c->W; A.H = c->H;
+  A.mix = c->accumMode == SAIL_ACCUM_MIX;
+  A.kf = (float)c->k; A.hf = (float)c->noiseK;
+  float ms[8] = {}, total = 0.0f;
+  int rc = SAIL_OK;
+  SailDenoisePrepareDemodArgs D;
+  memset(&D, 0, sizeof D);
+  D.P = A; D.alb = c->albMap; D.amin = amin;
+  hipError_t e = runAtrous(c, w, [&] { return demod ? sail_launch_denoise_prepare_demod(D, c->stream)
+                                                      : sail_launch_denoise_prepare(A, c->stream); },
+                           p.iterations, p.sigma_l, p.sigma_x, p.display, p.gamma_c, out_rgba, out_var, out_rgba8, ms, &total,
+                           &rc, demod ? c->albMap : nullptr, amin);
+  if (rc) return rc;
+  std::vector<uint32_t> bad(nt);
+  if (e == hipSuccess) e = hipMemcpy(bad.data(), w.bad, nt * 4, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(c, SAIL_E_HIP, "%s: %s", who, hipGetErrorString(e));
+  if (info) {
+    memset(info, 0, sizeof *info);
+    info->k = c->k;
+    info->k_mark = c->noiseK;
+    for (uint32_t b : bad) info->nonfinite += b;
+    info->iterations = p.iterations;
+    info->kernel_ms = total;
+    for (int i = 0; i <= p.iterations; i++) info->pass_ms[i] = ms[i];
+  }
+  return SAIL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sail_denoise(sail_ctx* c, const sail_denoise_params* params, float* out_rgba, float* out_var, uint8_t* out_rgba8,
+                 sail_denoise_info* info) {
+  return denoiseCall(c, "sail_denoise", false, params, 0.0f, out_rgba, out_var, out_rgba8, info);
+}
+
+int sail_denoise_albedo(sail_ctx* c, const sail_denoise_params* params, float amin, float* out_rgba, float* out_var,
+                        uint8_t* out_rgba8, sail_denoise_info* info) {
+  return denoiseCall(c, "sail_denoise_albedo", true, params, amin, out_rgba, out_var, out_rgba8, info);
+}
+
+// ---- camera-motion reprojection (include/sail_hip.h; the kernels are sail_temporal.hip) ---------------------------------------
+int sail_temporal_defaults(sail_temporal_params* p) {
+  if (!p) return SAIL_E_INVALID;
+  p->cap = 32.0f;
+  p->pos_tol = 0.05f;
+  p->display = SAIL_FILTER_COLOR;
+  p->gamma_c = 2.2f;
+  return SAIL_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+int temporalParams(sail_ctx* c, const char* who, const sail_temporal_params* params, sail_temporal_params* p) {
+  sail_temporal_defaults(p);
+  if (params) *p = *params;
+  if (!std::isfinite(p->cap) || p->cap < 1.0f || !std::isfinite(p->pos_tol) || !(p->pos_tol > 0.0f) ||
+      p->display < SAIL_FILTER_COLOR || p->display > SAIL_FILTER_TONEMAPPING)
+    return fail(c, SAIL_E_INVALID, "%s: bad parameters (cap %g finite and >= 1, pos_tol %g finite and > 0, display %d of 0..2)",
+                who, (double)p->cap, (double)p->pos_tol, p->display);
+  return SAIL_OK;
+}
+
+// what every temporal call refuses on one device's context
+int temporalState(sail_ctx* c, const char* who) {
+  if (!c->haveScene) return fail(c, SAIL_E_STATE, "%s: no scene (call sail_set_scene first)", who);
+  if (c->accumMode == SAIL_ACCUM_COMPAT8)
+    return fail(c, SAIL_E_STATE, "%s: SAIL_ACCUM_COMPAT8 stores 8-bit frames, which carry no sample count to blend with", who);
+  return SAIL_OK;
+}
+
+uint32_t* temporalOut8(const sail_ctx* c) { return (uint32_t*)((char*)c->tpWork + (size_t)c->W * c->H * 80); }
+uint32_t* temporalCounts(const sail_ctx* c) { return temporalOut8(c) + (size_t)c->W * c->H; }
+
+int ensureTemporal(sail_ctx* c) {
+  if (c->tpWork) return SAIL_OK;
+  const size_t np = (size_t)c->W * c->H;
+  // five float4 maps (16 B each) | rgba8 (4 B) per pixel, then three counts per tile
+  if (int rc = allocOnce(c, &c->tpWork, np * 84 + tiles16(c) * 12, "temporal maps")) return rc;
+  float4* base = (float4*)c->tpWork;
+  c->tpGcur = base; c->tpGprev = base + np; c->tpHist = base + 2 * np; c->tpR = base + 3 * np; c->tpOut = base + 4 * np;
+  return SAIL_OK;
+}
+
+// the G-buffer pass's arguments for a view: the corner directions of a sample without jitter
+int gbufferArgs(sail_ctx* c, const char* who, const double mvp[16], const float eye[3], SailGbufferArgs* A) {
+  float inv[16];
+  if (sail_jitter_inverse(mvp, 0.0, 0.0, c->W, c->H, inv) != SAIL_OK)
+    return fail(c, SAIL_E_INVALID, "%s: the camera matrix is singular", who);
+  memset(A, 0, sizeof *A);
+  A->prims = c->prims; A->n = c->n;
+  cornerDirs(inv, eye, A->d);
+  memcpy(A->eye, eye, sizeof A->eye);
+  A->W = c->W; A->H = c->H;
+  return SAIL_OK;
+}
+
+uint64_t sumTiles(const std::vector<uint32_t>& v, size_t from, size_t count) {
+  uint64_t s = 0;
+  for (size_t i = 0; i < count; i++) s += v[from + i];
+  return s;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sail_gbuffer(sail_ctx* c, const double mvp[16], const float eye[3], float* rays6, int32_t* id, float* t, float* xyz) {
+  if (!c) return SAIL_E_INVALID;
+  if (!mvp || !eye) return fail(c, SAIL_E_INVALID, "sail_gbuffer: mvp and eye are required");
+  if (!c->subs.empty()) return relay(c, sail_gbuffer(c->subs[0], mvp, eye, rays6, id, t, xyz), c->subs[0]);
+  if (!c->haveScene) return fail(c, SAIL_E_STATE, "sail_gbuffer: no scene (call sail_set_scene first)");
+  SailGbufferArgs A;
+  if (int rc = gbufferArgs(c, "sail_gbuffer", mvp, eye, &A)) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = sail_sync(c)) return rc;
+  const size_t np = (size_t)c->W * c->H;
+  void* work = nullptr;  // G (16 B) | rays (24 B) | t (4 B) per pixel
+  if (hipMalloc(&work, np * 44) != hipSuccess) return fail(c, SAIL_E_OOM, "G-buffer scratch");
+  A.G = (float4*)work;
+  A.rays = rays6 ? (float*)((char*)work + np * 16) : nullptr;
+  A.t = t ? (float*)((char*)work + np * 40) : nullptr;
+  std::vector<float> g((id || xyz) ? np * 4 : 0);
+  hipError_t e = sail_launch_gbuffer(A, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e == hipSuccess && !g.empty()) e = hipMemcpy(g.data(), A.G, np * 16, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && rays6) e = hipMemcpy(rays6, A.rays, np * 24, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && t) e = hipMemcpy(t, A.t, np * 4, hipMemcpyDeviceToHost);
+  (void)hipFree(work);
+  if (e != hipSuccess) return fail(c, SAIL_E_HIP, "sail_gbuffer: %s", hipGetErrorString(e));
+  for (size_t i = 0; i < np && !g.empty(); i++) {
+    if (id) id[i] = (int32_t)g[4 * i + 3];
+    if (xyz) { xyz[3 * i] = g[4 * i]; xyz[3 * i + 1] = g[4 * i + 1]; xyz[3 * i + 2] = g[4 * i + 2]; }
+  }
+  return SAIL_OK;
+}
+
+int sail_temporal_begin(sail_ctx* c, const double mvp[16], const float eye[3], const sail_temporal_params* params,
+                        sail_temporal_info* info) {
+  if (!c) return SAIL_E_INVALID;
+  sail_temporal_params p;
+  if (int rc = temporalParams(c, "sail_temporal_begin", params, &p)) return rc;
+  if (!mvp || !eye) return fail(c, SAIL_E_INVALID, "sail_temporal_begin: mvp and eye are required");
+  if (!c->subs.empty()) {  // device 0's reduced frame and scene, like sail_filter
+    if (int rc = reducedFrame(c, "sail_temporal_begin")) return rc;
+    return relay(c, sail_temporal_begin(c->subs[0], mvp, eye, &p, info), c->subs[0]);
+  }
+  if (int rc = temporalState(c, "sail_temporal_begin")) return rc;
+  SailGbufferArgs A;
+  if (int rc = gbufferArgs(c, "sail_temporal_begin", mvp, eye, &A)) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = sail_sync(c)) return rc;
+  if (int rc = ensureTemporal(c)) return rc;
+  const bool moved = c->tpMotionPending;
+  if (moved) {  // before anything is committed: a begin that fails keeps it all
+    const int rows = c->n > 0 ? c->n : 1;
+    if (int rc = growBuffer(c, &c->tpMotionDev, &c->tpMotionDevRows, rows, sizeof(float4) * (size_t)rows, "object motion table"))
+      return rc;
+  }
+  if (c->tpHaveCur) {  // commit the view that was current
+    std::swap(c->tpHist, c->tpOut);
+    std::swap(c->tpGprev, c->tpGcur);
+    if (c->tpMom) std::swap(c->tpMhist, c->tpMout);
+    c->tpPrev = c->tpCur;
+    c->tpHavePrev = true;
+    c->tpHaveCur = false;
+  }
+  const size_t nt = tiles16(c), np = (size_t)c->W * c->H;
+  uint32_t* cnt = temporalCounts(c);
+  A.G = c->tpGcur;
+  SailReprojectArgs B;
+  memset(&B, 0, sizeof B);
+  B.Gcur = c->tpGcur; B.Gprev = c->tpGprev; B.hist = c->tpHist; B.out = c->tpR;
+  B.tileHit = cnt; B.tileHist = cnt + nt;
+  for (int j = 0; j < 4; j++) { B.Mp[0][j] = c->tpPrev.m[j]; B.Mp[1][j] = c->tpPrev.m[4 + j]; B.Mp[2][j] = c->tpPrev.m[12 + j]; }
+  memcpy(B.eyePrev, c->tpPrev.eye, sizeof B.eyePrev);
+  B.tol2 = p.pos_tol * p.pos_tol;
+  B.W = c->W; B.H = c->H;
+  B.haveHist = c->tpHavePrev;
+  // an object motion is pending (sail_move_objects): the moved kernels, with the table uploaded ahead of them
+  B.motion = c->tpMotionDev; B.n = c->n; B.mc = c->tpMotionCap;
+  c->tpResolved = false;
+  // moment tracking: the same gather over Mhist, timed with the reproject pass
+  const int nev = c->tpMom ? 4 : 3;
+  SailReprojectArgs M = B;
+  M.hist = c->tpMhist; M.out = c->tpMR;
+  M.tileHit = nullptr; M.tileHist = nullptr;
+  PooledEvents ev(c, nev);
+  if (ev.rc) return ev.rc;
+  hipError_t e = hipSuccess;
+  if (moved && c->n > 0)
+    e = hipMemcpyAsync(c->tpMotionDev, c->tpMotion.data(), sizeof(float4) * (size_t)c->n, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipEventRecord(ev[0], c->stream);
+  if (e == hipSuccess) e = sail_launch_gbuffer(A, c->stream);
+  if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
+  if (e == hipSuccess) e = sail_launch_reproject(B, moved, c->stream);
+  if (e == hipSuccess) e = hipEventRecord(ev[2], c->stream);
+  if (c->tpMom) {
+    if (e == hipSuccess) e = sail_launch_moment_reproject(M, moved, c->stream);
+    if (e == hipSuccess) e = hipEventRecord(ev[3], c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->tpMout, c->tpMR, np * 16, hipMemcpyDeviceToDevice, c->stream);
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(c->tpOut, c->tpR, np * 16, hipMemcpyDeviceToDevice, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  float ms[3] = {};
+  for (int i = 0; i + 1 < nev && e == hipSuccess; i++) e = hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]);
+  ms[1] += ms[2];  // the moment reproject, when it ran
+  std::vector<uint32_t> host(nt * 2);
+  if (e == hipSuccess) e = hipMemcpy(host.data(), cnt, nt * 8, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(c, SAIL_E_HIP, "sail_temporal_begin: %s", hipGetErrorString(e));
+  for (int i = 0; i < 16; i++) c->tpCur.m[i] = (float)mvp[i];
+  memcpy(c->tpCur.eye, eye, sizeof c->tpCur.eye);
+  c->tpHaveCur = true;
+  clearMotion(c);  // consumed: the next begin is today's unless the rows move again
+  c->tpHitPixels = sumTiles(host, 0, nt);
+  if (info) {
+    memset(info, 0, sizeof *info);
+    info->k = c->k;
+    info->hit_pixels = c->tpHitPixels;
+    info->history_pixels = sumTiles(host, nt, nt);
+    info->kernel_ms = (double)ms[0] + (double)ms[1];
+    info->pass_ms[0] = ms[0]; info->pass_ms[1] = ms[1];
+  }
+  return SAIL_OK;
+}
+
+int sail_temporal_resolve(sail_ctx* c, const sail_temporal_params* params, float* out_rgba, uint8_t* out_rgba8,
+                          sail_temporal_info* info) {
+  if (!c) return SAIL_E_INVALID;
+  sail_temporal_params p;
+  if (int rc = temporalParams(c, "sail_temporal_resolve", params, &p)) return rc;
+  if (!c->subs.empty()) {
+    if (int rc = reducedFrame(c, "sail_temporal_resolve")) return rc;
+    return relay(c, sail_temporal_resolve(c->subs[0], &p, out_rgba, out_rgba8, info), c->subs[0]);
+  }
+  if (int rc = temporalState(c, "sail_temporal_resolve")) return rc;
+  if (!c->tpHaveCur || !c->tpWork)
+    return fail(c, SAIL_E_STATE, "sail_temporal_resolve: no current view (sail_temporal_begin first; a new scene drops it)");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = sail_sync(c)) return rc;
+  const size_t nt = tiles16(c), np = (size_t)c->W * c->H;
+  uint32_t* cnt = temporalCounts(c);
+  SailResolveArgs A;
+  memset(&A, 0, sizeof A);
+  A.S = shownAccum(c); A.R = c->tpR; A.Out = c->tpOut;
+  A.out8 = out_rgba8 ? temporalOut8(c) : nullptr;
+  A.tileHist = cnt + nt; A.tileBad = cnt + 2 * nt;
+  A.W = c->W; A.H = c->H;
+  A.mix = c->accumMode == SAIL_ACCUM_MIX;
+  A.kf = (float)c->k;
+  A.cap = p.cap; A.display = p.display; A.gammaC = p.gamma_c;
+  PooledEvents ev(c, 2);
+  if (ev.rc) return ev.rc;
+  float ms = 0.0f;
+  hipError_t e = hipEventRecord(ev[0], c->stream);
+  if (e == hipSuccess) e = sail_launch_temporal_resolve(A, c->stream);
+  if (c->tpMom && e == hipSuccess) {  // moment tracking: blended like the colour, timed with it
+    SailMomentResolveArgs M;
+    memset(&M, 0, sizeof M);
+    M.S = A.S; M.MR = c->tpMR; M.Mout = c->tpMout;
+    M.W = c->W; M.H = c->H; M.mix = A.mix; M.kf = A.kf; M.cap = A.cap;
+    e = sail_launch_moment_resolve(M, c->stream);
+  }
+  if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+  std::vector<uint32_t> host(nt * 2);
+  if (e == hipSuccess) e = hipMemcpy(host.data(), cnt + nt, nt * 8, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && out_rgba) e = hipMemcpy(out_rgba, c->tpOut, np * 16, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && out_rgba8) e = hipMemcpy(out_rgba8, A.out8, np * 4, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(c, SAIL_E_HIP, "sail_temporal_resolve: %s", hipGetErrorString(e));
+  c->tpResolved = true;
+  if (info) {
+    memset(info, 0, sizeof *info);
+    info->k = c->k;
+    info->hit_pixels = c->tpHitPixels;
+    info->history_pixels = sumTiles(host, 0, nt);
+    info->nonfinite = sumTiles(host, nt, nt);
+    info->kernel_ms = ms;
+    info->pass_ms[2] = ms;
+  }
+  return SAIL_OK;
+}
+
+int sail_temporal_read(sail_ctx* c, int which, float* out) {
+  if (!c) return SAIL_E_INVALID;
+  if (!out || which < SAIL_TEMPORAL_G_CUR || which > SAIL_TEMPORAL_OUT)
+    return fail(c, SAIL_E_INVALID, "sail_temporal_read: map %d of 0..4 and an output are required", which);
+  if (!c->subs.empty()) return relay(c, sail_temporal_read(c->subs[0], which, out), c->subs[0]);
+  const bool prev = which == SAIL_TEMPORAL_G_PREV || which == SAIL_TEMPORAL_HIST;
+  if (!c->tpWork || !(prev ? c->tpHavePrev : c->tpHaveCur))
+    return fail(c, SAIL_E_STATE, "sail_temporal_read: map %d needs a %s view (a new scene drops both)", which,
+                prev ? "committed" : "current");
+  const float4* maps[5] = {c->tpGcur, c->tpGprev, c->tpHist, c->tpR, c->tpOut};
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(out, maps[which], (size_t)c->W * c->H * 16, hipMemcpyDeviceToHost));
+  return SAIL_OK;
+}
+
+int sail_temporal_load_history(sail_ctx* c, const float* hist, const float* g, const double mvp_prev[16],
+                               const float eye_prev[3]) {
+  if (!c) return SAIL_E_INVALID;
+  if (!hist || !g || !mvp_prev || !eye_prev)
+    return fail(c, SAIL_E_INVALID, "sail_temporal_load_history: hist, g, mvp_prev and eye_prev are required");
+  if (!c->subs.empty()) return relay(c, sail_temporal_load_history(c->subs[0], hist, g, mvp_prev, eye_prev), c->subs[0]);
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (int rc = ensureTemporal(c)) return rc;
+  const size_t bytes = (size_t)c->W * c->H * 16;
+  HIPCHK(c, hipMemcpy(c->tpHist, hist, bytes, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->tpGprev, g, bytes, hipMemcpyHostToDevice));
+  for (int i = 0; i < 16; i++) c->tpPrev.m[i] = (float)mvp_prev[i];
+  memcpy(c->tpPrev.eye, eye_prev, sizeof c->tpPrev.eye);
+  c->tpHavePrev = true;
+  c->tpHaveCur = false;
+  c->tpResolved = false;
+  clearMotion(c);  // a loaded history belongs to the rows as they are now
+  if (c->tpMom) {  // the loaded history carries no moments
+    HIPCHK(c, hipMemsetAsync(c->tpMhist, 0, bytes, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return SAIL_OK;
+}
+
+int sail_temporal_pending_motion(sail_ctx* c, float* motion, float* hist_cap, int* pending) {
+  if (!c) return SAIL_E_INVALID;
+  if (!c->subs.empty()) return relay(c, sail_temporal_pending_motion(c->subs[0], motion, hist_cap, pending), c->subs[0]);
+  for (int r = 0; motion && r < c->n; r++)
+    for (int j = 0; j < 3; j++) motion[r * 3 + j] = c->tpMotionPending ? c->tpMotion[(size_t)r * 4 + j] : 0.0f;
+  if (hist_cap) *hist_cap = c->tpMotionPending ? c->tpMotionCap : INFINITY;
+  if (pending) *pending = c->tpMotionPending ? 1 : 0;
+  return SAIL_OK;
+}
+
+// ---- moment tracking and the temporal filter (include/sail_hip.h; the kernels are sail_tfilter.hip) ---------------------------
+int sail_temporal_moments(sail_ctx* c, int on) {
+  // the arguments first, so that they can be checked without a device (a NULL context's message: sail_last_error(NULL))
+  if (on != 0 && on != 1) return fail(c, SAIL_E_INVALID, "sail_temporal_moments: on must be 0 or 1, not %d", on);
+  if (!c) return fail(c, SAIL_E_INVALID, "sail_temporal_moments: a context is required");
+  if (!c->subs.empty()) return relay(c, sail_temporal_moments(c->subs[0], on), c->subs[0]);
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (!on) {
+    if (c->tpMom) HIPCHK(c, hipFree(c->tpMom));
+    c->tpMom = nullptr;
+    c->tpMhist = c->tpMR = c->tpMout = nullptr;
+    return SAIL_OK;
+  }
+  if (c->tpMom) return SAIL_OK;
+  const size_t np = (size_t)c->W * c->H;
+  // three float4 maps (16 B each) per pixel, then the filter's count of temporal pixels per tile
+  if (int rc = allocOnce(c, &c->tpMom, np * 48 + tiles16(c) * 4, "moment maps")) return rc;
+  float4* base = (float4*)c->tpMom;
+  c->tpMhist = base; c->tpMR = base + np; c->tpMout = base + 2 * np;
+  HIPCHK(c, zeroMoments(c));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SAIL_OK;
+}
+
+int sail_temporal_load_moments(sail_ctx* c, const float* mom) {
+  if (!c) return SAIL_E_INVALID;
+  if (!mom) return fail(c, SAIL_E_INVALID, "sail_temporal_load_moments: mom is required");
+  if (!c->subs.empty()) return relay(c, sail_temporal_load_moments(c->subs[0], mom), c->subs[0]);
+  if (!c->tpMom)
+    return fail(c, SAIL_E_STATE, "sail_temporal_load_moments: moment tracking is off (sail_temporal_moments first)");
+  if (!c->tpHavePrev || c->tpHaveCur)
+    return fail(c, SAIL_E_STATE, "sail_temporal_load_moments: needs a committed history and no current view (right after sail_temporal_load_history)");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(c->tpMhist, mom, (size_t)c->W * c->H * 16, hipMemcpyHostToDevice));
+  return SAIL_OK;
+}
+
+int sail_temporal_read_moments(sail_ctx* c, int which, float* out) {
+  if (!out || which < SAIL_TEMPORAL_M_HIST || which > SAIL_TEMPORAL_M_OUT)
+    return fail(c, SAIL_E_INVALID, "sail_temporal_read_moments: map %d of 0..2 and an output are required", which);
+  if (!c) return fail(c, SAIL_E_INVALID, "sail_temporal_read_moments: a context is required");
+  if (!c->subs.empty()) return relay(c, sail_temporal_read_moments(c->subs[0], which, out), c->subs[0]);
+  if (!c->tpMom)
+    return fail(c, SAIL_E_STATE, "sail_temporal_read_moments: moment tracking is off (sail_temporal_moments first)");
+  const bool prev = which == SAIL_TEMPORAL_M_HIST;
+  if (!c->tpWork || !(prev ? c->tpHavePrev : c->tpHaveCur))
+    return fail(c, SAIL_E_STATE, "sail_temporal_read_moments: map %d needs a %s view (a new scene drops both)", which,
+                prev ? "committed" : "current");
+  const float4* maps[3] = {c->tpMhist, c->tpMR, c->tpMout};
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(out, maps[which], (size_t)c->W * c->H * 16, hipMemcpyDeviceToHost));
+  return SAIL_OK;
+}
+
+int sail_temporal_filter_defaults(sail_tfilter_params* p) {
+  if (!p) return SAIL_E_INVALID;
+  p->iterations = 4;
+  p->sigma_l = 4.0f;
+  p->sigma_x = 0.2f;
+  p->min_hist = 4.0f;
+  p->display = SAIL_FILTER_COLOR;
+  p->gamma_c = 2.2f;
+  return SAIL_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// sail_temporal_filter (demod = false: amin is not read, no map is needed) and sail_temporal_filter_albedo
+int tfilterCall(sail_ctx* c, const char* who, bool demod, const sail_tfilter_params* params, float amin, float* out_rgba,
+                float* out_var, uint8_t* out_rgba8, sail_tfilter_info* info) {
+  // the parameters first, so that they can be checked without a device (a NULL context's message: sail_last_error(NULL))
+  sail_tfilter_params p;
+  sail_temporal_filter_defaults(&p);
+  if (params) p = *params;
+  if (p.iterations < 1 || p.iterations > 6 || !(p.sigma_l > 0.0f) || !std::isfinite(p.sigma_l) || !(p.sigma_x > 0.0f) ||
+      !std::isfinite(p.sigma_x) || !std::isfinite(p.min_hist) || p.min_hist < 1.0f || p.display < SAIL_FILTER_COLOR ||
+      p.display > SAIL_FILTER_TONEMAPPING)
+    return fail(c, SAIL_E_INVALID, "%s: bad parameters (iterations %d of 1..6, sigma_l %g and sigma_x %g finite and > 0, min_hist %g finite and >= 1, display %d of 0..2)",
+                who, p.iterations, (double)p.sigma_l, (double)p.sigma_x, (double)p.min_hist, p.display);
+  if (demod && !aminOk(amin)) return fail(c, SAIL_E_INVALID, "%s: amin %g must be finite and > 0", who, (double)amin);
+  if (!c) return fail(c, SAIL_E_INVALID, "%s: a context is required", who);
+  if (!c->subs.empty()) {  // device 0's reduced frame, AOV and temporal maps, like sail_denoise
+    if (int rc = reducedFrame(c, who)) return rc;
+    return relay(c, tfilterCall(c->subs[0], who, demod, &p, amin, out_rgba, out_var, out_rgba8, info), c->subs[0]);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = sail_sync(c)) return rc;
+  if (!c->tpMom)
+    return fail(c, SAIL_E_STATE, "%s: moment tracking is off (sail_temporal_moments first)", who);
+  if (!c->aovN || !c->aovP)
+    return fail(c, SAIL_E_STATE, "%s: reads the normal and position AOVs (create with SAIL_FLAG_AOV)", who);
+  if (c->accumMode == SAIL_ACCUM_COMPAT8)
+    return fail(c, SAIL_E_STATE, "%s: SAIL_ACCUM_COMPAT8 stores 8-bit frames, which carry no sample count to blend with", who);
+  if (!c->tpHaveCur || !c->tpWork)
+    return fail(c, SAIL_E_STATE, "%s: no current view (sail_temporal_begin first; a new scene drops it)", who);
+  if (!c->tpResolved)
+    return fail(c, SAIL_E_STATE, "%s: the current view is not resolved (sail_temporal_resolve first)", who);
+  if (c->k == 0)
+    return fail(c, SAIL_E_STATE, "%s: no sample of the current view (k = 0: the AOVs belong to another view)", who);
+  if (demod && (!c->albHave || !c->albMap))
+    return fail(c, SAIL_E_STATE, "%s: no albedo map (sail_albedo or sail_albedo_load first; new rows drop it)", who);
+  if (demod && memcmp(&c->albView, &c->tpCur, sizeof c->albView) != 0)
+    return fail(c, SAIL_E_STATE, "%s: the albedo map belongs to another view than the current temporal view", who);
+  const size_t nt = tiles16(c), np = (size_t)c->W * c->H;
+  if (int rc = ensureDenoiseWork(c)) return rc;
+  const DenoiseWork w = denoiseWork(c);  // sail_denoise's work buffers; the count of temporal pixels sits behind the moments
+  uint32_t* dTmp = (uint32_t*)((char*)c->tpMom + np * 48);
+  SailTfilterPrepareArgs A;
+  memset(&A, 0, sizeof A);
+  A.Out = c->tpOut; A.Mout = c->tpMout; A.S = shownAccum(c); A.N = shownAovN(c); A.X = shownAovP(c);
+  A.cv = w.cv[0]; A.g0 = w.g0; A.g1 = w.g1; A.tileBad = w.bad; A.tileTemporal = dTmp;
+  A.W = c->W; A.H = c->H;
+  A.mix = c->accumMode == SAIL_ACCUM_MIX;
+  A.kf = (float)c->k;
+  A.minHist = p.min_hist;
+  const float sx2 = p.sigma_x * 2.0f;
+  A.sx0 = sx2 * sx2;
+  float ms[8] = {}, total = 0.0f;
+  int rc = SAIL_OK;
+  SailTfilterPrepareDemodArgs D;
+  memset(&D, 0, sizeof D);
+  D.P = A; D.alb = c->albMap; D.amin = amin;
+  hipError_t e = runAtrous(c, w, [&] { return demod ? sail_launch_tfilter_prepare_demod(D, c->stream)
+                                                      : sail_launch_tfilter_prepare(A, c->stream); },
+                           p.iterations, p.sigma_l, p.sigma_x, p.display, p.gamma_c, out_rgba, out_var, out_rgba8, ms, &total,
+                           &rc, demod ? c->albMap : nullptr, amin);
+  if (rc) return rc;
+  std::vector<uint32_t> bad(nt), tmp(nt);
+  if (e == hipSuccess) e = hipMemcpy(bad.data(), w.bad, nt * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(tmp.data(), dTmp, nt * 4, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(c, SAIL_E_HIP, "%s: %s", who, hipGetErrorString(e));
+  if (info) {
+    memset(info, 0, sizeof *info);
+    info->k = c->k;
+    info->temporal_pixels = sumTiles(tmp, 0, nt);
+    info->spatial_pixels = (uint64_t)np - info->temporal_pixels;
+    info->nonfinite = sumTiles(bad, 0, nt);
+    info->iterations = p.iterations;
+    info->kernel_ms = total;
+    for (int i = 0; i <= p.iterations; i++) info->pass_ms[i] = ms[i];
+  }
+  return SAIL_OK;
+}
+
+uint32_t* albedoCounts(const sail_ctx* c) { return (uint32_t*)(c->albMap + (size_t)c->W * c->H); }
+
+// the albedo map and its two counts per tile, allocated on first use
+int ensureAlbedo(sail_ctx* c) {
+  return allocOnce(c, &c->albMap, (size_t)c->W * c->H * 16 + tiles16(c) * 8, "albedo map");
+}
+
+void albedoView(sail_ctx* c, const double mvp[16], const float eye[3]) {
+  memset(&c->albView, 0, sizeof c->albView);
+  for (int i = 0; i < 16; i++) c->albView.m[i] = (float)mvp[i];
+  memcpy(c->albView.eye, eye, sizeof c->albView.eye);
+}
+
+}  // namespace
+
+extern "C" {
+
+int sail_temporal_filter(sail_ctx* c, const sail_tfilter_params* params, float* out_rgba, float* out_var,
+                         uint8_t* out_rgba8, sail_tfilter_info* info) {
+  return tfilterCall(c, "sail_temporal_filter", false, params, 0.0f, out_rgba, out_var, out_rgba8, info);
+}
+
+int sail_temporal_filter_albedo(sail_ctx* c, const sail_tfilter_params* params, float amin, float* out_rgba, float* out_var,
+                                uint8_t* out_rgba8, sail_tfilter_info* info) {
+  return tfilterCall(c, "sail_temporal_filter_albedo", true, params, amin, out_rgba, out_var, out_rgba8, info);
+}
+
+// ---- the albedo map of a view (include/sail_hip.h; the kernel is sail_albedo.hip) ----------------------------------------------
+int sail_albedo(sail_ctx* c, const double mvp[16], const float eye[3], int grid, float* out_rgba, sail_albedo_info* info) {
+  if (grid < 1 || grid > 4) return fail(c, SAIL_E_INVALID, "sail_albedo: grid %d of 1..4", grid);
+  if (!c) return fail(c, SAIL_E_INVALID, "sail_albedo: a context is required");
+  if (!mvp || !eye) return fail(c, SAIL_E_INVALID, "sail_albedo: mvp and eye are required");
+  if (!c->subs.empty()) return relay(c, sail_albedo(c->subs[0], mvp, eye, grid, out_rgba, info), c->subs[0]);
+  if (!c->haveScene) return fail(c, SAIL_E_STATE, "sail_albedo: no scene (call sail_set_scene first)");
+  SailGbufferArgs G;
+  if (int rc = gbufferArgs(c, "sail_albedo", mvp, eye, &G)) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = sail_sync(c)) return rc;
+  if (int rc = ensureAlbedo(c)) return rc;
+  const size_t nt = tiles16(c), np = (size_t)c->W * c->H;
+  SailAlbedoArgs A;
+  memset(&A, 0, sizeof A);
+  A.prims = c->prims; A.texparams = c->tp; A.n = c->n; A.tn = c->tn;
+  A.texMask = c->plugins.texture_mask;
+  memcpy(A.d, G.d, sizeof A.d);
+  memcpy(A.eye, eye, sizeof A.eye);
+  A.W = c->W; A.H = c->H; A.grid = grid;
+  A.A = c->albMap;
+  A.tileHit = albedoCounts(c); A.tilePartial = A.tileHit + nt;
+  c->albHave = false;  // a call that fails leaves no map
+  PooledEvents ev(c, 2);
+  if (ev.rc) return ev.rc;
+  float ms = 0.0f;
+  hipError_t e = hipEventRecord(ev[0], c->stream);
+  if (e == hipSuccess) e = sail_launch_albedo(A, c->stream);
+  if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+  std::vector<uint32_t> host(nt * 2);
+  if (e == hipSuccess) e = hipMemcpy(host.data(), A.tileHit, nt * 8, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && out_rgba) e = hipMemcpy(out_rgba, c->albMap, np * 16, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(c, SAIL_E_HIP, "sail_albedo: %s", hipGetErrorString(e));
+  albedoView(c, mvp, eye);
+  c->albHave = true;
+  if (info) {
+    memset(info, 0, sizeof *info);
+    info->hit_pixels = sumTiles(host, 0, nt);
+    info->partial_pixels = sumTiles(host, nt, nt);
+    info->grid = grid;
+    info->kernel_ms = ms;
+  }
+  return SAIL_OK;
+}
+
+int sail_albedo_load(sail_ctx* c, const float* map, const double mvp[16], const float eye[3]) {
+  if (!c) return SAIL_E_INVALID;
+  if (!map || !mvp || !eye) return fail(c, SAIL_E_INVALID, "sail_albedo_load: map, mvp and eye are required");
+  if (!c->subs.empty()) return relay(c, sail_albedo_load(c->subs[0], map, mvp, eye), c->subs[0]);
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (int rc = ensureAlbedo(c)) return rc;
+  HIPCHK(c, hipMemcpy(c->albMap, map, (size_t)c->W * c->H * 16, hipMemcpyHostToDevice));
+  albedoView(c, mvp, eye);
+  c->albHave = true;
+  return SAIL_OK;
+}
+
+int sail_albedo_read(sail_ctx* c, float* out) {
+  if (!c) return SAIL_E_INVALID;
+  if (!out) return fail(c, SAIL_E_INVALID, "sail_albedo_read: an output is required");
+  if (!c->subs.empty()) return relay(c, sail_albedo_read(c->subs[0], out), c->subs[0]);
+  if (!c->albHave || !c->albMap)
+    return fail(c, SAIL_E_STATE, "sail_albedo_read: no albedo map (sail_albedo or sail_albedo_load first; new rows drop it)");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(out, c->albMap, (size_t)c->W * c->H * 16, hipMemcpyDeviceToHost));
+  return SAIL_OK;
+}
+
+}  // extern "C"

@@ -7,11 +7,14 @@ cd "$(dirname "$0")/../sail_amd"
 mkdir -p lib/variants build/variants
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 COMMON="-O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-slp-vectorize -Wno-unused-function --offload-arch=gfx950"
-$HIPCC $COMMON -c csrc/sail_capi.cpp -o build/variants/sail_capi.o
-$HIPCC $COMMON -c csrc/sail_hostmath.cpp -o build/variants/sail_hostmath.o
+# the host code: every csrc/*.cpp, and the generated sources (in build/variants/, so compiled once)
 python3 gen_jit_src.py build/variants/sail_jit_src.cpp csrc
-$HIPCC $COMMON -c csrc/sail_jit.cpp -o build/variants/sail_jit.o
-$HIPCC $COMMON -c build/variants/sail_jit_src.cpp -o build/variants/sail_jit_src.o
+HOST=""
+for s in csrc/*.cpp build/variants/sail_jit_src.cpp; do
+  o=build/variants/$(basename $s .cpp).o
+  $HIPCC $COMMON -c $s -o $o
+  HOST="$HOST $o"
+done
 while [ $# -ge 2 ]; do
   name=$1; flags=$2; shift 2
   # the device code is one translation unit, like the product: sail_kernels.hip (sail_noise.hip + sail_denoise.hip +
@@ -19,7 +22,6 @@ while [ $# -ge 2 ]; do
   src=sail_kernels.hip; pre=""
   case "$flags" in src=*) src=${flags%% *}; src=${src#src=}; flags=${flags#src=$src}; pre="-include csrc/sail_noise.hip -include csrc/sail_denoise.hip"; esac
   $HIPCC $COMMON $flags -Icsrc $pre -c csrc/$src -o build/variants/trace_$name.o
-  $HIPCC -shared -fPIC --offload-arch=gfx950 build/variants/trace_$name.o build/variants/sail_capi.o \
-    build/variants/sail_hostmath.o build/variants/sail_jit.o build/variants/sail_jit_src.o -o lib/variants/libsail_hip_$name.so -ldl
+  $HIPCC -shared -fPIC --offload-arch=gfx950 build/variants/trace_$name.o $HOST -o lib/variants/libsail_hip_$name.so -ldl
   echo "built $name ($flags)"
 done

@@ -16,10 +16,13 @@ python3 $d/gen_jit_src.py $d/sail_jit_src.cpp $d
 PIDS=""
 # the device code is one translation unit (sail_kernels.hip); revisions before the noise estimate have sail_trace.hip alone
 DEV=sail_trace.hip; [ -f $d/sail_kernels.hip ] && DEV=sail_kernels.hip
-for s in $DEV sail_capi.cpp sail_hostmath.cpp sail_jit.cpp sail_jit_src.cpp; do
-  $HIPCC $COMMON -c $d/$s -o $d/${s%.*}.o & PIDS="$PIDS $!"
+# the host code: every *.cpp the revision has, the generated sail_jit_src.cpp among them (written above, compiled once)
+OBJS=""
+for s in $d/$DEV $d/*.cpp; do
+  $HIPCC $COMMON -c $s -o ${s%.*}.o & PIDS="$PIDS $!"
+  OBJS="$OBJS ${s%.*}.o"
 done
 for p in $PIDS; do wait $p; done
-$HIPCC -shared -fPIC --offload-arch=gfx950 $d/${DEV%.*}.o $d/sail_capi.o $d/sail_hostmath.o $d/sail_jit.o $d/sail_jit_src.o \
+$HIPCC -shared -fPIC --offload-arch=gfx950 $OBJS \
   -o sail_amd/lib/variants/libsail_hip_$NAME.so -ldl -lpthread
 echo "built $NAME from $REV"

@@ -15,14 +15,15 @@ for name in "$@"; do
   python3 tools/study.py $name $d
   # the device code as one translation unit, like the product (sail_kernels.hip = sail_noise.hip + sail_denoise.hip + sail_trace.hip)
   $HIPCC $COMMON -c $d/sail_kernels.hip -o $d/sail_trace.o &
-  $HIPCC $COMMON -c $d/sail_capi.cpp -o $d/sail_capi.o &
-  $HIPCC $COMMON -c $d/sail_hostmath.cpp -o $d/sail_hostmath.o &
+  # the host code: every *.cpp of the copy, the generated sail_jit_src.cpp among them (written first, compiled once)
   python3 sail_amd/gen_jit_src.py $d/sail_jit_src.cpp $d
-  $HIPCC $COMMON -c $d/sail_jit.cpp -o $d/sail_jit.o &
-  $HIPCC $COMMON -c $d/sail_jit_src.cpp -o $d/sail_jit_src.o &
+  OBJS=$d/sail_trace.o
+  for s in $d/*.cpp; do
+    $HIPCC $COMMON -c $s -o ${s%.cpp}.o &
+    OBJS="$OBJS ${s%.cpp}.o"
+  done
   wait
-  for o in sail_trace sail_capi sail_hostmath sail_jit sail_jit_src; do [ -s $d/$o.o ] || { echo "study $name: $o failed"; exit 1; }; done
-  $HIPCC -shared -fPIC --offload-arch=gfx950 $d/sail_trace.o $d/sail_capi.o $d/sail_hostmath.o $d/sail_jit.o \
-    $d/sail_jit_src.o -o sail_amd/lib/variants/libsail_hip_$name.so -ldl
+  for o in $OBJS; do [ -s $o ] || { echo "study $name: $o failed"; exit 1; }; done
+  $HIPCC -shared -fPIC --offload-arch=gfx950 $OBJS -o sail_amd/lib/variants/libsail_hip_$name.so -ldl
   echo "built $name"
 done
