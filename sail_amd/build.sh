@@ -13,8 +13,7 @@ rm -f build/*.o  # a failed compile must not leave an older object to link
 # the per-plugin-set kernels compiled at run time (sail_jit.cpp) carry the kernel sources in the library
 python3 gen_jit_src.py build/sail_jit_src.cpp csrc
 PIDS=""
-# the device code: csrc/sail_kernels.hip = sail_noise.hip + sail_denoise.hip + sail_tfilter.hip + sail_trace.hip + sail_temporal.hip + sail_albedo.hip as one
-# translation unit (one code object)
+# the device code: csrc/sail_kernels.hip lists every kernel file; one translation unit (one code object)
 $HIPCC $COMMON --offload-arch=$ARCH -c csrc/sail_kernels.hip -o build/sail_trace.o ${SAIL_EXTRA:-} & PIDS="$PIDS $!"
 $HIPCC $COMMON --offload-arch=$ARCH -DSAIL_PHASE_TIMING=1 -c csrc/sail_kernels.hip -o build/sail_trace_phase.o & PIDS="$PIDS $!"
 # the host code: every csrc/*.cpp, and the generated sources (in build/, so compiled once)

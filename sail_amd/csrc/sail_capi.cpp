@@ -181,7 +181,7 @@ void dropValues(sail_ctx* c) {
 // (sail_plan_settle; after: SAIL_DEBUG_JIT_VALUES_AFTER)
 bool settledFor(uint64_t settled, int after) { return after >= 0 && settled >= (uint64_t)after; }
 // What a path's last bounce can add at a hit on each row (SailTraceArgs.lastQuietRows / lastSkipSort), decided with
-// the kernel's own tests and f32 operations on the values it reads (sail_trace.hip shadeLast: emission, matCat,
+// the kernel's own tests and f32 operations on the values it reads (sail_shade.h shadeLast: emission, matCat,
 // matRow -> kd, sigma, the Cornellbox wall constants or the uniform texture's colour). `lights`: the kernel that will
 // run has a light plugin compiled in (shadeLast then declines every lit matte hit).
 //   quiet: the emission words are +0.0f bit for bit (the facing test can only zero them again), and the row is not a
@@ -199,7 +199,7 @@ void lastBounceRows(const std::vector<SailPrim>& prims, const float* tp, int tn,
   *skipSort = 0;
   const int n = (int)prims.size();
   if (n < 1 || n > 32 || tn < 1 || !tp) return;
-  constexpr float kEps = 1e-5f, kInvPI = 0.3183098861837907f;  // sail_trace.hip
+  constexpr float kEps = 1e-5f, kInvPI = 0.3183098861837907f;  // sail_geom.h
   bool skip = true, any = false;
   for (int i = 0; i < n; i++) {
     const SailPrim& p = prims[(size_t)i];
@@ -245,7 +245,7 @@ void lastBounceRows(const std::vector<SailPrim>& prims, const float* tp, int tn,
 // without bit 8) would read its light sampler's geometry rows, textures and a full texParams table through the constant
 // tables too, which no test covers: it keeps its types kernel.
 // jit: the SAIL_DEBUG_JIT switches; bit 32 gives scenes of at most kSailJitRowRecordMax rows the row-shading form
-// (SAIL_JIT_ROWSHADE in sail_trace.hip).
+// (SAIL_JIT_ROWSHADE in sail_geom.h).
 bool valueSpecFor(const SailJitSpec& types, const std::vector<uint32_t>& rowWords, const float* tp, int tn, int jit, SailJitSpec* out) {
   const bool cornellSet = (types.ks & ~SAIL_KSET_CORNELL_SHAPES) == 0 && (types.km & ~SAIL_KSET_CORNELL_MATS) == 0 &&
                           (types.kt & ~SAIL_KSET_CORNELL_TEX) == 0 && types.kl == 0;
@@ -577,7 +577,7 @@ double primExtent(const std::vector<SailPrim>& prims) {
   return m;
 }
 
-// The fused pre-cull form (sail_trace.hip padHitF) tests each slab plane as fma(a, R, -RN(o R)): the plane
+// The fused pre-cull form (sail_geom.h padHitFMask) tests each slab plane as fma(a, R, -RN(o R)): the plane
 // lands within |o| 2^-24 of where the plain (a - o) R puts it, so the test stays conservative while that is
 // far inside the 1e-3 padding. |o| < 4096 keeps it under 2.5e-4; it also keeps o R finite with R <= 1e30.
 bool cullFmaOk(const sail_ctx* c) {

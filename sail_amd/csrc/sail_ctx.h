@@ -14,7 +14,7 @@
 #include "../../include/sail_hip.h"
 #include "sail_device.h"
 
-// launch wrappers defined next to the kernels (sail_trace.hip)
+// launch wrappers defined next to the kernels (sail_trace_sets.hip, sail_wavefront.hip, sail_frame.hip)
 hipError_t sail_launch_trace(const SailTraceArgs& A, int blocks, hipStream_t s);
 // sail_jit.cpp: the trace kernel pair compiled at run time for exactly one plugin set (on the current device)
 #include "sail_jit.h"

@@ -34,8 +34,8 @@
 //  * plain vector stores only, no atomics: equal data give equal bits;
 //  * the demodulated instances ("sail_albedo_kernel and the albedo-demodulated filters") are second
 //    instances of the same bodies, entry points of their own, not run-time switches: the plain kernels pay no map load.
-// Lives in its own file and defines no macro: the text of sail_trace.hip is embedded in the library and hashed into every
-// run-time kernel's cache key. Built with the library's flags (no contraction, no fast math: `/` is the IEEE divide).
+// Lives in its own file, no part of the text embedded in the library and hashed into every run-time kernel's cache key
+// (sail_amd/gen_jit_src.py), and defines no macro. Built with the library's flags (no contraction, no fast math: `/` is the IEEE divide).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "sail_post.h"

@@ -75,8 +75,8 @@ struct SailTraceArgs {
   int kernelSet;            // SAIL_KSET_*: the precompiled plugin-set kernel to launch
   // sample groups: sampleGroups workgroups share each 16x16 block, group g renders samples [g*groupSpp,
   // (g+1)*groupSpp); group 0 adds its samples to the accumulator itself, the others stage theirs, and
-  // sail_accum_kernel then adds the staged ones in sample order, so the sums are bit-identical to one workgroup
-  // doing all samples
+  // the accumulation pass (sail_frame.hip) then adds the staged ones in sample order, so the sums are bit-identical to
+  // one workgroup doing all samples
   int sampleGroups, groupSpp;
   int groupHome;            // 1: group 0 accumulated its samples itself (SAIL_GROUP_HOME_FOR), the stage starts at groupSpp
   float* stage;             // three f32 planes per sample: stage[(3k + c) * stageStride + slot]
@@ -110,7 +110,7 @@ enum { SAIL_KSET_GENERIC = 0, SAIL_KSET_CORNELL = 1, SAIL_KSET_ROOM = 2 };
 // Group home: with sample groups, the room kernel's first group adds its samples to the accumulator itself and the
 // other groups stage theirs (C3 +1 %); in the other kernels the extra path costs more registers than the staged
 // samples it saves (C2 -1.4 %, C4 -0.6 %), so every group stages. Shared by the kernel (traceTileCompact kHome) and the
-// host (which tells sail_accum_kernel where the staged samples start).
+// host (which tells the accumulation pass where the staged samples start).
 #define SAIL_GROUP_HOME_FOR(kernelSet) ((kernelSet) == SAIL_KSET_ROOM)
 // the exact segment counter is kept as this many partial sums (spread atomics), added on readback
 #define SAIL_SEG_SLOTS 64
@@ -141,7 +141,7 @@ struct SailFilterArgs {
   int halo;                 // window filters: LDS tile halo in pixels (0: taps read global memory)
 };
 
-// multi-device frame reduction on one GPU (sail_sum_kernel): dst = the sum of src[0..nsrc) in rank order
+// multi-device frame reduction on one GPU (sail_frame.hip): dst = the sum of src[0..nsrc) in rank order
 #define SAIL_SUM_MAX_SRC 64
 struct SailSumArgs {
   const float4* src[SAIL_SUM_MAX_SRC];

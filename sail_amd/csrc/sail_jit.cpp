@@ -5,7 +5,8 @@
 // and Shader.combinefs links the result (src/core/shader.js:58-76), inside Renderer.update (src/core/renderer.js:45-52),
 // in milliseconds. This build precompiles kernels for two plugin sets (the Cornell box, rooms of boxes / spheres /
 // rectangles) and the all-plugin one; a scene gets a kernel compiled for exactly its plugin set (and rows) here, from the
-// same sail_trace.hip (embedded in the library at build time, sail_jit_src.cpp), with the product's floating-point flags.
+// same sources (sail_trace.hip and the headers it includes, embedded in the library at build time by gen_jit_src.py as
+// sail_jit_src.cpp), with the product's floating-point flags.
 //
 // A hipRTC compile takes seconds, so it never runs on the caller's thread: the first request for a spec starts a
 // background build, and until its module is loaded the context launches the precompiled kernel of the scene's set (the
@@ -50,7 +51,7 @@
 extern const char* const sail_jit_src_names[];
 extern const char* const sail_jit_src_texts[];
 extern const int sail_jit_src_count;
-extern const int sail_trace_phase_timing;  // sail_trace.hip: 1 in the phase-timing build (libsail_hip_phase.so)
+extern const int sail_trace_phase_timing;  // sail_frame.hip: 1 in the phase-timing build (libsail_hip_phase.so)
 
 int sailJitThreads(const SailJitSpec& s) { return s.nt ? s.nt : (s.mode == 1 ? 1024 : 256); }
 bool sailJitSpecEqual(const SailJitSpec& a, const SailJitSpec& b) {

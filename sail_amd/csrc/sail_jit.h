@@ -7,7 +7,7 @@
 
 constexpr int kSailJitMaxRows = 8;  // scenes of at most this many rows can be compiled for their rows (flat path)
 constexpr int kSailJitMaxFlatTp = 32;  // flat forms copy texParams tables of at most this many rows into LDS
-constexpr int kSailJitRowRecordMax = 3;  // value kernels of at most this many rows: a hit record per row (sail_trace.hip kRowRecordMax)
+constexpr int kSailJitRowRecordMax = 3;  // value kernels of at most this many rows: a hit record per row (sail_geom.h kRowRecordMax)
 struct SailJitSpec {
   uint32_t ks = 0, km = 0, kt = 0, kl = 0;  // plugin masks: shapes, materials, textures, lights
   int mode = 0;                             // sail_jit_mode (include/sail_hip.h): 0 flat, 1 pre-cull, 2 room family
@@ -18,13 +18,13 @@ struct SailJitSpec {
   int ns = 1;                               // samples of each pixel in flight per workgroup (1, 4, 16: traceTileCompact)
   int nt = 0;                               // threads per workgroup (128 .. 1,024); 0 = the form's own (1,024 pre-cull, 256)
   int types[kSailJitMaxRows] = {};
-  // A value kernel (flat form with rows, SAIL_JIT_ROWVALS in sail_trace.hip): the words of the decoded rows (rows x 32,
+  // A value kernel (flat form with rows, SAIL_JIT_ROWVALS in sail_geom.h): the words of the decoded rows (rows x 32,
   // the bytes of the SailPrim array the host uploads) and of the texParams table (16 per row, at most kSailJitMaxFlatTp
   // rows; may be none). Both empty: the types kernel. Compared and keyed as words, never as floats: +0 / -0 and two NaN
   // payloads are different kernels.
   std::vector<uint32_t> rowWords, tpWords;
   // rowForm 1: a value kernel of at most kSailJitRowRecordMax rows in the row-shading form (SAIL_JIT_ROWSHADE in
-  // sail_trace.hip; SAIL_DEBUG_JIT bit 32). rowShade: the rows (bit i: row i) whose row-uniform waves run the rest of the
+  // sail_geom.h; SAIL_DEBUG_JIT bit 32). rowShade: the rows (bit i: row i) whose row-uniform waves run the rest of the
   // bounce in their row's branch, on the row's material constants; rowQuiet: those of them whose copy leaves the
   // radiance alone (quiet rows, sail_capi.cpp lastBounceRows). Both 0: the kernel is the plain value kernel's code.
   // All 0 in every types spec.

@@ -16,8 +16,8 @@
 //    sail_noise_copy_kernel, the masked sail_noise_mark) leaves the P of a frozen tile alone; the estimate reads no mask;
 //  * plain vector stores only.
 // The finite test and the wave count are sail_post.h's; the reduction stays here, since the sum and the count share its
-// one barrier. Lives in its own file: the text of sail_trace.hip is embedded in the library and hashed into every
-// run-time kernel's cache key. Built with the library's flags (no contraction, no fast math: `/` and sqrt are the IEEE ones, as
+// one barrier. Lives in its own file, no part of the text embedded in the library and hashed into every run-time
+// kernel's cache key (sail_amd/gen_jit_src.py). Built with the library's flags (no contraction, no fast math: `/` and sqrt are the IEEE ones, as
 // sail_math_probe functions 7 and 8 show on the device).
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -3,8 +3,7 @@
 // The formulas and their f32 operation order are part of the C ABI (include/sail_hip.h) and are checked bit for bit, so
 // each lives here once. A piece is here only where its sites perform the same operations: a-trous's normal stop
 // (sm::fmax_) and the spatial estimate's (a ternary) agree in value, differ in instructions, and stay where they are.
-// Defines no macro and is no part of a run-time kernel's text (sail_amd/gen_jit_src.py): sail_kernels.hip includes it
-// ahead of sail_trace.hip, whose kernels must compile exactly as they do alone.
+// Defines no macro and is no part of a run-time kernel's text (sail_amd/gen_jit_src.py).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -26,11 +26,11 @@
 //  * the counts are wave ballots, one barrier each (sp::tileCounts), summed per tile on the host;
 //  * lanes outside ragged tiles load nothing and store nothing;
 //  * plain vector stores only, no atomics: equal data give equal bits.
-// Included from sail_kernels.hip AFTER sail_trace.hip (it calls that file's mkRay, primT and constRow) and defines no
-// macro: the text of sail_trace.hip is embedded in the library and hashed into every run-time kernel's cache key. Built
+// mkRay, primT and constRow are sail_geom.h's. No part of a run-time kernel's text (sail_amd/gen_jit_src.py). Built
 // with the library's flags (no contraction, no fast math: `/` is the IEEE divide).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "sail_geom.h"
 #include "sail_post.h"
 
 extern "C" __global__ void __launch_bounds__(256) sail_gbuffer_kernel(SailGbufferArgs A) {

@@ -32,8 +32,8 @@
 //  * texels outside the frame are never loaded; lanes outside ragged tiles store nothing;
 //  * the prepare pass's two counts are wave ballots behind one barrier (sp::tileCounts), summed per tile on the host;
 //  * plain vector stores only, no atomics: equal data give equal bits.
-// Lives in its own file and defines no macro: the text of sail_trace.hip is embedded in the library and hashed into every
-// run-time kernel's cache key. Built with the library's flags (no contraction, no fast math: `/` is the IEEE divide).
+// Lives in its own file, no part of the text embedded in the library and hashed into every run-time kernel's cache key
+// (sail_amd/gen_jit_src.py), and defines no macro. Built with the library's flags (no contraction, no fast math: `/` is the IEEE divide).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "sail_post.h"

@@ -10,10 +10,11 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCENES = ("C1", "C3", "C4", "ALL")
-KERNEL_DEFAULT = "sail_amd/csrc/sail_trace.hip"
-ORACLE_DEFAULT = "oracle/sail_oracle.cpp"
-# where an unqualified name is looked up besides the default file (the math spec lives in headers)
-EXTRA = {KERNEL_DEFAULT: ["sail_amd/csrc/sail_math.h"], ORACLE_DEFAULT: ["oracle/ref_math.h"]}
+# where an unqualified function name is looked up, in this order: the trace kernels' sources (the path loop, the shapes
+# and hit records, the shading, the math spec) and the oracle's; an entry of the map names the file that holds it
+KERNEL_SOURCES = ["sail_amd/csrc/sail_trace.hip", "sail_amd/csrc/sail_geom.h", "sail_amd/csrc/sail_shade.h",
+                  "sail_amd/csrc/sail_math.h"]
+ORACLE_SOURCES = ["oracle/sail_oracle.cpp", "oracle/ref_math.h"]
 
 # functions of the generated program that no path of the trace runs (SURVEY §8(a) "Not on the hot path"):
 # never called, or only reachable through Beckmann (never selected), transmission BxDFs nobody builds, noise
@@ -67,23 +68,22 @@ def _match_close(text: str, i: int, open_c: str, close_c: str) -> int:
 
 
 def function_bodies(path: str, name: str) -> list:
-    """the bodies of every definition of `name` in the file (and its companion headers): an identifier followed by
-    a parameter list and then `{` (optionally after `const`), brace-matched"""
+    """the bodies of every definition of `name` in the file: an identifier followed by a parameter list and then `{`
+    (optionally after `const`), brace-matched"""
     out = []
-    for p in [path] + EXTRA.get(path, []):
-        text = source(p)
-        for m in re.finditer(r"(?<![\w.>])%s\s*\(" % re.escape(name), text):
-            close = _match_close(text, m.end() - 1, "(", ")")
-            if close < 0:
-                continue
-            rest = text[close + 1:close + 40]
-            mm = re.match(r"\s*(const\s*)?\{", rest)
-            if not mm:
-                continue
-            start = close + 1 + mm.end() - 1
-            end = _match_close(text, start, "{", "}")
-            if end > start:
-                out.append(text[start:end + 1])
+    text = source(path)
+    for m in re.finditer(r"(?<![\w.>])%s\s*\(" % re.escape(name), text):
+        close = _match_close(text, m.end() - 1, "(", ")")
+        if close < 0:
+            continue
+        rest = text[close + 1:close + 40]
+        mm = re.match(r"\s*(const\s*)?\{", rest)
+        if not mm:
+            continue
+        start = close + 1 + mm.end() - 1
+        end = _match_close(text, start, "{", "}")
+        if end > start:
+            out.append(text[start:end + 1])
     return out
 
 

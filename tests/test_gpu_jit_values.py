@@ -1,5 +1,5 @@
 """The value kernel on the GPU: a flat-form run-time kernel with the scene's decoded rows and texParams table compiled in
-(SAIL_JIT_ROWVALS in sail_trace.hip), asked for once the rows have stood still for SAIL_DEBUG_JIT_VALUES_AFTER samples
+(SAIL_JIT_ROWVALS in sail_geom.h), asked for once the rows have stood still for SAIL_DEBUG_JIT_VALUES_AFTER samples
 (sail_capi.cpp refreshValues). Every frame is compared bit for bit with the CPU oracle, and every case sets the switch
 explicitly; the value tier is told from the types tier by the build id, against the id obtained with the switch
 negative. Scenes are C1 and variants of it: the value kernel exists for the flat form compiled for rows, which the

@@ -558,7 +558,7 @@ def test_coverage_scenes_bit_exact(gpu, fixtures, monkeypatch, name, W, H, spp, 
 
 @pytest.mark.parametrize("name", ["AREA0", "ALL", "BILERP", "N1"])
 def test_cull_kernel_ungrouped_small_frames(gpu, fixtures, monkeypatch, name):
-    """The ungrouped pre-cull kernel runs 1024-thread workgroups (16 x 64 pixel strips, sail_trace.hip SAIL_CULL_NT):
+    """The ungrouped pre-cull kernel runs 1024-thread workgroups (16 x 64 pixel strips, sail_trace_sets.hip SAIL_CULL_NT):
     forced on for small scenes and ragged frames (sample groups off), it must stay bit-exact"""
     monkeypatch.setitem(capi.DEBUG_DEFAULTS, capi.DEBUG_CULL_MIN_PRIMS, 0)
     monkeypatch.setitem(capi.DEBUG_DEFAULTS, capi.DEBUG_SAMPLE_GROUPS, 1)
@@ -578,7 +578,7 @@ def test_coverage_kernel_selection(gpu, fixtures):
         ctx.close()
 
 
-# ---- the last-bounce shortcut (sail_trace.hip shadeLast) on the materials it must decline or pass NaN through ----
+# ---- the last-bounce shortcut (sail_shade.h shadeLast) on the materials it must decline or pass NaN through ----
 # C1 uses the Cornell kernel (no light plugin), where shadeLast handles every path: Oren-Nayar matte (sigma > 0) must
 # decline to the full bounce (f needs the sampled direction); an infinite kd makes the matte f inf / NaN, which the
 # last bounce's direct term (0 + 0 * f) must carry into the radiance exactly as the full bounce does.
@@ -613,7 +613,7 @@ def test_last_bounce_shortcut_edge_materials(gpu, fixtures, variant, B):
         assert np.isnan(got[..., :3]).any() or np.isinf(got[..., :3]).any()
 
 
-# ---- the phase-timing build (the one instrumentation switch left in sail_trace.hip) ------------------------------
+# ---- the phase-timing build (the one instrumentation switch left in the trace kernels) ------------------------------
 @pytest.mark.parametrize("name,W,H,spp,B", [("C1", 40, 24, 3, 6), ("C3", 40, 24, 3, 5), ("C4", 40, 24, 2, 6)])
 def test_phase_timing_build_bit_exact(gpu, fixtures, monkeypatch, name, W, H, spp, B):
     """libsail_hip_phase.so (-DSAIL_PHASE_TIMING=1, tools/phase_profile.py) renders the oracle's bits in all three

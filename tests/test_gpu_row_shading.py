@@ -1,4 +1,4 @@
-"""Row shading on the GPU (SAIL_JIT_ROWSHADE in sail_trace.hip, SAIL_DEBUG_JIT bit 32): in the value kernel of a scene
+"""Row shading on the GPU (SAIL_JIT_ROWSHADE in sail_geom.h, SAIL_DEBUG_JIT bit 32): in the value kernel of a scene
 of at most three rows, a wave whose paths all hit one quiet row runs the rest of the bounce in that row's branch of the
 hit record, on the row's material constants, and neither loads nor stores the radiance. Every frame here is compared
 bit for bit (raw uint32: a NaN equals only the same NaN) with the CPU oracle and with the switch-off arm's frame, and the

@@ -223,6 +223,30 @@ def test_prebuild_fills_the_shipped_cache_layout(tmp_path, fixtures):
         assert len(files) == count and all(open(d / f, "rb").read(8) == b"SAILJIT1" for f in files)
 
 
+def test_embedded_sources_are_what_a_run_time_kernel_compiles():
+    """The texts embedded in the library (sail_amd/gen_jit_src.py FILES) are hashed into every run-time kernel's cache
+    key, so they are exactly what such a kernel compiles: the closure of the quoted #include lines from sail_trace.hip,
+    nothing reachable missing and nothing unreachable embedded, and none of the kernels and launch wrappers that only
+    the precompiled library has is named in them (an edit to those must leave the keys alone)."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("gen_jit_src", os.path.join(root, "sail_amd", "gen_jit_src.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    texts, todo = {}, ["sail_trace.hip"]
+    while todo:
+        name = todo.pop()
+        if name not in texts:
+            texts[name] = open(os.path.join(root, "sail_amd", "csrc", name)).read()
+            todo += re.findall(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', texts[name], re.M)
+    assert gen.FILES[0] == "sail_trace.hip" and len(set(gen.FILES)) == len(gen.FILES)
+    assert set(gen.FILES) == set(texts), (sorted(set(texts) - set(gen.FILES)), sorted(set(gen.FILES) - set(texts)))
+    absent = ("sail_filter_kernel", "sail_pick_kernel", "sail_math_kernel", "sail_wf_", "sail_accum_kernel",
+              "sail_sum_kernel", "sail_negzero_unowned_kernel", "sail_launch_", "hipLaunchKernelGGL")
+    found = [(f, a) for f in gen.FILES for a in absent if a in texts[f]]
+    assert not found, found
+
+
 @pytest.mark.gpu
 def test_box_compiler_matches_precompiled_kernels(tmp_path, fixtures, product_kernels):
     """on the GPU box itself, the hipRTC the library opens there compiles the all-plugin, room and

@@ -21,9 +21,8 @@ import oracle
 from sail_amd import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNEL_SOURCES = ["sail_amd/csrc/sail_trace.hip", "sail_amd/csrc/sail_math.h", "sail_amd/csrc/sail_device.h",
-                  "sail_amd/csrc/sail_capi.cpp"]
-ORACLE_SOURCES = ["oracle/sail_oracle.cpp", "oracle/ref_math.h"]
+KERNEL_SOURCES = lp.KERNEL_SOURCES + ["sail_amd/csrc/sail_device.h", "sail_amd/csrc/sail_capi.cpp"]
+ORACLE_SOURCES = lp.ORACLE_SOURCES
 
 
 def _src(paths):
@@ -205,7 +204,7 @@ def test_program_defines_match_kernel_and_oracle(fixtures, name):
             assert f32(v) in lits_k and f32(v) in lits_o, (col, v)
     # the object-space frame (OBJECT_SPACE_N/S/T = (0,1,0), (0,0,-1), (1,0,0))
     assert (d["OBJECT_SPACE_N"], d["OBJECT_SPACE_S"], d["OBJECT_SPACE_T"]) == ("vec3(0,1,0)", "vec3(0,0,-1)", "vec3(1,0,0)")
-    # the kernel folds the frame's exact zero products into FMAs (W2L / L2W, sail_trace.hip), documented per row;
+    # the kernel folds the frame's exact zero products into FMAs (W2L / L2W, sail_geom.h), documented per row;
     # the oracle keeps the reference's full dot products over the literal frame
     assert "D V3 W2L(V3 v) {  // (dot(v, (0,0,-1)), dot(v, (1,0,0)), dot(v, (0,1,0)))" in kern
     assert "D V3 L2W(V3 v) {  // (0,0,-1) v.x + (1,0,0) v.y + (0,1,0) v.z" in kern
@@ -260,6 +259,8 @@ def test_literal_map_is_not_vacuous():
         e = table["random2"][v]
         assert e["kernel"].endswith(":hash1") or e["kernel"].endswith(":random2"), e
         assert e["oracle"].endswith(":hash1") or e["oracle"].endswith(":random2"), e
-    assert not lp.literal_in_function("sail_amd/csrc/sail_trace.hip", "hash1", "12.9897", "value")
+    assert lp.literal_in_function("sail_amd/csrc/sail_shade.h", "random2", "12.9898", "value")
+    assert not lp.literal_in_function("sail_amd/csrc/sail_shade.h", "random2", "12.9897", "value")
+    assert not lp.literal_in_function("sail_amd/csrc/sail_shade.h", "hash1", "12.9897", "value")
     assert table["equalZero"]["1e-3"]["kernel"].endswith(":equalZero")
     assert table["point_sample"]["0.1"]["kernel"].endswith(":lightPrep")

@@ -1,7 +1,8 @@
 #!/bin/sh
 # Builds experimental variants of libsail_hip.so (same sources, different -D flags) into sail_amd/lib/variants/.
 # Usage: tools/build_variants.sh name1 "-DFLAG=1" name2 "-DFLAG=2" ...
-# A flags string may start with "src=<file under csrc/>" to build that source in place of sail_trace.hip.
+# A flags string may start with "src=<file under csrc/>" to build that source in place of sail_trace_sets.hip (the
+# precompiled plugin sets and sail_launch_trace).
 set -e
 cd "$(dirname "$0")/../sail_amd"
 mkdir -p lib/variants build/variants
@@ -17,11 +18,15 @@ for s in csrc/*.cpp build/variants/sail_jit_src.cpp; do
 done
 while [ $# -ge 2 ]; do
   name=$1; flags=$2; shift 2
-  # the device code is one translation unit, like the product: sail_kernels.hip (sail_noise.hip + sail_denoise.hip +
-  # sail_trace.hip), or the first two force-included in front of the source that stands in for sail_trace.hip
-  src=sail_kernels.hip; pre=""
-  case "$flags" in src=*) src=${flags%% *}; src=${src#src=}; flags=${flags#src=$src}; pre="-include csrc/sail_noise.hip -include csrc/sail_denoise.hip"; esac
-  $HIPCC $COMMON $flags -Icsrc $pre -c csrc/$src -o build/variants/trace_$name.o
+  # the device code is one translation unit, like the product: sail_kernels.hip, or a copy of that list with the
+  # stand-in's name in the place of sail_trace_sets.hip
+  dev=csrc/sail_kernels.hip
+  case "$flags" in src=*)
+    src=${flags%% *}; src=${src#src=}; flags=${flags#src=$src}
+    dev=build/variants/kernels_$name.hip
+    sed "s/\"sail_trace_sets.hip\"/\"$src\"/" csrc/sail_kernels.hip > $dev;;
+  esac
+  $HIPCC $COMMON $flags -Icsrc -c $dev -o build/variants/trace_$name.o
   $HIPCC -shared -fPIC --offload-arch=gfx950 build/variants/trace_$name.o $HOST -o lib/variants/libsail_hip_$name.so -ldl
   echo "built $name ($flags)"
 done

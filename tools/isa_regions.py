@@ -106,7 +106,7 @@ def part(names, line):
             return "hit record"
         # else: the hit record in front of it
     if not names:
-        return "kernel body (sort, gather, sample loop)" if 1929 <= line <= 2100 else "kernel body (setup, sample end)"
+        return "kernel body (sort, gather, sample loop)" if 237 <= line <= 408 else "kernel body (setup, sample end)"  # sail_trace.hip lines
     top = names[0]
     if top.startswith(("mkRay", "operator+", "operator-", "operator*", "operator/")):
         return "primary ray (sample start)"

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Static ISA attribution report of the trace kernels (tools/isa.sh output /tmp/isa/trace_g.s): per kernel, the
 instruction count by opcode class, by source function (the enclosing D / SM_D / __global__ definition of each
-line-table entry in sail_trace.hip / sail_math.h) and the register-spill (scratch) instructions by function.
+line-table entry in the trace kernels' sources, TRACE_SOURCES) and the register-spill (scratch) instructions by function.
 Static counts: code size per function and class, not execution frequency (no PC sampling on this pool).
 Usage: python tools/isa_report.py > profiles/r02_isa_attribution.txt"""
 import collections
@@ -9,8 +9,8 @@ import os
 import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = {"sail_trace.hip": os.path.join(ROOT, "sail_amd", "csrc", "sail_trace.hip"),
-       "sail_math.h": os.path.join(ROOT, "sail_amd", "csrc", "sail_math.h")}
+TRACE_SOURCES = ["sail_trace_sets.hip", "sail_trace.hip", "sail_geom.h", "sail_shade.h", "sail_math.h"]
+SRC = {f: os.path.join(ROOT, "sail_amd", "csrc", f) for f in TRACE_SOURCES}
 KERNELS = ["sail_trace_kernel_cornell", "sail_trace_kernel_room", "sail_trace_kernel", "sail_trace_kernel_cull"]
 CLASSES = [("scratch (spill)", r"^scratch_"), ("LDS", r"^ds_"), ("vector memory", r"^(global|buffer|flat)_"),
            ("scalar memory", r"^s_(load|buffer_load)"), ("f64", r"^v_\w+_f64"), ("transcendental", r"^v_(rcp|rsq|sqrt|sin|cos|exp|log)_"),

@@ -19,7 +19,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import literal_pins as lp  # noqa: E402
 
 K, O = "kernel", "oracle"
-# GLSL function -> ([kernel functions], [oracle functions]); "file:function" when the file is not the default
+# GLSL function -> ([kernel functions], [oracle functions]); "file:function" when the file is not one of the side's
+# sources (literal_pins.KERNEL_SOURCES / ORACLE_SOURCES, searched in order)
 MAP = {
     "area_sample": (["lightPrep", "sampleGeometry"], ["light_sample", "sampleGeometry"]),
     "checkerboard": (["getSurfaceColor"], ["getSurfaceColor"]),
@@ -144,10 +145,11 @@ def main():
                 entry[v] = {"kind": "folded", "why": lp.FOLDED[(fn, v)]}
                 continue
             hit = {}
-            for side, cands, default in ((K, kc, lp.KERNEL_DEFAULT), (O, oc, lp.ORACLE_DEFAULT)):
+            for side, cands, sources in ((K, kc, lp.KERNEL_SOURCES), (O, oc, lp.ORACLE_SOURCES)):
                 for cand in cands:
-                    path, func = cand.split(":") if ":" in cand else (default, cand)
-                    if lp.literal_in_function(path, func, v, kind):
+                    paths, func = ([cand.split(":")[0]], cand.split(":")[1]) if ":" in cand else (sources, cand)
+                    path = next((p for p in paths if lp.literal_in_function(p, func, v, kind)), None)
+                    if path:
                         hit[side] = f"{path}:{func}"
                         break
             if len(hit) != 2:

@@ -14,7 +14,8 @@ for f in $(git ls-tree --name-only $REV sail_amd/csrc/); do git show $REV:$f > $
 git show $REV:sail_amd/gen_jit_src.py > $d/gen_jit_src.py
 python3 $d/gen_jit_src.py $d/sail_jit_src.cpp $d
 PIDS=""
-# the device code is one translation unit (sail_kernels.hip); revisions before the noise estimate have sail_trace.hip alone
+# the device code is one translation unit (sail_kernels.hip, whatever files the revision lists in it); revisions before
+# the noise estimate have sail_trace.hip alone
 DEV=sail_trace.hip; [ -f $d/sail_kernels.hip ] && DEV=sail_kernels.hip
 # the host code: every *.cpp the revision has, the generated sail_jit_src.cpp among them (written above, compiled once)
 OBJS=""

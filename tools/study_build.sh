@@ -13,7 +13,7 @@ for name in "$@"; do
   d=sail_amd/build/study/$name/csrc   # two levels below the root, like sail_amd/csrc: "../../include" resolves
   rm -rf sail_amd/build/study/$name && mkdir -p $d && cp sail_amd/csrc/* $d/ && ln -sfn ../../../include sail_amd/build/study/include
   python3 tools/study.py $name $d
-  # the device code as one translation unit, like the product (sail_kernels.hip = sail_noise.hip + sail_denoise.hip + sail_trace.hip)
+  # the device code as one translation unit, like the product (sail_kernels.hip lists every kernel file)
   $HIPCC $COMMON -c $d/sail_kernels.hip -o $d/sail_trace.o &
   # the host code: every *.cpp of the copy, the generated sail_jit_src.cpp among them (written first, compiled once)
   python3 sail_amd/gen_jit_src.py $d/sail_jit_src.cpp $d
