@@ -125,6 +125,10 @@ enum sail_debug_option {
    * 32 the value kernel (SAIL_DEBUG_JIT_VALUES_AFTER) of a scene of at most 3 rows in the row-shading form: a wave whose
    * paths all hit one quiet row (no emission, a light term of exactly +0) shades in that row's branch, on the row's
    * material constants and without touching the radiance (profiles/rowshade.jsonl).
+   * 64, inverted (a study switch: the default leaves it clear): the value kernel WITHOUT its deferred Sphere row. A value
+   * kernel otherwise leaves the root solve of the scene's first Sphere row undone in the sweep of every bounce that sorts
+   * its paths and is not the last, sorts the rays that may hit it under the sphere's key, and finishes the solve in the
+   * sphere's waves after the sort (profiles/spheredefer.jsonl).
    * 0: the precompiled kernels only. Same results [59 = 1 + 2 + 8 + 16 + 32; measured in profiles/r04_jit_*.jsonl] */
   SAIL_DEBUG_JIT = 9,
   /* how long (ms) a launch waits for the scene's run-time kernel while it is still being built in the background; -1:

@@ -29,6 +29,7 @@ DEBUG_WAVEFRONT = 6
 DEBUG_GROUP_ROUNDS = 7
 DEBUG_CULL_GROUP_ROUNDS = 8
 DEBUG_JIT = 9
+JIT_NO_ROWDEFER = 64  # DEBUG_JIT bit, inverted: the value kernel without its deferred Sphere row (include/sail_hip.h)
 DEBUG_JIT_WAIT = 10  # ms a launch waits for the scene's run-time kernel (-1: until built; the C ABI's default is 0)
 DEBUG_JIT_NT = 12  # threads per workgroup of the run-time kernels (0: the form's own)
 DEBUG_JIT_NS = 11  # samples of each pixel in flight per workgroup of the run-time kernels (0: the form's default)

@@ -127,7 +127,7 @@ int jitNtFor(int mode, int kernelSet) {
 // The run-time kernel spec of the context's scene under its switches, or false when none applies.
 // SAIL_DEBUG_JIT bits (include/sail_hip.h): 1 flat scenes outside the Cornell and room sets, 2 pre-cull scenes, 4 room-set
 // scenes, 8 the flat scenes of bit 1 in the room form, 16 flat scenes compiled for their rows as well (any flat scene),
-// 32 the row-shading form of the value kernel (valueSpecFor).
+// 32 the row-shading form of the value kernel (valueSpecFor), 64 the value kernel without its deferred Sphere row.
 bool jitSpecFor(const sail_ctx* c, SailJitSpec* out, int* mode) {
   if (!c->jit || !c->haveScene || c->forceGeneric) return false;
   const int set = kernelSetFor(c);
@@ -245,7 +245,7 @@ void lastBounceRows(const std::vector<SailPrim>& prims, const float* tp, int tn,
 // without bit 8) would read its light sampler's geometry rows, textures and a full texParams table through the constant
 // tables too, which no test covers: it keeps its types kernel.
 // jit: the SAIL_DEBUG_JIT switches; bit 32 gives scenes of at most kSailJitRowRecordMax rows the row-shading form
-// (SAIL_JIT_ROWSHADE in sail_geom.h).
+// (SAIL_JIT_ROWSHADE in sail_geom.h); bit 64 (inverted: the default leaves it clear) takes the deferred Sphere row away.
 bool valueSpecFor(const SailJitSpec& types, const std::vector<uint32_t>& rowWords, const float* tp, int tn, int jit, SailJitSpec* out) {
   const bool cornellSet = (types.ks & ~SAIL_KSET_CORNELL_SHAPES) == 0 && (types.km & ~SAIL_KSET_CORNELL_MATS) == 0 &&
                           (types.kt & ~SAIL_KSET_CORNELL_TEX) == 0 && types.kl == 0;
@@ -271,6 +271,12 @@ bool valueSpecFor(const SailJitSpec& types, const std::vector<uint32_t>& rowWord
     out->rowShade = (int)(quiet & ((1u << types.rows) - 1u));
     out->rowQuiet = out->rowShade;
   }
+  // The scene's first Sphere row is deferred (its root solve runs after the path sort, SAIL_JIT_ROWDEFER in sail_geom.h),
+  // whatever the row-shading switch and the row count; bit 64 asks for the kernel without it.
+  out->rowDefer = -1;
+  if (!(jit & 64))
+    for (int i = types.rows - 1; i >= 0; i--)
+      if (types.types[i] == SAIL_SPHERE) out->rowDefer = i;
   return true;
 }
 // Ask for the scene's value kernel once it has settled (after every refreshJit, and between and after launches): the build
@@ -1085,7 +1091,7 @@ int sail_set_debug(sail_ctx* c, int option, int value) {
     case SAIL_DEBUG_WAVEFRONT: c->wavefront = value; break;
     case SAIL_DEBUG_JIT:
       // the value kernel's other form, derived anew below (refreshValues); the rows did not move: the count stays
-      if ((c->jit ^ value) & 32) { const uint64_t s = c->settled; dropValues(c); c->settled = s; }
+      if ((c->jit ^ value) & (32 | 64)) { const uint64_t s = c->settled; dropValues(c); c->settled = s; }
       c->jit = value;
       break;
     case SAIL_DEBUG_JIT_NT:

@@ -83,17 +83,28 @@ D V3 L2W(V3 v) {  // (0,0,-1) v.x + (1,0,0) v.y + (0,1,0) v.z, row by row as loc
 D bool equalZero(float x) { return x < 1e-3f && x > -1e-3f; }
 D float sgn(int rev) { return rev ? -1.0f : 1.0f; }
 
-D bool quadratic(float A, float B, float C, float& t0, float& t1) {  // utility.glsl:37-51
-  const float discrim = B * B - 4.0f * A * C;
-  if (discrim < 0.0f) return false;
-  const float rootDiscrim = sqrtf_(discrim);
-  float q;
-  if (B < 0.0f) q = -0.5f * (B - rootDiscrim);
-  else q = -0.5f * (B + rootDiscrim);
-  t0 = fdiv(q, A);
-  t1 = fdiv(C, q);
-  if (t0 > t1) { const float tmp = t0; t0 = t1; t1 = tmp; }
+// utility.glsl:37-51, whole (PART 0) or in two parts for a sweep that defers a sphere's roots (sphereT below): 1 the
+// discriminant alone (false when it is negative), 2 the roots of a discriminant that is not negative
+template <int PART>
+D bool quadratic(float A, float B, float C, float& t0, float& t1, float& discrim) {
+  if constexpr (PART != 2) {
+    discrim = B * B - 4.0f * A * C;
+    if (discrim < 0.0f) return false;
+  }
+  if constexpr (PART != 1) {
+    const float rootDiscrim = sqrtf_(discrim);
+    float q;
+    if (B < 0.0f) q = -0.5f * (B - rootDiscrim);
+    else q = -0.5f * (B + rootDiscrim);
+    t0 = fdiv(q, A);
+    t1 = fdiv(C, q);
+    if (t0 > t1) { const float tmp = t0; t0 = t1; t1 = tmp; }
+  }
   return true;
+}
+D bool quadratic(float A, float B, float C, float& t0, float& t1) {
+  float discrim = 0.0f;
+  return quadratic<0>(A, B, C, t0, t1, discrim);
 }
 
 // A ray carries the reciprocals of its direction: every slab test divides by the same three components, and
@@ -181,6 +192,21 @@ constexpr TpTabC kTpTab = __builtin_bit_cast(TpTabC, kTpW);
 #define SAIL_ROWSHADE 1
 #else
 #define SAIL_ROWSHADE 0
+#endif
+// A deferred row (SAIL_JIT_ROWDEFER = the index of a Sphere row of a flat value kernel; absent or -1: none; SAIL_DEBUG_JIT
+// bit 64 leaves it out). At the bounces that sort their paths and are not the last, the sweep runs only the head of
+// that row's sphereT. A lane whose discriminant is not negative is a candidate: it is sorted under the sphere's key with
+// its winner among the other rows, and the sphere's waves run the tail after the gather (sphereResolve), where nearly
+// every lane needs it, instead of nearly every wave of the sweep running it for one lane in ten. Same operations on
+// the same operands, and the sweep's strict-`<`, first-index rule decides between the sphere and the provisional winner.
+#if defined(SAIL_JIT_ROWDEFER) && SAIL_JIT_ROWDEFER >= 0
+#define SAIL_ROWDEFER 1
+static_assert(SAIL_ROWVALS, "a deferred row: in a value kernel");
+static_assert(!SAIL_JIT_CULL && !SAIL_JIT_FAM, "a deferred row: in the flat form");
+constexpr int kDeferRow = SAIL_JIT_ROWDEFER;
+#else
+#define SAIL_ROWDEFER 0
+constexpr int kDeferRow = -1;
 #endif
 
 D V3 P3(const SailPrim& p, int k) { return v3(p.a[k], p.a[k + 1], p.a[k + 2]); }
@@ -373,20 +399,36 @@ D void boxHit(const Ctx& c, const SailPrim& p, const Ray& r, float t, Hit& h, bo
 // ray, so their order is free: the discriminant rejects most rays more cheaply than the six-divide slab test,
 // and only candidate hits pay the exact slab test (same results; C3 +4 %, C4 +5 %, measured).
 // ---- sphere.glsl:45-86 ---------------------------------------------------------------------------------------
-D float sphereT(const SailPrim& p, const Ray& r0, V3* hitOut) {
+// In two parts. The head, up to the discriminant, is what every ray pays; the tail -- the square root, the two divides,
+// the root choice and the slab test -- is what only a ray whose discriminant is not negative runs. sphereT is the head
+// followed by the tail; a sweep that defers the row (SAIL_JIT_ROWDEFER below) runs the head in the sweep and the tail
+// after the path sort, on the same operands.
+// One text, three uses (PART): 0 the whole test; 1 the head alone, which fills q and returns kMaxDistance for a
+// negative discriminant, else 0; 2 the tail, from a q whose discriminant is not negative.
+struct SphereQuad { V3 o, d; float a, b, cc, discrim; };
+template <int PART>
+D float sphereT(const SailPrim& p, const Ray& r0, V3* hitOut, SphereQuad& q) {
   const V3 c = P3(p, 0);
   const float rad = p.a[3];
-  const V3 d = W2L(r0.d), o = W2L(r0.o - c);
-  const float a = dot(d, d), b = 2.0f * dot(o, d), cc = dot(o, o) - rad * rad;
   float t1 = 0.0f, t2 = 0.0f;
-  if (!quadratic(a, b, cc, t1, t2)) return kMaxDistance;
+  if constexpr (PART != 2) {
+    q.d = W2L(r0.d); q.o = W2L(r0.o - c);
+    q.a = dot(q.d, q.d); q.b = 2.0f * dot(q.o, q.d); q.cc = dot(q.o, q.o) - rad * rad;
+    if (!quadratic<1>(q.a, q.b, q.cc, t1, t2, q.discrim)) return kMaxDistance;
+  }
+  if constexpr (PART == 1) return 0.0f;
+  quadratic<2>(q.a, q.b, q.cc, t1, t2, q.discrim);
   if (t2 < kEps) return kMaxDistance;
   float t = t1;
   if (t1 < kEps) t = t2;
   if (t >= kMaxDistance) return kMaxDistance;
   if (!testBoundbox(r0, c - v3s(rad), c + v3s(rad))) return kMaxDistance;
-  if (hitOut) *hitOut = o + t * d;
+  if (hitOut) *hitOut = q.o + t * q.d;
   return t;
+}
+D float sphereT(const SailPrim& p, const Ray& r0, V3* hitOut) {
+  SphereQuad q;
+  return sphereT<0>(p, r0, hitOut, q);
 }
 D float phiOf(float y, float x) {
   float phi = atan2f_(y, x);
@@ -1043,6 +1085,60 @@ D Sweep sweepRay(const Ctx& c, const Ray& r, bool primary) {
   Sweep sw; sw.best = best; sw.bi = bi; sw.bhl = bhl;
   return sw;
 }
+#if SAIL_ROWDEFER
+static_assert(kDeferRow < kRows && kRowType[kDeferRow] == SAIL_SPHERE && HAS(SAIL_JIT_KS, SAIL_SPHERE),
+              "the deferred row is a Sphere the kernel intersects");
+// The deferring sweep: the other rows in order as sweepRows, row kDeferRow's head only. cand: the discriminant is not
+// negative (written so that a NaN one stays a candidate, as sphereT does not reject it), and the ray is not one whose
+// origin is outside the sphere and which moves away from it. For b > 0 and cc > 0 quadratic takes q = -0.5 (b + root)
+// with b + root > 0, so q <= -0, and t0 = q RN(1/a), t1 = cc RN(1/q) are each <= -0 or NaN: the tail either returns
+// kMaxDistance at its t2 < kEps test or goes on with a NaN t and returns kMaxDistance or that NaN, and neither passes
+// the sweep's t < best (tests/test_sphere_defer_host.py). That keeps the mirror's own reflected rays, the one large
+// class of false candidates, out of the sphere's waves.
+// defer (wave-uniform): this bounce defers; otherwise row kDeferRow's head is followed by its tail, which is sphereT. One
+// text for both, so that the other rows' tests are in the kernel once.
+template <int I>
+D void sweepRowsDefer(const Ctx& c, const Ray& r, bool defer, float& best, int& bi, V3& bhl, bool& cand) {
+  if constexpr (I < kRows) {
+    if constexpr (I == kDeferRow) {
+      SphereQuad q;
+      const bool live = sphereT<1>(PRIM(c, I), r, nullptr, q) < kMaxDistance;  // the discriminant is not negative
+      if (defer) {
+        cand = live && !(q.b > 0.0f && q.cc > 0.0f);
+      } else if (live) {
+        V3 hl = v3s(0.0f);
+        const float t = sphereT<2>(PRIM(c, I), r, &hl, q);
+        if (t < best) { best = t; bi = I; bhl = hl; }
+      }
+    } else {
+      V3 hl = v3s(0.0f);
+      const float t = primTy(c, kRowType[I], PRIM(c, I), r, &hl);
+      if (t < best) { best = t; bi = I; bhl = hl; }
+    }
+    sweepRowsDefer<I + 1>(c, r, defer, best, bi, bhl, cand);
+  }
+}
+D Sweep sweepRayDefer(const Ctx& c, const Ray& r, bool defer, bool& cand) {
+  Sweep sw;
+  sw.best = kMaxDistance; sw.bi = -1; sw.bhl = v3s(0.0f);
+  cand = false;
+  sweepRowsDefer<0>(c, r, defer, sw.best, sw.bi, sw.bhl, cand);
+  return sw;
+}
+// A gathered candidate's tail, on the ray it was sorted with: the head's expressions again (the packed path state
+// carries the ray, not a, b, cc), the ray's reciprocals again (mkRay: the gather leaves them out), then the tail. The
+// sphere wins iff the in-order sweep would have taken it: nearer than the provisional winner, or as near with a
+// lower row index (the candidate sweep's rule for a row visited out of order, candType).
+D void sphereResolve(const Ctx& c, const Ray& r, Sweep& sw) {
+  const SailPrim& p = PRIM(c, kDeferRow);
+  const Ray rr = mkRay(r.o, r.d);
+  // the discriminant is the sweep's, bit for bit (the same operations on the same operands): not negative, so the whole
+  // test is the head followed by the tail
+  SphereQuad q;
+  const float t = sphereT<0>(p, rr, nullptr, q);
+  if (t < sw.best || (t == sw.best && kDeferRow < sw.bi)) { sw.best = t; sw.bi = kDeferRow; }
+}
+#endif
 // The winner's local hit point from the ray and its distance: every local-space intersect above ends with
 // hit = o + t * d on the same local o and d (W2L of the ray for the quadrics and the disk, the rectangle's frame), so
 // this is the sweep's own value bit for bit -- the compacting kernels recompute it instead of moving it through LDS

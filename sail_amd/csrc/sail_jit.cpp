@@ -57,7 +57,7 @@ int sailJitThreads(const SailJitSpec& s) { return s.nt ? s.nt : (s.mode == 1 ? 1
 bool sailJitSpecEqual(const SailJitSpec& a, const SailJitSpec& b) {
   const auto t = [](const SailJitSpec& x) {
     return std::tie(x.ks, x.km, x.kt, x.kl, x.mode, x.waves, x.rows, x.ldsFit, x.tn, x.ns, x.nt, x.types[0], x.types[1], x.types[2],
-                    x.types[3], x.types[4], x.types[5], x.types[6], x.types[7], x.rowWords, x.tpWords, x.rowForm, x.rowShade, x.rowQuiet, x.masked);
+                    x.types[3], x.types[4], x.types[5], x.types[6], x.types[7], x.rowWords, x.tpWords, x.rowForm, x.rowShade, x.rowQuiet, x.rowDefer, x.masked);
   };
   return t(a) == t(b);
 }
@@ -71,7 +71,7 @@ struct Key {
   bool operator<(const Key& o) const {
     const auto t = [](const SailJitSpec& x) {
       return std::tie(x.ks, x.km, x.kt, x.kl, x.mode, x.waves, x.rows, x.ldsFit, x.tn, x.ns, x.nt, x.types[0], x.types[1], x.types[2],
-                      x.types[3], x.types[4], x.types[5], x.types[6], x.types[7], x.rowWords, x.tpWords, x.rowForm, x.rowShade, x.rowQuiet, x.masked);
+                      x.types[3], x.types[4], x.types[5], x.types[6], x.types[7], x.rowWords, x.tpWords, x.rowForm, x.rowShade, x.rowQuiet, x.rowDefer, x.masked);
     };
     return t(s) < t(o.s);
   }
@@ -117,7 +117,9 @@ std::string defsFor(const SailJitSpec& sp) {
     };
     vals = (sp.rowForm ? "#define SAIL_JIT_ROWSHADE " + std::to_string(sp.rowShade) + "\n#define SAIL_JIT_ROWQUIET " +
                              std::to_string(sp.rowQuiet) + "\n"
-                       : std::string()) + "#define SAIL_JIT_ROWVALS 1\n#define SAIL_JIT_TPN " + std::to_string(sp.tpWords.size() / 16) +
+                       : std::string()) +
+           (sp.rowDefer >= 0 ? "#define SAIL_JIT_ROWDEFER " + std::to_string(sp.rowDefer) + "\n" : std::string()) +
+           "#define SAIL_JIT_ROWVALS 1\n#define SAIL_JIT_TPN " + std::to_string(sp.tpWords.size() / 16) +
            "\n#define SAIL_JIT_ROW_WORDS " + list(sp.rowWords) + "\n#define SAIL_JIT_TP_WORDS " + list(sp.tpWords) + "\n";
   }
   char defs[768];
@@ -350,6 +352,8 @@ bool validSpec(const SailJitSpec& sp, std::string* err) {
          sp.tpWords.size() % 16 == 0 && sp.tpWords.size() <= (size_t)kSailJitMaxFlatTp * 16;
     for (int i = 0; ok && i < sp.rows; i++) ok = sp.rowWords[(size_t)i * 32] == (uint32_t)sp.types[i];
   }
+  // a deferred row: a Sphere row (shape id 2, sail_device.h) of a value kernel
+  if (ok && sp.rowDefer != -1) ok = isValue(sp) && sp.rowDefer >= 0 && sp.rowDefer < sp.rows && sp.types[sp.rowDefer] == 2;
   if (!ok) *err = "invalid kernel specialisation";
   return ok;
 }

@@ -29,6 +29,9 @@ struct SailJitSpec {
   // radiance alone (quiet rows, sail_capi.cpp lastBounceRows). Both 0: the kernel is the plain value kernel's code.
   // All 0 in every types spec.
   int rowForm = 0, rowShade = 0, rowQuiet = 0;
+  // >= 0: a value kernel that defers this Sphere row's root solve past the path sort (SAIL_JIT_ROWDEFER in sail_geom.h;
+  // SAIL_DEBUG_JIT bit 64 asks for the kernel without it). -1: none, and in every types spec.
+  int rowDefer = -1;
   // 1: the MASKED instances of the spec's kernel pair (sail_trace.hip ownedTileIndex), which a launch under a tile mask
   // runs: a module of its own, built when a context first launches under a mask
   int masked = 0;

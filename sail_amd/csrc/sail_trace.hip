@@ -329,9 +329,27 @@ __device__ __forceinline__ void traceTileCompact(const SailTraceArgs& A) {
       sw.best = kMaxDistance; sw.bi = -1; sw.bhl = v3s(0.0f);
       int key = 0;
       if constexpr (CULL) segsW += (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(alive));
+#if SAIL_ROWDEFER
+      // The deferred row (sail_geom.h kDeferRow): at a bounce that sorts and is not the last (the last needs the true winner
+      // for the quiet-row test and may skip the sort), a candidate of that row travels under the row's key with its
+      // winner among the other rows -- alive even when that is a miss -- and the row's waves finish its test after the
+      // gather (sphereResolve). Its segment is counted here, at its sweep.
+      static_assert(!CULL && !FAM && kRows < kKeys, "a deferred row: in the flat form, sorted by winning row");
+      const bool deferB = depth > 1 && depth < A.maxBounces;  // uniform
+      bool cand = false;
+#endif
       if (alive) {
         if constexpr (!CULL) segs++;
+#if SAIL_ROWDEFER
+        sw = sweepRayDefer(c, ray, deferB, cand);
+#else
         sw = sweepRay(c, ray, depth == 1);
+#endif
+#if SAIL_ROWDEFER
+        if (cand) {
+          key = 1 + kDeferRow;
+        } else
+#endif
         if (sw.best >= kMaxDistance) {  // the path leaves the scene: its radiance is final
           if (depth == 1 && aovs && k + pixel / kPX == A.spp - 1) {  // fstrace.glsl:15-16 with n = p = 0 (GLSL: undefined)
             const size_t g = (size_t)homeY(pixel) * A.W + homeX(pixel);
@@ -498,6 +516,18 @@ __device__ __forceinline__ void traceTileCompact(const SailTraceArgs& A) {
           if (mixedW) __builtin_amdgcn_s_setprio(kPrioMixed);
           else __builtin_amdgcn_s_setprio(0);
         }
+#if SAIL_ROWDEFER
+        // the deferred row's paths: candidates finish the row's test (sweep time in the phase build); one left without
+        // a winner ends here like a path that left the scene -- its radiance is final in LDS, and no AOV is due past
+        // the first bounce. The record and shading below see the resolved winner.
+        if (deferB) {  // uniform
+          PHASE_MARK(pc, 1);
+          if (keyG == 1 + kDeferRow) sphereResolve(c, ray, sw);
+          if (sw.best >= kMaxDistance) alive = false;
+          PHASE_MARK(pc, 0);
+        }
+#endif
+        if (alive) {  // still: a deferred candidate may have ended just above (without a deferred row, always)
         c.fcx = (float)homeX(pixel) + 0.5f;
         c.fcy = (float)homeY(pixel) + 0.5f;
         const float seed = pathSeed(pixel) + (float)depth;
@@ -531,6 +561,7 @@ __device__ __forceinline__ void traceTileCompact(const SailTraceArgs& A) {
         SAIL_BOUNCE_REST(ins, false)
 #endif
 #undef SAIL_BOUNCE_REST
+        }
       }
       if constexpr (kShCompact) {
         if (c.ln > 0) {  // uniform

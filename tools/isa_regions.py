@@ -23,7 +23,7 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-
          "--offload-arch=gfx950", "--cuda-device-only", "-gline-tables-only"]
 
 # part of the bounce <- the first inlined function under traceTileCompact (then refined by the one under it)
-PARTS = [("sweepRay", "sweep"), ("closestT", "light + shadow"), ("hitRecord", "hit record"), ("quadLocalHit", "hit record"),
+PARTS = [("sweepRay", "sweep"), ("sphereResolve", "sweep: the deferred row's tail, after the gather"),("closestT", "light + shadow"), ("hitRecord", "hit record"), ("quadLocalHit", "hit record"),
          ("rectLocalHit", "hit record"), ("shadeLast", "last bounce (shadeLast)"), ("accumulateSample", "sample end"),
          ("stageSample", "sample end"), ("keyRank", "sort"), ("waveScanIncl", "sort"), ("atomicAdd", "sort"),
          ("__shfl", "sort")]
@@ -106,7 +106,7 @@ def part(names, line):
             return "hit record"
         # else: the hit record in front of it
     if not names:
-        return "kernel body (sort, gather, sample loop)" if 237 <= line <= 408 else "kernel body (setup, sample end)"  # sail_trace.hip lines
+        return "kernel body (sort, gather, sample loop)" if 237 <= line <= 426 else "kernel body (setup, sample end)"  # sail_trace.hip lines
     top = names[0]
     if top.startswith(("mkRay", "operator+", "operator-", "operator*", "operator/")):
         return "primary ray (sample start)"
