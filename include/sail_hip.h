@@ -731,6 +731,55 @@ int sail_jit_spec_key(const float* objects, int n, const float* texparams, int t
 /* 1 when a context that rendered `settled` samples since its rows last changed asks for its value kernel under
  * SAIL_DEBUG_JIT_VALUES_AFTER = after (0: at once, < 0: never), else 0 */
 int sail_plan_settle(uint64_t settled, int after);
+/* Host only (no device): the shape of one trace launch, as a context with these facts derives it -- which precompiled
+ * kernel set the scene falls in, which run-time kernel runs, how the launch's samples are split into staged sample groups,
+ * and the grid. Frames are bit-identical whatever the split, so this is where that policy is stated and tested
+ * (tests/test_launch_plan.py). The entry derives the run-time kernel's spec itself from the scene, the switches and the
+ * share; `tier` only says which tier a context has loaded. Returns -1 with a message (sail_last_error(NULL)) for bad
+ * facts, among them a tier the scene does not get under these switches. */
+enum sail_launch_tier {
+  SAIL_LAUNCH_TIER_NONE = 0,  /* no run-time kernel is loaded: the precompiled kernel of the scene's set runs */
+  SAIL_LAUNCH_TIER_TYPES = 1, /* the scene's run-time kernel */
+  SAIL_LAUNCH_TIER_VALUE = 2  /* the value kernel on top of it (SAIL_DEBUG_JIT_VALUES_AFTER) */
+};
+typedef struct sail_launch_facts {
+  /* the scene, as sail_set_scene takes it (ln light rows; the rows themselves are not read) */
+  const float* objects;
+  const float* texparams;
+  const sail_plugins* plugins;
+  int n, tn, ln;
+  /* the switches: bit o of debug_set says sail_set_debug(ctx, o, debug[o]) was called, every other option is at its
+   * default. Only the options that decide a kernel or a launch shape are taken (not SAIL_DEBUG_CULL_FMA, FORCE_RCCL,
+   * JIT_WAIT). launch_spp: sail_set_launch_samples (0: by form). */
+  uint32_t debug_set;
+  int debug[16];
+  int launch_spp;
+  /* the share of the frame and the device (sail_set_partition; compute_units as sail_device_info reports them) */
+  int width, height, rank, world, part_mode, compute_units;
+  /* the launch: its samples; the tiles a tile mask leaves active of this rank's share, or -1 without a mask; whether the
+   * fused pre-cull form is safe and whether primary rays may use the pre-cull for this eye (both decided from the eye
+   * and the scene's extent by the context); the tier that is loaded */
+  int nspp, active_tiles, cull_fma_ok, eye_near_scene, tier;
+} sail_launch_facts;
+typedef struct sail_launch_plan {
+  int kernel_set;     /* 0 every plugin, 1 the Cornell box's set, 2 the rooms' */
+  int cull_prims;     /* 0 flat path, 1 the plain pre-cull form, 2 the fused one */
+  int cull_primary;   /* primary rays use the pre-cull */
+  int wavefront;      /* the launch goes by the wavefront split (SAIL_DEBUG_WAVEFRONT on a pre-cull scene) */
+  int jit_mode;       /* sail_jit_mode of the run-time kernel that runs, -1: a precompiled kernel or the wavefront split */
+  int ns;             /* samples of each pixel in flight per workgroup */
+  int sample_groups;  /* workgroups per block that share the launch's samples */
+  int group_spp;      /* samples per group (the last group takes the rest) */
+  int group_home;     /* 1: group 0 adds its samples to the accumulator itself */
+  int staged;         /* 1: the groups' samples go through the stage, and sail_accum_kernel follows */
+  /* a run-time kernel: grid workgroups of `threads`; a precompiled kernel: grid counts 256-thread blocks, launched as
+   * grid * 256 / threads workgroups of `threads`; the wavefront split: every one of its passes */
+  uint32_t grid, threads;
+  int kernel_lights;  /* the kernel has a light plugin compiled in (sail_plan_last_bounce's kernel_lights) */
+  int launch_samples; /* the samples a context with these switches puts into one launch while it holds the scene's
+                       * run-time kernel (built or still building): nspp never exceeds it */
+} sail_launch_plan;
+int sail_plan_launch(const sail_launch_facts* facts, sail_launch_plan* plan);
 /* What the process keeps of value kernels: *code_objects in host memory, *modules loaded on devices. A value kernel is
  * one per pose of a scene at rest, so both are released when the last context that holds one drops it (a change of its
  * rows, another scene, sail_destroy): they are bounded by the live contexts, not by the poses seen. The objects stay in

@@ -14,7 +14,8 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SAIL_HIP_LIB: another build of the same library (a study variant, tools/study_build.sh), for the profiling tools
-LIB_PATH = os.environ.get("SAIL_HIP_LIB") or os.path.join(_HERE, "lib", "libsail_hip.so")
+_PRODUCT_LIB = os.path.join(_HERE, "lib", "libsail_hip.so")
+LIB_PATH = os.environ.get("SAIL_HIP_LIB") or _PRODUCT_LIB
 
 SAIL_OK = 0
 FLAG_AOV = 1
@@ -50,7 +51,7 @@ EXPORTS = (
     "sail_abi_version", "sail_accum_parts", "sail_save_accum", "sail_load_accum", "sail_jit_compile",
     "sail_get_kernel_info", "sail_kernel_ready", "sail_set_jit_cache", "sail_jit_prebuild",
     "sail_jit_value_key", "sail_jit_spec_key", "sail_plan_settle", "sail_jit_resident",
-    "sail_plan_reduce", "sail_plan_keep", "sail_plan_load_part", "sail_plan_last_bounce",
+    "sail_plan_reduce", "sail_plan_keep", "sail_plan_load_part", "sail_plan_last_bounce", "sail_plan_launch",
     "sail_noise_mark", "sail_noise_estimate", "sail_plan_until", "sail_render_until",
     "sail_set_active_tiles", "sail_get_active_tiles", "sail_plan_adaptive", "sail_adaptive_defaults", "sail_render_adaptive",
     "sail_denoise_defaults", "sail_denoise",
@@ -87,6 +88,27 @@ class KernelInfo(ctypes.Structure):
 class ReducePlan(ctypes.Structure):
     _fields_ = [("receives", ctypes.c_int), ("tiles", ctypes.c_int), ("aov_owner", ctypes.c_int),
                 ("send_own_aovs", ctypes.c_int), ("samples", ctypes.c_uint64)]
+
+
+LAUNCH_TIER_NONE, LAUNCH_TIER_TYPES, LAUNCH_TIER_VALUE = 0, 1, 2  # sail_plan_launch: the tier a context has loaded
+
+
+class LaunchFacts(ctypes.Structure):
+    _fields_ = [("objects", ctypes.POINTER(ctypes.c_float)), ("texparams", ctypes.POINTER(ctypes.c_float)),
+                ("plugins", ctypes.POINTER(Plugins)), ("n", ctypes.c_int), ("tn", ctypes.c_int), ("ln", ctypes.c_int),
+                ("debug_set", ctypes.c_uint32), ("debug", ctypes.c_int * 16), ("launch_spp", ctypes.c_int),
+                ("width", ctypes.c_int), ("height", ctypes.c_int), ("rank", ctypes.c_int), ("world", ctypes.c_int),
+                ("part_mode", ctypes.c_int), ("compute_units", ctypes.c_int),
+                ("nspp", ctypes.c_int), ("active_tiles", ctypes.c_int), ("cull_fma_ok", ctypes.c_int),
+                ("eye_near_scene", ctypes.c_int), ("tier", ctypes.c_int)]
+
+
+class LaunchPlan(ctypes.Structure):
+    _fields_ = [("kernel_set", ctypes.c_int), ("cull_prims", ctypes.c_int), ("cull_primary", ctypes.c_int),
+                ("wavefront", ctypes.c_int), ("jit_mode", ctypes.c_int), ("ns", ctypes.c_int),
+                ("sample_groups", ctypes.c_int), ("group_spp", ctypes.c_int), ("group_home", ctypes.c_int),
+                ("staged", ctypes.c_int), ("grid", ctypes.c_uint32), ("threads", ctypes.c_uint32),
+                ("kernel_lights", ctypes.c_int), ("launch_samples", ctypes.c_int)]
 
 
 class NoiseInfo(ctypes.Structure):
@@ -242,6 +264,7 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
                                              ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64), ctypes.c_char_p,
                                              ctypes.POINTER(ctypes.c_size_t)]),
         "sail_plan_settle": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_int]),
+        "sail_plan_launch": (ctypes.c_int, [ctypes.POINTER(LaunchFacts), ctypes.POINTER(LaunchPlan)]),
         "sail_jit_resident": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
         "sail_plan_reduce": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                             ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ReducePlan)]),
@@ -290,7 +313,11 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
                                                        ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(TfilterInfo)]),
     }
     for name, (res, args) in sig.items():
-        fn = getattr(lib, name)
+        # another build (a path, or SAIL_HIP_LIB: tools/rev_build.sh builds older revisions as A/B controls) may predate
+        # an entry point; the product's own library must have them all
+        fn = getattr(lib, name) if p == _PRODUCT_LIB else getattr(lib, name, None)
+        if fn is None:
+            continue
         fn.restype = res
         fn.argtypes = args
     if path is None:
@@ -628,6 +655,31 @@ def plan_settle(settled: int, after: int) -> bool:
     """Whether a context that rendered `settled` samples since its rows last changed asks for its value kernel under
     DEBUG_JIT_VALUES_AFTER = after"""
     return bool(load().sail_plan_settle(int(settled), int(after)))
+
+
+def plan_launch(sc: dict, width: int, height: int, nspp: int, tier: int = LAUNCH_TIER_NONE, debug: Optional[dict] = None,
+                launch_spp: int = 0, rank: int = 0, world: int = 1, part_mode: int = PART_TILES, compute_units: int = 256,
+                active_tiles: int = -1, cull_fma_ok: bool = True, eye_near_scene: bool = True) -> dict:
+    """Host-only (sail_plan_launch): the shape of one trace launch of `nspp` samples of scene `sc`, as a context with
+    these facts derives it. debug: {DEBUG_* option: value} as given to a Context; tier: which run-time kernel the context
+    has loaded (LAUNCH_TIER_*); active_tiles: the tiles a tile mask leaves of the rank's share (-1: no mask)."""
+    lib = load()
+    o, t = _f32(sc["objects"]), _f32(sc["texparams"])
+    pl = Plugins(*[int(m) for m in plugin_masks(sc["plugins"])])
+    f = LaunchFacts(objects=_ptr(o), texparams=_ptr(t), plugins=ctypes.pointer(pl), n=sc["n"], tn=sc["tn"], ln=sc["ln"],
+                    launch_spp=launch_spp, width=width, height=height, rank=rank, world=world, part_mode=part_mode,
+                    compute_units=compute_units, nspp=nspp, active_tiles=active_tiles, cull_fma_ok=int(bool(cull_fma_ok)),
+                    eye_near_scene=int(bool(eye_near_scene)), tier=tier)
+    for opt, val in (debug or {}).items():
+        if not 0 <= int(opt) < 16:
+            raise SailError(f"sail_plan_launch: no debug option {opt}")
+        f.debug_set |= 1 << int(opt)
+        f.debug[int(opt)] = int(val)
+    out = LaunchPlan()
+    rc = lib.sail_plan_launch(ctypes.byref(f), ctypes.byref(out))
+    if rc:
+        raise SailError(f"sail_plan_launch: {rc}: {lib.sail_last_error(None).decode()}")
+    return {name: int(getattr(out, name)) for name, _ in LaunchPlan._fields_}
 
 
 def comm_unique_id() -> bytes:

@@ -1,7 +1,7 @@
-// sail_capi.cpp — libsail_hip.so: the context's life cycle, scene decode and upload, the run-time-kernel policy and the
-// trace launch, readback, display filter, picking. What it shares with the other host files (sail_multi.cpp: RCCL and
-// multi-device reduce, checkpoints; sail_converge.cpp: noise estimate, render-until, tile mask; sail_post.cpp: denoiser,
-// reprojection, temporal filter, albedo map) is in sail_ctx.h.
+// sail_capi.cpp — libsail_hip.so: the context's life cycle, scene decode and upload, the run-time kernels' slots and the
+// trace launch (which kernel and what shape: sail_plan.cpp), readback, display filter, picking. What it shares with the
+// other host files (sail_multi.cpp: RCCL and multi-device reduce, checkpoints; sail_converge.cpp: noise estimate,
+// render-until, tile mask; sail_post.cpp: denoiser, reprojection, temporal filter, albedo map) is in sail_ctx.h.
 // The C ABI is declared (with the reference interface each entry replaces) in include/sail_hip.h.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -67,108 +67,6 @@ int fail(sail_ctx* c, int code, const char* fmt, ...) {
 
 namespace {
 
-// the smallest precompiled plugin-set kernel that covers the scene (sail_device.h SAIL_KSET_*)
-int kernelSetFor(const sail_ctx* c) {
-  if (c->forceGeneric || c->n >= c->cullMinPrims) return SAIL_KSET_GENERIC;
-  const sail_plugins& p = c->plugins;
-  const bool lightsOk = c->ln == 0 || (p.light_mask & ~SAIL_KSET_CORNELL_LIGHTS) == 0;
-  if ((p.shape_mask & ~SAIL_KSET_CORNELL_SHAPES) == 0 && (p.material_mask & ~SAIL_KSET_CORNELL_MATS) == 0 &&
-      (p.texture_mask & ~SAIL_KSET_CORNELL_TEX) == 0 && lightsOk && SAIL_KSET_CORNELL_LIGHTS == 0 && c->ln == 0)
-    return SAIL_KSET_CORNELL;
-  if ((p.shape_mask & ~SAIL_KSET_ROOM_SHAPES) == 0) return SAIL_KSET_ROOM;
-  return SAIL_KSET_GENERIC;
-}
-
-// the sample-group stage's cap (12 B per owned pixel per staged sample): 8 GiB
-constexpr size_t kStageCapBytes = (size_t)8 << 30;
-// Launch bounds of a run-time kernel by form and by the precompiled family its plugin set falls in: the precompiled
-// kernels' own (6 waves all-plugin, 8 Cornell, 7 room, 8 pre-cull), except that a flat scene outside the Cornell and room
-// sets compiled in the room form runs at 8 waves (its smaller kernel spills less: ALL +3.6 %, AREA +3.8 % over 7,
-// profiles/r04_jit_occupancy.jsonl).
-int jitWaves(int mode, int kernelSet) {
-  if (mode == SAIL_JIT_MODE_CULL) return 8;
-  if (mode == SAIL_JIT_MODE_ROOM) return kernelSet == SAIL_KSET_ROOM ? 7 : 8;
-  return kernelSet == SAIL_KSET_CORNELL ? 8 : 6;
-}
-// the tiles of this rank's share of the partition
-int partitionTiles(const sail_ctx* c, int* tilesX, int* tilesY) {
-  const int tx = (c->W + 63) / 64, ty = (c->H + 63) / 64;
-  *tilesX = tx; *tilesY = ty;
-  if (c->partMode == SAIL_PART_SAMPLES) return tx * ty;
-  const int total = tx * ty;
-  return c->rank < total ? (total - c->rank + c->world - 1) / c->world : 0;
-}
-// Workgroup shape of a run-time kernel by form (profiles/r05_ns_*.jsonl, r05_nt*_C1.jsonl; 1080p / 4K, 64-sample
-// launches, bit-identical): the Cornell form at 512 threads holding 16 samples of 32 pixels (C1 98.6 Gseg/s against 97.5-98.1
-// at 256 threads x 1 sample with 8 staged sample groups: no stage and no sail_accum_kernel at full frame; 512 x 1 sample,
-// staged, 98.8-99.0); the room and pre-cull forms at their 256 / 1,024 threads holding 4 samples (C3 +1.2 %, C4 +0.8 %;
-// 16 samples C3 -0.4 %, C4 -1.3 %; C3 at 128 / 512 threads -9 % / -4 %, C4 at 512 -62 %: its LDS tables then
-// leave room for too few workgroups).
-// The Cornell form's 16 samples in flight pay while the context's share of the frame queues enough workgroups: with a
-// small share (a rank of 8 or more, one eighth of 1080p) it holds 1 sample and the launch is split into staged sample
-// groups instead (C2 per GPU at N = 8: 95.4 Gseg/s against 92.1 with 16 samples and no groups, 91.4 with both; at
-// N = 4 95.2 against 94.9; profiles/r05_scale_ns_c2.jsonl, tools/scale_groups.sh).
-// (the share is the partition's, whatever tile mask is set: a mask must not swap the scene's kernel for another build)
-bool cornellShareLarge(const sail_ctx* c) {
-  int tx, ty;
-  const int owned = partitionTiles(c, &tx, &ty);
-  // residency rounds of 512-thread workgroups at 8 waves per SIMD (4,096 / 32 pixels = 128 workgroups per tile)
-  const double rounds = (double)owned * 128.0 / ((double)c->numCUs * 4.0);
-  return rounds >= 12.0;
-}
-int jitNsFor(const sail_ctx* c, int mode, int kernelSet) {
-  if (mode == SAIL_JIT_MODE_FLAT && kernelSet == SAIL_KSET_CORNELL) return cornellShareLarge(c) ? 16 : 1;
-  if (mode == SAIL_JIT_MODE_ROOM || mode == SAIL_JIT_MODE_CULL) return 4;
-  return 1;
-}
-int jitNtFor(int mode, int kernelSet) {
-  return (mode == SAIL_JIT_MODE_FLAT && kernelSet == SAIL_KSET_CORNELL) ? 512 : 0;
-}
-// The run-time kernel spec of the context's scene under its switches, or false when none applies.
-// SAIL_DEBUG_JIT bits (include/sail_hip.h): 1 flat scenes outside the Cornell and room sets, 2 pre-cull scenes, 4 room-set
-// scenes, 8 the flat scenes of bit 1 in the room form, 16 flat scenes compiled for their rows as well (any flat scene),
-// 32 the row-shading form of the value kernel (valueSpecFor), 64 the value kernel without its deferred Sphere row.
-bool jitSpecFor(const sail_ctx* c, SailJitSpec* out, int* mode) {
-  if (!c->jit || !c->haveScene || c->forceGeneric) return false;
-  const int set = kernelSetFor(c);
-  const bool rows = (c->jit & 16) && c->n >= 1 && c->n <= kSailJitMaxRows && c->n < c->cullMinPrims &&
-                    (int)c->primTypes.size() == c->n;
-  int m;
-  if (set == SAIL_KSET_GENERIC && c->n >= c->cullMinPrims) {
-    if (!(c->jit & 2)) return false;
-    m = SAIL_JIT_MODE_CULL;
-  } else if (set == SAIL_KSET_GENERIC) {
-    if (!(c->jit & 1) && !rows) return false;
-    m = (c->jit & 8) ? SAIL_JIT_MODE_ROOM : SAIL_JIT_MODE_FLAT;
-  } else if (set == SAIL_KSET_ROOM) {
-    if (!(c->jit & 4) && !rows) return false;
-    m = SAIL_JIT_MODE_ROOM;
-  } else {
-    if (!rows) return false;  // the Cornell kernel's set is the Cornell box's own
-    m = SAIL_JIT_MODE_FLAT;
-  }
-  const sail_plugins& p = c->plugins;
-  SailJitSpec spec;
-  spec.ks = p.shape_mask; spec.km = p.material_mask; spec.kt = p.texture_mask; spec.kl = p.light_mask;
-  spec.mode = m;
-  spec.waves = jitWaves(m, set);
-  spec.ldsFit = (m == SAIL_JIT_MODE_CULL && c->n <= SAIL_CULL_LDS_ROWS && c->tn <= SAIL_CULL_LDS_TP) ? 1 : 0;
-  spec.ns = c->jitNs ? c->jitNs : jitNsFor(c, m, set);
-  spec.nt = c->jitNt ? c->jitNt : jitNtFor(m, set);
-  if (sailJitThreads(spec) / spec.ns < 16) spec.ns = 4;  // at least 16 pixels per workgroup
-  if (rows && m != SAIL_JIT_MODE_CULL) {
-    spec.rows = c->n;
-    for (int i = 0; i < c->n; i++) spec.types[i] = c->primTypes[i];
-    for (int i = 0; i < c->n; i++)
-      if (spec.types[i] < 1 || !((spec.ks >> spec.types[i]) & 1u)) spec.rows = 0;  // a row no compiled shape hits
-    if (!spec.rows) for (int& t : spec.types) t = 0;
-    // the room form copies both tables into LDS (C3 +2.8 %, UI +2.2 %; the Cornell form measured -0.5 %)
-    if (spec.rows && m == SAIL_JIT_MODE_ROOM && c->tn >= 1 && c->tn <= kSailJitMaxFlatTp) spec.tn = c->tn;
-  }
-  *out = spec;
-  *mode = m;
-  return true;
-}
 // The rows changed, or the spec their value kernel was derived from: the hold on the value spec goes (a queued build of it
 // is skipped, a finished one stays in the caches for a scene that returns to this pose), its masked twin's first, launches
 // run the types kernel again, and the settle count restarts.
@@ -177,115 +75,13 @@ void dropValues(sail_ctx* c) {
   c->valueSlot.drop(c->device, c->stream);
   c->settled = 0;
 }
-// Whether the value kernel of a scene that rendered `settled` samples since its rows changed is asked for now
-// (sail_plan_settle; after: SAIL_DEBUG_JIT_VALUES_AFTER)
-bool settledFor(uint64_t settled, int after) { return after >= 0 && settled >= (uint64_t)after; }
-// What a path's last bounce can add at a hit on each row (SailTraceArgs.lastQuietRows / lastSkipSort), decided with
-// the kernel's own tests and f32 operations on the values it reads (sail_shade.h shadeLast: emission, matCat,
-// matRow -> kd, sigma, the Cornellbox wall constants or the uniform texture's colour). `lights`: the kernel that will
-// run has a light plugin compiled in (shadeLast then declines every lit matte hit).
-//   quiet: the emission words are +0.0f bit for bit (the facing test can only zero them again), and the row is not a
-//     matte, or it is one whose light term is fma(f, 0, 0) with f = (kd * sc) * (1 / pi) finite for every colour sc the
-//     record can give it: +0. Its update is e + (+0) * throughput whatever the record says.
-//   record-only: shadeLast accepts every hit on the row, but the value depends on the record (an emitter's facing test,
-//     a non-finite f).
-//   full: shadeLast can decline (a light plugin, Oren-Nayar), or the matte's colour is not a per-scene constant.
-// Rows of more than 32-row scenes are not classified (the pre-cull kernels take none of this); a row no ray can hit
-// (type 0) has no class. skipSort: no full row, and every record-only row emits (a black one is a matte whose light
-// term is not +0: those keep the sort). Anything this cannot decide is full.
-void lastBounceRows(const std::vector<SailPrim>& prims, const float* tp, int tn, uint32_t matMask, bool lights,
-                    uint32_t* quietRows, int* skipSort) {
-  *quietRows = 0;
-  *skipSort = 0;
-  const int n = (int)prims.size();
-  if (n < 1 || n > 32 || tn < 1 || !tp) return;
-  constexpr float kEps = 1e-5f, kInvPI = 0.3183098861837907f;  // sail_geom.h
-  bool skip = true, any = false;
-  for (int i = 0; i < n; i++) {
-    const SailPrim& p = prims[(size_t)i];
-    if (p.type == 0) continue;
-    any = true;
-    uint32_t eb[3];
-    memcpy(eb, p.em, sizeof eb);
-    const bool emPosZero = (eb[0] | eb[1] | eb[2]) == 0u;
-    const bool emBlack = p.em[0] == 0.0f && p.em[1] == 0.0f && p.em[2] == 0.0f;  // isBlack: -0 too, never NaN
-    const bool matte = (int)(short)(p.cats & 0xffff) == SAIL_MATTE;
-    bool matteOk = true;  // a lit matte hit on the row adds exactly +0
-    if (matte) {
-      const bool rowsOk = p.matRow >= 0 && p.matRow < tn && p.texRow >= 0 && p.texRow < tn;
-      if (lights || !rowsOk) {
-        matteOk = false;
-      } else if ((matMask >> SAIL_MATTE) & 1u) {  // material()'s matte branch; without the plugin f stays +0
-        const float kd = tp[(size_t)p.matRow * 16 + 1], sigma = tp[(size_t)p.matRow * 16 + 2];
-        float sc[4][3] = {{0.25f, 0.75f, 0.25f}, {0.25f, 0.25f, 0.75f}, {1.0f, 1.0f, 1.0f}, {0.0f, 0.0f, 0.0f}};
-        int ncol = 0;
-        if (p.type == SAIL_CORNELLBOX) {
-          ncol = 4;
-        } else if ((p.cats >> 16) == SAIL_TEX_UNIFORM) {
-          for (int k = 0; k < 3; k++) sc[0][k] = tp[(size_t)p.texRow * 16 + 1 + k];
-          ncol = 1;
-        }
-        matteOk = sigma < kEps && ncol > 0;
-        for (int q = 0; q < ncol; q++)
-          for (int k = 0; k < 3; k++) {
-            volatile float f = kd * sc[q][k];  // two roundings, as the kernel's (kd * sc) * kInvPI
-            f = f * kInvPI;
-            if (!std::isfinite((float)f)) matteOk = false;
-          }
-      }
-    }
-    if (emPosZero && matteOk) *quietRows |= 1u << i;
-    else if (!(matteOk && !emBlack)) skip = false;
-  }
-  *skipSort = (any && skip) ? 1 : 0;
-}
-// The value spec of a types spec: the flat form compiled for rows, with a texParams table small enough to compile in.
-// Scenes of the Cornell plugin set only (cubes, spheres, the box; matte and mirror; no textures, no lights): the form
-// that was measured and that the parity tests run with constant rows. A flat-form kernel of a wider set (SAIL_DEBUG_JIT
-// without bit 8) would read its light sampler's geometry rows, textures and a full texParams table through the constant
-// tables too, which no test covers: it keeps its types kernel.
-// jit: the SAIL_DEBUG_JIT switches; bit 32 gives scenes of at most kSailJitRowRecordMax rows the row-shading form
-// (SAIL_JIT_ROWSHADE in sail_geom.h); bit 64 (inverted: the default leaves it clear) takes the deferred Sphere row away.
-bool valueSpecFor(const SailJitSpec& types, const std::vector<uint32_t>& rowWords, const float* tp, int tn, int jit, SailJitSpec* out) {
-  const bool cornellSet = (types.ks & ~SAIL_KSET_CORNELL_SHAPES) == 0 && (types.km & ~SAIL_KSET_CORNELL_MATS) == 0 &&
-                          (types.kt & ~SAIL_KSET_CORNELL_TEX) == 0 && types.kl == 0;
-  if (!cornellSet || types.mode != SAIL_JIT_MODE_FLAT || types.rows <= 0 || types.tn != 0 || tn < 0 || tn > kSailJitMaxFlatTp ||
-      rowWords.size() != (size_t)types.rows * 32 || (tn > 0 && !tp))
-    return false;
-  *out = types;
-  out->rowWords = rowWords;
-  out->tpWords.resize((size_t)tn * 16);
-  if (tn > 0) memcpy(out->tpWords.data(), tp, sizeof(float) * 16 * (size_t)tn);
-  out->rowForm = out->rowShade = out->rowQuiet = 0;
-  if ((jit & 32) && types.rows <= kSailJitRowRecordMax) {
-    out->rowForm = 1;
-    // The rows that get a shading copy of their own: the quiet ones (lastBounceRows, for a kernel without a light plugin:
-    // cornellSet), whose copies also leave the radiance alone. Measured on C2: a copy
-    // for every row lost 4.8 % (VGPR spills 22 -> 50), copies for the quiet rows gained 4.5 %, and 6.7 % without the
-    // radiance round trip; a copy for the emitting row on top of those gained less (3.9 %).
-    std::vector<SailPrim> prims((size_t)types.rows);
-    memcpy(prims.data(), rowWords.data(), sizeof(SailPrim) * prims.size());
-    uint32_t quiet = 0;
-    int skip = 0;
-    lastBounceRows(prims, tp, tn, types.km, false, &quiet, &skip);
-    out->rowShade = (int)(quiet & ((1u << types.rows) - 1u));
-    out->rowQuiet = out->rowShade;
-  }
-  // The scene's first Sphere row is deferred (its root solve runs after the path sort, SAIL_JIT_ROWDEFER in sail_geom.h),
-  // whatever the row-shading switch and the row count; bit 64 asks for the kernel without it.
-  out->rowDefer = -1;
-  if (!(jit & 64))
-    for (int i = types.rows - 1; i >= 0; i--)
-      if (types.types[i] == SAIL_SPHERE) out->rowDefer = i;
-  return true;
-}
 // Ask for the scene's value kernel once it has settled (after every refreshJit, and between and after launches): the build
 // starts in the background, or the object loads here when a disk cache has it, as refreshJit does for the types kernel.
 // When it fails the types kernel serves.
 void refreshValues(sail_ctx* c) {
-  if (!c->subs.empty() || c->valueSlot.have || !c->typesSlot.have || !settledFor(c->settled, c->jitValuesAfter)) return;
+  if (!c->subs.empty() || c->valueSlot.have || !c->typesSlot.have || !settledFor(c->settled, c->sw.jitValuesAfter)) return;
   SailJitSpec spec;
-  if (!valueSpecFor(c->typesSlot.spec, c->rowWords, c->tpRows.data(), c->tn, c->jit, &spec)) return;
+  if (!valueSpecFor(c->typesSlot.spec, c->rowWords, c->tpRows.data(), c->facts.tn, c->sw.jit, &spec)) return;
   c->valueSlot.adopt(c->device, c->stream, spec);
 }
 // Re-derive the scene's run-time kernel after anything it depends on changed (scene, rows, switches). A new spec starts
@@ -296,7 +92,7 @@ void refreshJit(sail_ctx* c) {
   if (!c->subs.empty()) return;
   SailJitSpec spec;
   int mode = 0;
-  const bool have = jitSpecFor(c, &spec, &mode);
+  const bool have = c->haveScene && jitSpecFor(c->facts, c->sw, c->share, &spec, &mode);
   if (have == c->typesSlot.have && (!have || sailJitSpecEqual(spec, c->typesSlot.spec))) return;
   dropValues(c);  // the value kernel is the old spec's
   c->typesTwin.drop(c->device, c->stream);  // and so is the types kernel's masked twin
@@ -326,31 +122,27 @@ JitSlot* runningSlot(sail_ctx* c, bool masked, bool wavefront) {
   if (c->typesSlot.poll(c->device, c->jitWait)) return masked ? maskedTwin(c, c->typesTwin, c->typesSlot) : &c->typesSlot;
   return nullptr;
 }
-// Samples per launch when the host has not fixed them: the Cornell form holding 16 samples in flight runs a whole
-// 1,024-sample frame in one launch (its waves live 16 times longer, so their per-wave start -- the spill stores of the
-// loop-invariant registers among it -- is paid 16 times less often: C1 Gseg/s at 64 / 128 / 256 / 1,024 samples per
-// launch 97.26 / 97.73 / 97.99 / 98.36, profiles/r05_launch_*.jsonl); everything else 64 (sample groups stage a launch's
-// samples, which a larger launch would push past the stage's cap).
-int launchSamples(const sail_ctx* c) {
-  if (c->launchSpp > 0) return c->launchSpp;
+// the spec launchSamples goes by: the scene's run-time kernel while one is held whose build has not failed
+const SailJitSpec* heldTypes(const sail_ctx* c) {
   const JitSlot& t = c->typesSlot;
-  return (t.have && t.state != SAIL_KERNEL_JIT_FAILED && t.spec.ns >= 16) ? 1024 : 64;
+  return (t.have && t.state != SAIL_KERNEL_JIT_FAILED) ? &t.spec : nullptr;
 }
 // the tiles a launch traces, and their in-frame pixels: the share, or with a tile mask its active tiles (tileMap)
 int ownedTiles(const sail_ctx* c, int* tilesX, int* tilesY) {
-  const int part = partitionTiles(c, tilesX, tilesY);
+  const int part = partitionTiles(c->share, tilesX, tilesY);
   return c->maskSet ? c->maskTiles : part;
 }
 long long ownedPixels(const sail_ctx* c) {
   if (c->maskSet) return c->maskPixels;
   int tx, ty;
-  const int owned = partitionTiles(c, &tx, &ty);
+  const ShareFacts& sh = c->share;
+  const int owned = partitionTiles(sh, &tx, &ty);
   long long px = 0;
-  const int w = (c->partMode == SAIL_PART_SAMPLES) ? 1 : c->world, r = (c->partMode == SAIL_PART_SAMPLES) ? 0 : c->rank;
+  const int w = (sh.partMode == SAIL_PART_SAMPLES) ? 1 : sh.world, r = (sh.partMode == SAIL_PART_SAMPLES) ? 0 : sh.rank;
   for (int j = 0; j < owned; j++) {
     const int t = r + j * w;
     const int x0 = (t % tx) * 64, y0 = (t / tx) * 64;
-    const int cw = (c->W - x0) < 64 ? (c->W - x0) : 64, ch = (c->H - y0) < 64 ? (c->H - y0) : 64;
+    const int cw = (sh.W - x0) < 64 ? (sh.W - x0) : 64, ch = (sh.H - y0) < 64 ? (sh.H - y0) : 64;
     px += (long long)cw * ch;
   }
   return px;
@@ -397,12 +189,12 @@ int resetAccum(sail_ctx* c) {
   c->mask.clear();
   c->frozenAt.clear();
   c->tpResolved = false;  // Out no longer belongs to this accumulator: sail_temporal_filter wants a resolve of the new one
-  const size_t bytes = (size_t)c->W * c->H * sizeof(float4);
+  const size_t bytes = (size_t)c->share.W * c->share.H * sizeof(float4);
   HIPCHK(c, hipMemsetAsync(c->accum, 0, bytes, c->stream));
   if (c->aovN) HIPCHK(c, hipMemsetAsync(c->aovN, 0, bytes, c->stream));
   if (c->aovP) HIPCHK(c, hipMemsetAsync(c->aovP, 0, bytes, c->stream));
-  if ((c->aovN || c->aovP) && c->partMode == SAIL_PART_TILES && c->world > 1)
-    HIPCHK(c, sail_launch_negzero_unowned(c->aovN, c->aovP, c->W, c->H, c->rank, c->world, c->stream));
+  if ((c->aovN || c->aovP) && c->share.partMode == SAIL_PART_TILES && c->share.world > 1)
+    HIPCHK(c, sail_launch_negzero_unowned(c->aovN, c->aovP, c->share.W, c->share.H, c->share.rank, c->share.world, c->stream));
   if (c->segCounter) HIPCHK(c, hipMemsetAsync(c->segCounter, 0, SAIL_SEG_SLOTS * sizeof(unsigned long long), c->stream));
   int rc = collectEvents(c);
   if (rc) return rc;
@@ -685,6 +477,34 @@ void decodePrims(const float* objects, int n, int tn, uint32_t shapeMask, std::v
   if (sbOut) *sbOut = sb;
 }
 
+// One decoded scene, as sail_set_scene uploads it and as the device-free entry points derive kernels from it: the rows
+// with their category words filled, their shape ids, their words (32 per row: what a value kernel compiles in), whether
+// a shadow ray may stop at any hit, and the scene box
+struct DecodedScene {
+  std::vector<SailPrim> prims;
+  std::vector<int> types;
+  std::vector<uint32_t> rowWords;
+  int anyHit = 1;
+  SceneBox box{};
+};
+DecodedScene decodeScene(const float* objects, int n, const float* texparams, int tn, const sail_plugins& plugins) {
+  DecodedScene d;
+  decodePrims(objects, n, tn, plugins.shape_mask, d.prims, &d.anyHit, &d.box);
+  fillCats(d.prims, texparams, tn);
+  for (const SailPrim& q : d.prims) d.types.push_back(q.type);
+  d.rowWords.resize((size_t)n * 32);
+  if (n > 0) memcpy(d.rowWords.data(), d.prims.data(), sizeof(SailPrim) * (size_t)n);
+  return d;
+}
+// the policy's facts of a decoded scene (ln: the light rows of sail_set_scene)
+SceneFacts sceneFacts(const DecodedScene& d, int tn, int ln, const sail_plugins& plugins) {
+  SceneFacts f;
+  f.plugins = plugins;
+  f.n = (int)d.prims.size(); f.tn = tn; f.ln = ln;
+  f.primTypes = d.types;
+  return f;
+}
+
 int ensureSamples(sail_ctx* c, int count) {
   if (count <= c->samplesCap) return SAIL_OK;
   c->samplesPos = 0;
@@ -718,92 +538,47 @@ int launchTrace(sail_ctx* c, const SailSample* hs, int count, int maxBounces) {
   c->samplesPos += count;
   HIPCHK(c, hipMemcpyAsync(dev, src, sizeof(SailSample) * count, hipMemcpyHostToDevice, c->stream));
   const long long px = ownedPixels(c);
-  // The stage holds 12 B per owned pixel per staged sample. It is capped (kStageCapBytes): a launch that would need
-  // more runs one workgroup per block (no stage).
-  const long long stageStride = (long long)owned * 4096;
-  const int stageSpp = (int)std::max<long long>(1, (long long)(kStageCapBytes / ((size_t)stageStride * 12)));
-  const int L = launchSamples(c);
+  const long long stageStride = (long long)owned * 4096;  // the stage's floats per staged sample and colour
+  const int L = launchSamples(c->sw, heldTypes(c));
   for (int s0 = 0; s0 < count; s0 += L) {
     const int nspp = (count - s0) < L ? (count - s0) : L;
     SailTraceArgs A;
     memset(&A, 0, sizeof A);
-    A.prims = c->prims; A.typeMasks = reinterpret_cast<const unsigned long long*>(c->prims + c->n);
+    A.prims = c->prims; A.typeMasks = reinterpret_cast<const unsigned long long*>(c->prims + c->facts.n);
     A.texparams = c->tp; A.lights = c->lt; A.lightObjRow = c->lightObjRow;
     A.samples = dev + s0;
     A.accum = c->accum; A.aovN = c->aovN; A.aovP = c->aovP; A.segCounter = c->segCounter;
-    A.W = c->W; A.H = c->H; A.n = c->n; A.tn = c->tn; A.ln = c->ln;
-    A.matMask = c->plugins.material_mask; A.texMask = c->plugins.texture_mask; A.lightMask = c->plugins.light_mask;
+    A.W = c->share.W; A.H = c->share.H; A.n = c->facts.n; A.tn = c->facts.tn; A.ln = c->facts.ln;
+    const sail_plugins& pl = c->facts.plugins;
+    A.matMask = pl.material_mask; A.texMask = pl.texture_mask; A.lightMask = pl.light_mask;
     A.maxBounces = maxBounces; A.spp = nspp; A.accumMode = c->accumMode;
     A.tilesX = tx; A.tilesY = ty;
-    A.world = (c->partMode == SAIL_PART_SAMPLES) ? 1 : c->world;
-    A.rank = (c->partMode == SAIL_PART_SAMPLES) ? 0 : c->rank;
+    A.world = (c->share.partMode == SAIL_PART_SAMPLES) ? 1 : c->share.world;
+    A.rank = (c->share.partMode == SAIL_PART_SAMPLES) ? 0 : c->share.rank;
     A.ownedTiles = owned;
     A.tileMap = c->maskSet ? c->tileMap : nullptr;
     A.shadowAnyHit = c->shadowAnyHit;
-    A.cullPrims = c->n >= c->cullMinPrims ? (cullFmaOk(c) ? 2 : 1) : 0;
-    A.cullPrimary = eyeNearScene(c);
-    A.kernelSet = kernelSetFor(c);
     memcpy(A.eye, c->eyeCache, sizeof A.eye);
-    // Sample groups: a rank's share of a small frame is too few workgroups to fill the device (1/8 of 1080p
-    // = 1,016 workgroups = 4 waves per SIMD); split the launch's samples over G workgroups per block so
-    // that about 4 rounds of 7-wave-per-SIMD residency are queued, and add the staged samples in order.
-    const bool wavefront = c->wavefront && A.kernelSet == SAIL_KSET_GENERIC && A.cullPrims;
     refreshValues(c);  // the settle count may have crossed its threshold with the launch before
-    const JitSlot* run = runningSlot(c, A.tileMap != nullptr, wavefront);
-    // samples of each pixel in flight per workgroup (the run-time kernels' spec; the precompiled kernels hold one):
-    // NS times the workgroups of one sample in flight, each NS times shorter
-    const int ns = run ? run->spec.ns : 1;
-    {  // the last bounce's row classes for the light plugins compiled into the kernel that runs (shadeLast's kLights)
-      const bool kl = run ? run->spec.kl != 0u : A.kernelSet != SAIL_KSET_CORNELL;
-      A.lastQuietRows = A.cullPrims ? 0u : c->lastQuietRows[kl];
-      A.lastSkipSort = A.cullPrims ? 0 : c->lastSkipSort[kl];
-    }
-    int G = 1;
-    if (c->forceGroups > 0) {
-      G = c->forceGroups;
-    } else if (A.kernelSet == SAIL_KSET_GENERIC && A.cullPrims) {
-      // The pre-cull kernel's workgroups are 1,024 threads, two per CU at 8 waves per SIMD. Its per-workgroup cost
-      // varies with the primitives a 16x64 strip sees, so a grid of few rounds ends in a long tail (1/8 of C4: 1,020
-      // workgroups = 2 rounds, 0.92 of the one-GPU rate per GPU): below 6 rounds, split the samples so that about 8
-      // rounds are queued (the grouped kernel is 1,024 threads too; measured 0.95 at N = 8 with 4 groups).
-      // Round 3: more groups pay at any frame size (a shorter tail per launch); C4 at N = 1: G = 1 / 2 / 4 9.96 / 10.06
-      // / 10.12 Gseg/s (gpurun_out/r03o), so about SAIL_CULL_GROUP_ROUNDS rounds are queued.
-      const double rounds = (double)owned * 4.0 * ns / (double)(c->numCUs * 2);
-      if (rounds < (double)c->cullGroupRounds) G = (int)ceil((double)c->cullGroupRounds / rounds);
-    } else {
-      // Round 3: splitting pays at full frame size too (shorter launch tails): C2 at N = 1 with G = 1 / 2 / 4 / 8 / 16
-      // 89.3 / 89.7 / 90.9 / 91.6 / 91.4 Gseg/s, C5 87.0 / 89.3 / 90.9 / 91.6 / 91.9, C3 29.2 / 28.6 / 29.2 / 29.5 / 29.4;
-      // at N = 8 (C2) G = 8 / 16 / 32 85 / 87 / 88 (gpurun_out/r03o). About 36 rounds of 7-wave residency are queued.
-      const long long waves = (long long)owned * 16 * 4 * ns;
-      const long long target = (long long)c->numCUs * 4 * 7 * c->flatGroupRounds;
-      G = (int)((target + waves - 1) / waves);
-      // the Cornell form holds 16 samples in flight only while its share queues enough workgroups (jitNsFor), and then
-      // runs unsplit: staged groups lost 2-3 % per GPU at N = 4 and 8 (profiles/r05_scale_groups_c2.jsonl)
-      // (under a tile mask that leaves too few active tiles for that, the kernel still holds its 16 samples, so the launch
-      // is split after all: rate_by_active_tiles against rate_by_active_tiles_unsplit in profiles/adaptive_1080p.json)
-      const bool fewActive = c->maskSet && (double)owned * 128.0 / ((double)c->numCUs * 4.0) < 12.0;
-      if (ns >= 16 && !fewActive) G = 1;
-    }
-    if (G > nspp) G = nspp;
-    if (G < 1) G = 1;
-    if (nspp > stageSpp) G = 1;  // the stage would pass its cap
-    A.groupSpp = (nspp + G - 1) / G;
-    // whole steps of the workgroup's samples in flight: a group of 11 samples at 4 in flight would idle a quarter of
-    // the lanes in its last step (C4 per GPU at N = 2 and 4: 12.6 Gseg/s against 13.4, profiles/r05_scale_groups_c4.jsonl)
-    if (ns > 1 && A.groupSpp < nspp && c->forceGroups <= 0) A.groupSpp = ((A.groupSpp + ns - 1) / ns) * ns;
-    A.sampleGroups = (nspp + A.groupSpp - 1) / A.groupSpp;
-    A.groupHome = (run ? run->spec.mode == SAIL_JIT_MODE_ROOM : SAIL_GROUP_HOME_FOR(A.kernelSet)) ? 1 : 0;
+    const JitSlot* run = runningSlot(c, A.tileMap != nullptr, wavefrontFor(c->facts, c->sw));
+    LaunchChunk chunk;
+    chunk.nspp = nspp; chunk.owned = owned; chunk.masked = c->maskSet;
+    chunk.cullFmaOk = cullFmaOk(c); chunk.eyeNearScene = eyeNearScene(c) != 0;
+    chunk.run = run ? &run->spec : nullptr;
+    const LaunchPlan P = planLaunch(c->facts, c->sw, c->share, chunk);
+    A.cullPrims = P.cullPrims; A.cullPrimary = P.cullPrimary; A.kernelSet = P.kernelSet;
+    A.lastQuietRows = P.cullPrims ? 0u : c->lastQuietRows[P.kernelLights];
+    A.lastSkipSort = P.cullPrims ? 0 : c->lastSkipSort[P.kernelLights];
+    A.groupSpp = P.groupSpp; A.sampleGroups = P.sampleGroups; A.groupHome = P.groupHome;
     A.stageStride = stageStride;
-    const bool staged = A.sampleGroups > 1;
-    if (staged) {  // sized for this launch's samples (it grows to the largest launch seen)
+    if (P.staged) {  // sized for this launch's samples (it grows to the largest launch seen)
       const size_t need = (size_t)A.stageStride * (size_t)nspp * 3 * sizeof(float);
       if ((rc = growBuffer(c, &c->stage, &c->stageBytes, need, need, "sample-group stage"))) return rc;
       A.stage = c->stage;
     }
     SailWfState WS;
     memset(&WS, 0, sizeof WS);
-    if (wavefront) {
-      A.sampleGroups = 1; A.groupSpp = nspp; A.stage = nullptr;
+    if (P.wavefront) {
       const size_t slots = (size_t)owned * 4096;
       if ((rc = growBuffer(c, &c->wf, &c->wfSlots, slots, slots * 11 * sizeof(float4), "wavefront state"))) return rc;
       float4* b = c->wf;
@@ -813,30 +588,27 @@ int launchTrace(sail_ctx* c, const SailSample* hs, int count, int maxBounces) {
     hipEvent_t e0, e1;
     if ((rc = getEvent(c, &e0)) || (rc = getEvent(c, &e1))) return rc;
     HIPCHK(c, hipEventRecord(e0, c->stream));
-    if (wavefront) {
+    if (P.wavefront) {
       HIPCHK(c, sail_launch_wavefront(A, WS, c->stream));
     } else {
       if (run) {
         void* args[] = {&A};
-        const unsigned nt = (unsigned)sailJitThreads(run->spec);
-        const unsigned px = nt / (unsigned)ns;                            // pixels per workgroup
-        HIPCHK(c, hipModuleLaunchKernel(A.sampleGroups > 1 ? run->k.grouped : run->k.plain,
-                                        (unsigned)owned * (4096u / px) * (unsigned)A.sampleGroups, 1, 1, nt, 1, 1, 0,
-                                        c->stream, args, nullptr));
+        HIPCHK(c, hipModuleLaunchKernel(P.staged ? run->k.grouped : run->k.plain, P.grid, 1, 1, P.threads, 1, 1, 0, c->stream,
+                                        args, nullptr));
         c->lastJit = true;
         c->lastJitMode = run->spec.mode;
         c->lastBuildId = run->k.buildId;
       } else {
-        HIPCHK(c, sail_launch_trace(A, owned * 16 * A.sampleGroups, c->stream));
+        HIPCHK(c, sail_launch_trace(A, (int)P.grid, c->stream));
         c->lastJit = false;
       }
-      if (staged) HIPCHK(c, sail_launch_accum(A, owned * 16, c->stream));
+      if (P.staged) HIPCHK(c, sail_launch_accum(A, owned * 16, c->stream));
     }
     HIPCHK(c, hipEventRecord(e1, c->stream));
     c->pending.emplace_back(e0, e1);
     c->lastGroups = A.sampleGroups;
     c->lastMasked = A.tileMap != nullptr;
-    c->lastWavefront = wavefront;
+    c->lastWavefront = P.wavefront;
     c->launches++;
     c->nominalSegments += (uint64_t)px * (uint64_t)nspp * (uint64_t)maxBounces;
     c->settled += (uint64_t)nspp;
@@ -872,10 +644,10 @@ int sail_kernel_name(sail_ctx* c, char* name, int len) {
   if (!c || !name || len <= 0) return SAIL_E_INVALID;
   if (!c->subs.empty()) return relay(c, sail_kernel_name(c->subs[0], name, len), c->subs[0]);
   if (!c->haveScene) return fail(c, SAIL_E_STATE, "sail_kernel_name: no scene");
-  const int set = kernelSetFor(c);
+  const int set = kernelSetFor(c->facts, c->sw);
   const char* k = set == SAIL_KSET_CORNELL ? "sail_trace_kernel_cornell"
                   : set == SAIL_KSET_ROOM ? "sail_trace_kernel_room"
-                  : (c->n >= c->cullMinPrims ? "sail_trace_kernel_cull" : "sail_trace_kernel");
+                  : (c->facts.n >= c->sw.cullMinPrims ? "sail_trace_kernel_cull" : "sail_trace_kernel");
   // the last launch's form: sample groups run the _grouped kernel followed by sail_accum_kernel
   if (c->lastWavefront) k = "sail_wf_*";
   else if (c->lastJit) k = c->lastJitMode == SAIL_JIT_MODE_CULL ? "sail_trace_kernel_cull_jit" : "sail_trace_kernel_jit";
@@ -957,7 +729,7 @@ int sail_create(sail_ctx** out, int width, int height, int device, uint32_t flag
   if (device < 0) { if (hipGetDevice(&device) != hipSuccess) device = 0; }
   if (device >= ndev) return fail(nullptr, SAIL_E_INVALID, "device %d out of range (%d devices)", device, ndev);
   sail_ctx* c = new sail_ctx();
-  c->device = device; c->W = width; c->H = height; c->flags = flags;
+  c->device = device; c->share.W = width; c->share.H = height; c->flags = flags;
   auto bail = [&](int code, const char* what) {
     g_create_error = std::string("sail_create: ") + what;
     sail_destroy(c);
@@ -966,7 +738,7 @@ int sail_create(sail_ctx** out, int width, int height, int device, uint32_t flag
   if (hipSetDevice(device) != hipSuccess) return bail(SAIL_E_HIP, "hipSetDevice");
   {
     int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) c->numCUs = cus;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) c->share.numCUs = cus;
   }
   if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) return bail(SAIL_E_HIP, "stream");
   const size_t bytes = (size_t)width * height * sizeof(float4);
@@ -1028,8 +800,8 @@ int sail_create_multi(sail_ctx** out, int width, int height, const int* devices,
   if (!allSame && !allDistinct)
     return fail(nullptr, SAIL_E_INVALID, "sail_create_multi: devices must be all distinct or all the same one");
   sail_ctx* g = new sail_ctx();
-  g->W = width; g->H = height; g->flags = flags; g->device = dev[0];
-  g->world = n_devices;
+  g->share.W = width; g->share.H = height; g->flags = flags; g->device = dev[0];
+  g->share.world = n_devices;
   g->groupLocal = n_devices > 1 && allSame;
   for (int i = 0; i < n_devices; i++) {
     sail_ctx* s = nullptr;
@@ -1084,43 +856,23 @@ int sail_set_debug(sail_ctx* c, int option, int value) {
   for (sail_ctx* s : c->subs) if (int rc = sail_set_debug(s, option, value)) return relay(c, rc, s);
   if (int rc = flushQueued(c)) return rc;  // queued samples launch with the settings they were queued under
   switch (option) {
-    case SAIL_DEBUG_CULL_MIN_PRIMS: c->cullMinPrims = value; break;
-    case SAIL_DEBUG_FORCE_GENERIC: c->forceGeneric = value; break;
     case SAIL_DEBUG_CULL_FMA: c->cullFma = value; break;
-    case SAIL_DEBUG_SAMPLE_GROUPS: c->forceGroups = value; break;
-    case SAIL_DEBUG_WAVEFRONT: c->wavefront = value; break;
-    case SAIL_DEBUG_JIT:
-      // the value kernel's other form, derived anew below (refreshValues); the rows did not move: the count stays
-      if ((c->jit ^ value) & (32 | 64)) { const uint64_t s = c->settled; dropValues(c); c->settled = s; }
-      c->jit = value;
-      break;
-    case SAIL_DEBUG_JIT_NT:
-      if (value != 0 && value != 128 && value != 256 && value != 512 && value != 1024)
-        return fail(c, SAIL_E_INVALID, "sail_set_debug: threads per workgroup must be 0 (default), 128, 256, 512 or 1024");
-      c->jitNt = value;
-      break;
-    case SAIL_DEBUG_JIT_NS:
-      if (value != 0 && value != 1 && value != 4 && value != 16)
-        return fail(c, SAIL_E_INVALID, "sail_set_debug: samples in flight must be 0 (default), 1, 4 or 16");
-      c->jitNs = value;
-      break;
     case SAIL_DEBUG_JIT_WAIT:
       if (value < -1) return fail(c, SAIL_E_INVALID, "sail_set_debug: jit wait must be >= -1");
       c->jitWait = value;
       break;
-    case SAIL_DEBUG_JIT_VALUES_AFTER:
-      c->jitValuesAfter = value;
-      if (value < 0) { const uint64_t s = c->settled; dropValues(c); c->settled = s; }  // never: back to the types kernel
-      break;
-    case SAIL_DEBUG_GROUP_ROUNDS:
-      if (value <= 0) return fail(c, SAIL_E_INVALID, "sail_set_debug: group rounds must be > 0");
-      c->flatGroupRounds = value;
-      break;
-    case SAIL_DEBUG_CULL_GROUP_ROUNDS:
-      if (value <= 0) return fail(c, SAIL_E_INVALID, "sail_set_debug: group rounds must be > 0");
-      c->cullGroupRounds = value;
-      break;
-    default: return fail(c, SAIL_E_INVALID, "sail_set_debug: unknown option %d", option);
+    default: {  // a switch of the policy (sail_plan.h)
+      const int jitWas = c->sw.jit;
+      if (const char* why = setSwitch(&c->sw, option, value))
+        return fail(c, SAIL_E_INVALID, "sail_set_debug: option %d: %s", option, why);
+      // the value kernel's other form, derived anew below (refreshValues), or never a value kernel: back to the types
+      // kernel; the rows did not move: the count stays
+      if (((jitWas ^ c->sw.jit) & (32 | 64)) || (option == SAIL_DEBUG_JIT_VALUES_AFTER && value < 0)) {
+        const uint64_t settled = c->settled;
+        dropValues(c);
+        c->settled = settled;
+      }
+    }
   }
   refreshJit(c);  // the switches decide which run-time kernel (if any) the scene gets
   refreshValues(c);
@@ -1133,7 +885,8 @@ static size_t primBytes(int n) {
   const size_t chunks = (size_t)(n + 63) / 64;
   return sizeof(SailPrim) * (size_t)(n > 0 ? n : 1) + chunks * 16 * sizeof(unsigned long long);
 }
-static int uploadPrims(sail_ctx* c, const std::vector<SailPrim>& prims) {
+static int uploadPrims(sail_ctx* c, const DecodedScene& d) {
+  const std::vector<SailPrim>& prims = d.prims;
   const int n = (int)prims.size();
   if (n <= 0) return SAIL_OK;
   const size_t chunks = (size_t)(n + 63) / 64;
@@ -1141,21 +894,23 @@ static int uploadPrims(sail_ctx* c, const std::vector<SailPrim>& prims) {
   for (int i = 0; i < n; i++)
     if (prims[i].type >= 0 && prims[i].type < 16) c->typeMasksHost[(size_t)(i / 64) * 16 + prims[i].type] |= 1ull << (i % 64);
   HIPCHK(c, hipMemcpyAsync(c->prims, prims.data(), sizeof(SailPrim) * n, hipMemcpyHostToDevice, c->stream));
-  c->rowWords.resize((size_t)n * 32);  // what a value kernel compiles in (refreshValues)
-  memcpy(c->rowWords.data(), prims.data(), sizeof(SailPrim) * (size_t)n);
+  c->rowWords = d.rowWords;  // what a value kernel compiles in (refreshValues)
   HIPCHK(c, hipMemcpyAsync(c->prims + n, c->typeMasksHost.data(), chunks * 16 * sizeof(unsigned long long),
                            hipMemcpyHostToDevice, c->stream));
   return SAIL_OK;
 }
 
-// Decode the rows for the context's plugin set (c->plugins) and derive what follows them: the category words, the
-// last-bounce classes for a kernel without and with a light plugin, and the scene's extent
-static void decodeRows(sail_ctx* c, const float* objects, int n, const float* texparams, int tn, std::vector<SailPrim>& prims) {
-  decodePrims(objects, n, tn, c->plugins.shape_mask, prims, &c->shadowAnyHit, &c->scene);
-  fillCats(prims, texparams, tn);
+// Decode the rows for the context's plugin set and derive what follows them: the rows' shape ids, the last-bounce classes
+// for a kernel without and with a light plugin, and the scene's extent
+static DecodedScene decodeRows(sail_ctx* c, const float* objects, int n, const float* texparams, int tn) {
+  DecodedScene d = decodeScene(objects, n, texparams, tn, c->facts.plugins);
+  c->shadowAnyHit = d.anyHit;
+  c->scene = d.box;
+  c->facts.primTypes = d.types;  // a kernel compiled for the rows follows them
   for (int l = 0; l < 2; l++)
-    lastBounceRows(prims, texparams, tn, c->plugins.material_mask, l != 0, &c->lastQuietRows[l], &c->lastSkipSort[l]);
-  c->primExtent = primExtent(prims);
+    lastBounceRows(d.prims, texparams, tn, c->facts.plugins.material_mask, l != 0, &c->lastQuietRows[l], &c->lastSkipSort[l]);
+  c->primExtent = primExtent(d.prims);
+  return d;
 }
 
 // What a context forgets when its rows change (sail_set_scene, sail_update_objects, sail_move_objects), written once.
@@ -1184,7 +939,7 @@ int sail_set_scene(sail_ctx* c, const float* objects, int n, const float* texpar
   if (!c->subs.empty()) {
     for (sail_ctx* s : c->subs)
       if (int rc = sail_set_scene(s, objects, n, texparams, tn, lights, ln, plugins)) return relay(c, rc, s);
-    c->haveScene = true; c->n = n; c->tn = tn; c->ln = ln; c->dirty = false;
+    c->haveScene = true; c->facts.n = n; c->facts.tn = tn; c->facts.ln = ln; c->dirty = false;
     c->loadMissing = 0;  // every device's accumulation restarted: a half-loaded checkpoint is abandoned
     return SAIL_OK;
   }
@@ -1193,14 +948,11 @@ int sail_set_scene(sail_ctx* c, const float* objects, int n, const float* texpar
   if (n > 0 && tn < 1) return fail(c, SAIL_E_INVALID, "sail_set_scene: objects need texParams rows");
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->plugins = *plugins;
+  c->facts.plugins = *plugins;
   c->lastGroups = 1;
   c->lastWavefront = false;
   c->lastJit = false;
-  std::vector<SailPrim> prims;
-  decodeRows(c, objects, n, texparams, tn, prims);
-  c->primTypes.clear();
-  for (const SailPrim& q : prims) c->primTypes.push_back(q.type);
+  const DecodedScene prims = decodeRows(c, objects, n, texparams, tn);
   // per light row: the geometry row an AreaLight samples (area.glsl:8 + shader.shape.js:56)
   std::vector<int32_t> lrow((size_t)(ln > 0 ? ln : 1), 0);
   TexView lv{lights, 18, ln};
@@ -1226,7 +978,7 @@ int sail_set_scene(sail_ctx* c, const float* objects, int n, const float* texpar
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->objectsRows.assign(objects, objects + (size_t)n * 18);
   c->tpRows.assign(texparams, texparams + (size_t)tn * 16);
-  c->n = n; c->tn = tn; c->ln = ln;
+  c->facts.n = n; c->facts.tn = tn; c->facts.ln = ln;
   c->haveScene = true;
   return rowsChanged(c, false);
 }
@@ -1235,10 +987,7 @@ int sail_set_scene(sail_ctx* c, const float* objects, int n, const float* texpar
 // its ids and positions are stale) and sail_move_objects (it stays: the caller records how the rows moved)
 static int updateRows(sail_ctx* c, const float* objects, int n, bool keepTemporal) {
   HIPCHK(c, hipSetDevice(c->device));
-  std::vector<SailPrim> prims;
-  decodeRows(c, objects, n, c->tpRows.data(), c->tn, prims);
-  c->primTypes.clear();
-  for (const SailPrim& q : prims) c->primTypes.push_back(q.type);  // a kernel compiled for the rows follows them
+  const DecodedScene prims = decodeRows(c, objects, n, c->tpRows.data(), c->facts.tn);
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (int rc = uploadPrims(c, prims)) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1254,7 +1003,7 @@ int sail_update_objects(sail_ctx* c, const float* objects, int n) {
     return SAIL_OK;
   }
   if (!c || !c->haveScene) return c ? fail(c, SAIL_E_STATE, "sail_update_objects before sail_set_scene") : SAIL_E_INVALID;
-  if (n != c->n || !objects) return fail(c, SAIL_E_INVALID, "sail_update_objects: n must stay %d", c->n);
+  if (n != c->facts.n || !objects) return fail(c, SAIL_E_INVALID, "sail_update_objects: n must stay %d", c->facts.n);
   return updateRows(c, objects, n, false);
 }
 
@@ -1262,7 +1011,7 @@ int sail_move_objects(sail_ctx* c, const float* objects, int n, const float* mot
   if (!c) return SAIL_E_INVALID;
   // everything is checked before anything changes: a refused call leaves rows, accumulator and temporal state alone
   if (!c->haveScene) return fail(c, SAIL_E_STATE, "sail_move_objects before sail_set_scene");
-  if (n != c->n || !objects) return fail(c, SAIL_E_INVALID, "sail_move_objects: n must stay %d", c->n);
+  if (n != c->facts.n || !objects) return fail(c, SAIL_E_INVALID, "sail_move_objects: n must stay %d", c->facts.n);
   for (size_t i = 0; motion && i < (size_t)n * 3; i++)
     if (!std::isfinite(motion[i]))
       return fail(c, SAIL_E_INVALID, "sail_move_objects: the motion of row %d is not finite", (int)(i / 3));
@@ -1301,7 +1050,7 @@ int sail_set_accum_mode(sail_ctx* c, int mode) {
     c->loadMissing = 0;
     return SAIL_OK;
   }
-  if (mode != SAIL_ACCUM_SUM && c->partMode == SAIL_PART_SAMPLES && c->world > 1)
+  if (mode != SAIL_ACCUM_SUM && c->share.partMode == SAIL_PART_SAMPLES && c->share.world > 1)
     return fail(c, SAIL_E_INVALID, "running-mean accumulation cannot be split by samples");
   HIPCHK(c, hipSetDevice(c->device));
   c->accumMode = mode;
@@ -1315,7 +1064,7 @@ int sail_set_partition(sail_ctx* c, int rank, int world, int mode) {
       return fail(c, SAIL_E_INVALID, "multi-device context: partition must be (0, 1, mode), got (%d, %d, %d)", rank, world, mode);
     const int nd = (int)c->subs.size();
     for (int i = 0; i < nd; i++) if (int rc = sail_set_partition(c->subs[i], i, nd, mode)) return relay(c, rc, c->subs[i]);
-    c->partMode = mode; c->dirty = false;
+    c->share.partMode = mode; c->dirty = false;
     c->loadMissing = 0;
     return SAIL_OK;
   }
@@ -1324,7 +1073,7 @@ int sail_set_partition(sail_ctx* c, int rank, int world, int mode) {
   if (mode == SAIL_PART_SAMPLES && world > 1 && c->accumMode != SAIL_ACCUM_SUM)
     return fail(c, SAIL_E_INVALID, "sample partition needs SAIL_ACCUM_SUM");
   HIPCHK(c, hipSetDevice(c->device));
-  c->rank = rank; c->world = world; c->partMode = mode;
+  c->share.rank = rank; c->share.world = world; c->share.partMode = mode;
   refreshJit(c);  // the Cornell form's samples in flight follow the share of the frame (jitNsFor)
   refreshValues(c);
   return resetAccum(c);
@@ -1335,7 +1084,7 @@ int sail_set_launch_samples(sail_ctx* c, int spp) {
   if (spp < 0 || spp > 1 << 20) return fail(c, SAIL_E_INVALID, "launch samples %d", spp);  // 0: by form
   for (sail_ctx* s : c->subs) if (int rc = sail_set_launch_samples(s, spp)) return relay(c, rc, s);
   if (int rc = flushQueued(c)) return rc;
-  c->launchSpp = spp;
+  c->sw.launchSpp = spp;
   return SAIL_OK;
 }
 
@@ -1358,7 +1107,7 @@ int sail_render_schedule(sail_ctx* c, const float* inv, const float* seeds, cons
   c->hostSamples.clear();
   for (int s = 0; s < spp; s++) {
     const uint64_t k = c->k + (uint64_t)s;
-    if (c->partMode == SAIL_PART_SAMPLES && c->world > 1 && (int)(k % (uint64_t)c->world) != c->rank) continue;
+    if (c->share.partMode == SAIL_PART_SAMPLES && c->share.world > 1 && (int)(k % (uint64_t)c->share.world) != c->share.rank) continue;
     SailSample S;
     memset(&S, 0, sizeof S);
     cornerDirs(inv + 16 * s, eye, S.d);
@@ -1394,7 +1143,7 @@ int sail_render(sail_ctx* c, const float inv[16], const float eye[3], float seed
   memcpy(c->eyeCache, eye, sizeof(float) * 3);
   c->queuedBounces = maxBounces;
   const uint64_t k = c->k;
-  if (!(c->partMode == SAIL_PART_SAMPLES && c->world > 1 && (int)(k % (uint64_t)c->world) != c->rank)) {
+  if (!(c->share.partMode == SAIL_PART_SAMPLES && c->share.world > 1 && (int)(k % (uint64_t)c->share.world) != c->share.rank)) {
     SailSample S;
     memset(&S, 0, sizeof S);
     cornerDirs(inv, eye, S.d);
@@ -1408,7 +1157,7 @@ int sail_render(sail_ctx* c, const float inv[16], const float eye[3], float seed
   // one-sample frames launch 64 at a time unless the host fixed the launch size: the host keeps queueing the next
   // frames while a launch runs (a whole 1,024-frame queue launched at once left the GPU idle meanwhile: the JS host's
   // render() per frame at 85,391 against 91,161 Msamples/s, profiles/r05_bench_js_host*.json)
-  if ((int)c->queued.size() >= (c->launchSpp > 0 ? c->launchSpp : 64)) return flushQueued(c);
+  if ((int)c->queued.size() >= (c->sw.launchSpp > 0 ? c->sw.launchSpp : 64)) return flushQueued(c);
   return SAIL_OK;
 }
 
@@ -1445,7 +1194,7 @@ int sail_read_accum(sail_ctx* c, float* rgba) {
   }
   int rc = sail_sync(c);
   if (rc) return rc;
-  HIPCHK(c, hipMemcpy(rgba, shownAccum(c), (size_t)c->W * c->H * sizeof(float4), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(rgba, shownAccum(c), (size_t)c->share.W * c->share.H * sizeof(float4), hipMemcpyDeviceToHost));
   return SAIL_OK;
 }
 
@@ -1457,7 +1206,7 @@ int sail_readback(sail_ctx* c, float* rgba, float* normal, float* position) {
   }
   int rc = sail_sync(c);
   if (rc) return rc;
-  const size_t np = (size_t)c->W * c->H, bytes = np * sizeof(float4);
+  const size_t np = (size_t)c->share.W * c->share.H, bytes = np * sizeof(float4);
   if (rgba) {
     HIPCHK(c, hipMemcpy(rgba, shownAccum(c), bytes, hipMemcpyDeviceToHost));
     if (c->accumMode == SAIL_ACCUM_SUM) {
@@ -1493,7 +1242,7 @@ int sail_filter(sail_ctx* c, int kind, const float* weights16, float rx, float r
   HIPCHK(c, hipSetDevice(c->device));
   int rc = sail_sync(c);
   if (rc) return rc;
-  const size_t np = (size_t)c->W * c->H;
+  const size_t np = (size_t)c->share.W * c->share.H;
   if (out && (rc = allocOnce(c, &c->filterOut, np * sizeof(float4), "filter output"))) return rc;
   if (out8 && (rc = allocOnce(c, &c->filterOut8, np * 4, "filter output"))) return rc;
   float4* dOut = out ? c->filterOut : nullptr;
@@ -1501,7 +1250,7 @@ int sail_filter(sail_ctx* c, int kind, const float* weights16, float rx, float r
   SailFilterArgs A;
   memset(&A, 0, sizeof A);
   A.accum = shownAccum(c); A.aovN = shownAovN(c); A.aovP = shownAovP(c);
-  A.out = dOut; A.out8 = dOut8; A.W = c->W; A.H = c->H; A.kind = kind; A.accumMode = c->accumMode;
+  A.out = dOut; A.out8 = dOut8; A.W = c->share.W; A.H = c->share.H; A.kind = kind; A.accumMode = c->accumMode;
   if (weights16) memcpy(A.weights, weights16, sizeof A.weights);
   A.rx = rx; A.ry = ry; A.gammaC = gammaC;
   // window taps reach 0.875 r pixels (offsets (j + 0.5) r / 4, j < 4) + the bilinear footprint + rounding
@@ -1546,7 +1295,7 @@ int sail_pick(sail_ctx* c, const float* rays, int count, int32_t* index, float* 
   int32_t* dIdx = (int32_t*)dOut;
   float* dT = (float*)((char*)dOut + (size_t)count * 4);
   hipError_t e = hipMemcpyAsync(dRays, rays, (size_t)count * 6 * sizeof(float), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = sail_launch_pick(c->prims, c->n, dRays, count, dIdx, dT, c->stream);
+  if (e == hipSuccess) e = sail_launch_pick(c->prims, c->facts.n, dRays, count, dIdx, dT, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(index, dIdx, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(t, dT, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -1563,7 +1312,7 @@ int sail_get_stats(sail_ctx* c, sail_stats* s) {
     for (sail_ctx* d : c->subs) {
       sail_stats q;
       if (int rc = sail_get_stats(d, &q)) return relay(c, rc, d);
-      s->samples = c->partMode == SAIL_PART_SAMPLES ? s->samples + q.samples : q.samples;
+      s->samples = c->share.partMode == SAIL_PART_SAMPLES ? s->samples + q.samples : q.samples;
       s->segments += q.segments;
       s->nominal_segments += q.nominal_segments;
       s->kernel_ms = fmax(s->kernel_ms, q.kernel_ms);
@@ -1594,14 +1343,12 @@ int sail_jit_compile(const sail_plugins* plugins, int mode, const int32_t* row_t
   if (!plugins || !bytes || mode < SAIL_JIT_MODE_FLAT || mode > SAIL_JIT_MODE_ROOM || rows < 0 ||
       rows > kSailJitMaxRows || (rows > 0 && !row_types))
     return SAIL_E_INVALID;
-  // the plugin set's precompiled family, as kernelSetFor decides it for a flat scene of these masks
+  // the plugin set's precompiled family, as kernelSetFor decides it for a flat scene of these masks (a light plugin
+  // named stands for light rows)
   const sail_plugins& p = *plugins;
-  int set = SAIL_KSET_GENERIC;
-  if ((p.shape_mask & ~SAIL_KSET_CORNELL_SHAPES) == 0 && (p.material_mask & ~SAIL_KSET_CORNELL_MATS) == 0 &&
-      (p.texture_mask & ~SAIL_KSET_CORNELL_TEX) == 0 && p.light_mask == 0)
-    set = SAIL_KSET_CORNELL;
-  else if ((p.shape_mask & ~SAIL_KSET_ROOM_SHAPES) == 0)
-    set = SAIL_KSET_ROOM;
+  const int set = cornellSet(p.shape_mask, p.material_mask, p.texture_mask, p.light_mask) ? SAIL_KSET_CORNELL
+                  : (p.shape_mask & ~SAIL_KSET_ROOM_SHAPES) == 0                          ? SAIL_KSET_ROOM
+                                                                                          : SAIL_KSET_GENERIC;
   SailJitSpec spec;
   spec.ks = p.shape_mask; spec.km = p.material_mask; spec.kt = p.texture_mask; spec.kl = p.light_mask;
   spec.mode = mode;
@@ -1620,33 +1367,27 @@ int sail_jit_prebuild(const float* objects, int n, const float* texparams, int t
       !arch || (n > 0 && tn < 1))
     return fail(nullptr, SAIL_E_INVALID, "sail_jit_prebuild: bad arguments");
   (void)lights;
-  // the spec a context with the product's defaults derives for this scene (jitSpecFor), without a device
-  sail_ctx t;
-  t.plugins = *plugins;
-  t.n = n; t.tn = tn; t.ln = ln;
-  t.haveScene = true;
-  std::vector<SailPrim> prims;
-  int anyHit = 0;
-  decodePrims(objects, n, tn, plugins->shape_mask, prims, &anyHit, nullptr);
-  fillCats(prims, texparams, tn);  // the rows as sail_set_scene uploads them: the value kernel compiles them in
-  for (const SailPrim& q : prims) t.primTypes.push_back(q.type);
-  std::vector<uint32_t> rowWords((size_t)n * 32);
-  if (n > 0) memcpy(rowWords.data(), prims.data(), sizeof(SailPrim) * (size_t)n);
-  SailJitSpec spec;
-  int mode = 0;
+  // the specs a context with the product's defaults derives for this scene (jitSpecFor), without a device: for a large
+  // share of the frame and for a small one, which differ for the Cornell form alone (16 samples in flight and 1, jitNsFor)
+  const DecodedScene d = decodeScene(objects, n, texparams, tn, *plugins);
+  const SceneFacts f = sceneFacts(d, tn, ln, *plugins);
+  const PlanSwitches sw;
   if (built) *built = 0;
-  if (!jitSpecFor(&t, &spec, &mode)) return SAIL_OK;  // the scene gets no run-time kernel
-  std::string err;
-  // the Cornell form in both shapes: 16 samples in flight (a large share of the frame) and 1 (a rank of 8, jitNsFor)
-  const bool cornell = mode == SAIL_JIT_MODE_FLAT && kernelSetFor(&t) == SAIL_KSET_CORNELL;
-  for (int ns : {16, 1}) {
-    if (cornell) spec.ns = ns;
+  SailJitSpec first;
+  bool any = false;
+  for (const ShareFacts& sh : {largeShare(), smallShare()}) {
+    SailJitSpec spec;
+    int mode = 0;
+    if (!jitSpecFor(f, sw, sh, &spec, &mode)) return SAIL_OK;  // the scene gets no run-time kernel
+    if (any && sailJitSpecEqual(spec, first)) break;  // one shape serves both shares
+    first = spec;
+    any = true;
+    std::string err;
     if (sail_jit_code_to_dir(arch, spec, dir, &err)) return fail(nullptr, SAIL_E_INVALID, "sail_jit_prebuild: %s", err.c_str());
     // and the value kernel a context loads once the scene has settled, where the spec has one
     SailJitSpec vspec;
-    if (valueSpecFor(spec, rowWords, texparams, tn, t.jit, &vspec) && sail_jit_code_to_dir(arch, vspec, dir, &err))
+    if (valueSpecFor(spec, d.rowWords, texparams, tn, sw.jit, &vspec) && sail_jit_code_to_dir(arch, vspec, dir, &err))
       return fail(nullptr, SAIL_E_INVALID, "sail_jit_prebuild: %s", err.c_str());
-    if (!cornell) break;
   }
   if (built) *built = 1;
   return SAIL_OK;
@@ -1669,23 +1410,16 @@ int sail_jit_spec_key(const float* objects, int n, const float* texparams, int t
                       const char* arch, int jit, int value, uint64_t* key, char* defs, size_t* defs_len) {
   if (n < 1 || tn < 1 || !objects || !texparams || !plugins || !arch || !key)
     return fail(nullptr, SAIL_E_INVALID, "sail_jit_spec_key: bad arguments");
-  // as sail_jit_prebuild: the spec a context with these switches (else the product's defaults) derives, without a device
-  sail_ctx t;
-  if (jit >= 0) t.jit = jit;
-  t.plugins = *plugins;
-  t.n = n; t.tn = tn;
-  t.haveScene = true;
-  std::vector<SailPrim> prims;
-  int anyHit = 0;
-  decodePrims(objects, n, tn, plugins->shape_mask, prims, &anyHit, nullptr);
-  fillCats(prims, texparams, tn);
-  for (const SailPrim& q : prims) t.primTypes.push_back(q.type);
-  std::vector<uint32_t> rowWords((size_t)n * 32);
-  memcpy(rowWords.data(), prims.data(), sizeof(SailPrim) * (size_t)n);
+  // as sail_jit_prebuild: the spec a context with these switches (else the product's defaults) derives, without a device,
+  // for a small share of the frame (the Cornell form holding 1 sample in flight) and a scene without light rows
+  const DecodedScene d = decodeScene(objects, n, texparams, tn, *plugins);
+  const SceneFacts f = sceneFacts(d, tn, 0, *plugins);
+  PlanSwitches sw;
+  if (jit >= 0) sw.jit = jit;
   SailJitSpec spec, vspec;
   int mode = 0;
   *key = 0;
-  if (!jitSpecFor(&t, &spec, &mode) || (value && !valueSpecFor(spec, rowWords, texparams, tn, t.jit, &vspec))) {
+  if (!jitSpecFor(f, sw, smallShare(), &spec, &mode) || (value && !valueSpecFor(spec, d.rowWords, texparams, tn, sw.jit, &vspec))) {
     if (defs_len) *defs_len = 0;
     return SAIL_OK;  // the scene gets no such kernel
   }
@@ -1720,11 +1454,59 @@ int sail_plan_last_bounce(const float* objects, int n, const float* texparams, i
   if (n < 0 || tn < 0 || (n > 0 && !objects) || (tn > 0 && !texparams) || !plugins || !quiet_rows || !skip_sort ||
       (n > 0 && tn < 1))
     return fail(nullptr, SAIL_E_INVALID, "sail_plan_last_bounce: bad arguments");
-  std::vector<SailPrim> prims;
-  int anyHit = 0;
-  decodePrims(objects, n, tn, plugins->shape_mask, prims, &anyHit, nullptr);
-  fillCats(prims, texparams, tn);
-  lastBounceRows(prims, texparams, tn, plugins->material_mask, kernel_lights != 0, quiet_rows, skip_sort);
+  const DecodedScene d = decodeScene(objects, n, texparams, tn, *plugins);
+  lastBounceRows(d.prims, texparams, tn, plugins->material_mask, kernel_lights != 0, quiet_rows, skip_sort);
+  return SAIL_OK;
+}
+
+int sail_plan_launch(const sail_launch_facts* in, sail_launch_plan* out) {
+  if (!in || !out) return fail(nullptr, SAIL_E_INVALID, "sail_plan_launch: bad arguments");
+  const sail_launch_facts& q = *in;
+  if (q.n < 1 || q.tn < 1 || q.ln < 0 || !q.objects || !q.texparams || !q.plugins)
+    return fail(nullptr, SAIL_E_INVALID, "sail_plan_launch: bad scene (n=%d tn=%d ln=%d)", q.n, q.tn, q.ln);
+  if (q.width <= 0 || q.height <= 0 || q.width > 32768 || q.height > 32768 || q.world < 1 || q.rank < 0 || q.rank >= q.world ||
+      (q.part_mode != SAIL_PART_TILES && q.part_mode != SAIL_PART_SAMPLES) || q.compute_units < 1)
+    return fail(nullptr, SAIL_E_INVALID, "sail_plan_launch: bad share (%dx%d rank %d of %d, mode %d, %d CUs)", q.width, q.height,
+                q.rank, q.world, q.part_mode, q.compute_units);
+  if (q.nspp < 1 || q.launch_spp < 0 || q.tier < SAIL_LAUNCH_TIER_NONE || q.tier > SAIL_LAUNCH_TIER_VALUE)
+    return fail(nullptr, SAIL_E_INVALID, "sail_plan_launch: bad launch (nspp=%d launch_spp=%d tier=%d)", q.nspp, q.launch_spp, q.tier);
+  PlanSwitches sw;
+  sw.launchSpp = q.launch_spp;
+  for (int o = 0; o < 16; o++)
+    if ((q.debug_set >> o) & 1u)
+      if (const char* why = setSwitch(&sw, o, q.debug[o]))
+        return fail(nullptr, SAIL_E_INVALID, "sail_plan_launch: option %d: %s", o, why);
+  ShareFacts sh;
+  sh.W = q.width; sh.H = q.height; sh.rank = q.rank; sh.world = q.world; sh.partMode = q.part_mode; sh.numCUs = q.compute_units;
+  int tx, ty;
+  const int share = partitionTiles(sh, &tx, &ty);
+  if (q.active_tiles > share || share < 1 || q.active_tiles == 0)
+    return fail(nullptr, SAIL_E_INVALID, "sail_plan_launch: no tile to trace (%d active of the share's %d)", q.active_tiles, share);
+  const DecodedScene d = decodeScene(q.objects, q.n, q.texparams, q.tn, *q.plugins);
+  const SceneFacts f = sceneFacts(d, q.tn, q.ln, *q.plugins);
+  // the kernel that runs, as a context derives it: the types spec of the scene and share, and the value spec on top
+  SailJitSpec types, value;
+  int mode = 0;
+  const bool haveTypes = jitSpecFor(f, sw, sh, &types, &mode);
+  if (q.tier >= SAIL_LAUNCH_TIER_TYPES && !haveTypes)
+    return fail(nullptr, SAIL_E_INVALID, "sail_plan_launch: the scene gets no run-time kernel under these switches");
+  if (q.tier == SAIL_LAUNCH_TIER_VALUE && !valueSpecFor(types, d.rowWords, q.texparams, q.tn, sw.jit, &value))
+    return fail(nullptr, SAIL_E_INVALID, "sail_plan_launch: the scene gets no value kernel under these switches");
+  LaunchChunk k;
+  k.nspp = q.nspp;
+  k.masked = q.active_tiles > 0;
+  k.owned = k.masked ? q.active_tiles : share;
+  k.cullFmaOk = q.cull_fma_ok != 0; k.eyeNearScene = q.eye_near_scene != 0;
+  k.run = q.tier == SAIL_LAUNCH_TIER_VALUE ? &value : (q.tier == SAIL_LAUNCH_TIER_TYPES ? &types : nullptr);
+  const LaunchPlan P = planLaunch(f, sw, sh, k);
+  memset(out, 0, sizeof *out);
+  out->kernel_set = P.kernelSet; out->cull_prims = P.cullPrims; out->cull_primary = P.cullPrimary;
+  out->wavefront = P.wavefront; out->ns = P.ns;
+  out->sample_groups = P.sampleGroups; out->group_spp = P.groupSpp; out->group_home = P.groupHome; out->staged = P.staged;
+  out->grid = P.grid; out->threads = P.threads;
+  out->kernel_lights = P.kernelLights;
+  out->jit_mode = (k.run && !P.wavefront) ? k.run->mode : -1;
+  out->launch_samples = launchSamples(sw, haveTypes ? &types : nullptr);
   return SAIL_OK;
 }
 

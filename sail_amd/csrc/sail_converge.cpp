@@ -23,14 +23,14 @@ int sail_noise_mark(sail_ctx* c) {
     return fail(c, SAIL_E_STATE, "sail_noise_mark: SAIL_ACCUM_COMPAT8 stores 8-bit frames, whose halves cannot be compared");
   HIPCHK(c, hipSetDevice(c->device));
   if (int rc = sail_sync(c)) return rc;
-  const size_t bytes = (size_t)c->W * c->H * sizeof(float4);
+  const size_t bytes = (size_t)c->share.W * c->share.H * sizeof(float4);
   if (int rc = allocOnce(c, &c->noiseMark, bytes, "noise mark")) return rc;
   if (c->maskSet && c->noiseHave) {  // frozen tiles keep the mark they froze with
     SailNoiseArgs A;
     memset(&A, 0, sizeof A);
     A.S = shownAccum(c); A.P = c->noiseMark;
-    A.W = c->W; A.H = c->H;
-    A.active64 = c->maskBytes; A.tiles64X = (c->W + 63) / 64;
+    A.W = c->share.W; A.H = c->share.H;
+    A.active64 = c->maskBytes; A.tiles64X = (c->share.W + 63) / 64;
     HIPCHK(c, sail_launch_noise_copy(A, c->stream));
   } else {
     HIPCHK(c, hipMemcpyAsync(c->noiseMark, shownAccum(c), bytes, hipMemcpyDeviceToDevice, c->stream));
@@ -56,8 +56,8 @@ int sail_noise_estimate(sail_ctx* c, sail_noise_info* out, float* tile_err, floa
   if (c->k <= c->noiseK)
     return fail(c, SAIL_E_STATE, "sail_noise_estimate: no sample since the mark (k = %llu, marked at %llu)",
                 (unsigned long long)c->k, (unsigned long long)c->noiseK);
-  const int tx = (c->W + 15) / 16, ty = (c->H + 15) / 16;
-  const size_t nt = (size_t)tx * ty, np = (size_t)c->W * c->H;
+  const int tx = (c->share.W + 15) / 16, ty = (c->share.H + 15) / 16;
+  const size_t nt = (size_t)tx * ty, np = (size_t)c->share.W * c->share.H;
   if (int rc = allocOnce(c, &c->noiseOut, nt * 8, "noise tiles")) return rc;
   if (pixel_err)
     if (int rc = allocOnce(c, &c->noisePix, np * sizeof(float), "noise map")) return rc;
@@ -66,11 +66,11 @@ int sail_noise_estimate(sail_ctx* c, sail_noise_info* out, float* tile_err, floa
   A.S = shownAccum(c); A.P = c->noiseMark;
   A.tileSum = c->noiseOut; A.tileBad = (uint32_t*)(c->noiseOut + nt);
   A.pixErr = pixel_err ? c->noisePix : nullptr;
-  A.W = c->W; A.H = c->H;
+  A.W = c->share.W; A.H = c->share.H;
   A.mix = c->accumMode == SAIL_ACCUM_MIX;
   A.kf = (float)c->k; A.hf = (float)c->noiseK;
   A.remark = remark != 0;
-  if (c->maskSet) { A.active64 = c->maskBytes; A.tiles64X = (c->W + 63) / 64; }
+  if (c->maskSet) { A.active64 = c->maskBytes; A.tiles64X = (c->share.W + 63) / 64; }
   std::vector<float> host(nt * 2);
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (int rc = getEvent(c, &e0)) return rc;
@@ -93,7 +93,7 @@ int sail_noise_estimate(sail_ctx* c, sail_noise_info* out, float* tile_err, floa
   for (int j = 0; j < ty; j++)
     for (int i = 0; i < tx; i++) {
       const size_t t = (size_t)j * tx + i;
-      const int w = c->W - i * 16 < 16 ? c->W - i * 16 : 16, h = c->H - j * 16 < 16 ? c->H - j * 16 : 16;
+      const int w = c->share.W - i * 16 < 16 ? c->share.W - i * 16 : 16, h = c->share.H - j * 16 < 16 ? c->share.H - j * 16 : 16;
       const double tileMean = (double)host[t] / (double)(w * h);
       sum += (double)host[t];
       if (tileMean > maxTile) maxTile = tileMean;
@@ -131,7 +131,7 @@ static int renderSamplesTo(sail_ctx* c, const char* who, const double mvp[16], c
     const int spp = (int)(next - *k < kChunk ? next - *k : kChunk);
     inv.resize((size_t)spp * 16);
     seeds.resize((size_t)spp);
-    if (int rc = sail_schedule(mvp, c->W, c->H, (int)*k, spp, inv.data(), seeds.data()))
+    if (int rc = sail_schedule(mvp, c->share.W, c->share.H, (int)*k, spp, inv.data(), seeds.data()))
       return fail(c, rc, "%s: sail_schedule failed (a singular camera matrix?)", who);
     if (int rc = sail_render_schedule(c, inv.data(), seeds.data(), eye, spp, maxBounces)) return rc;
     *k += (uint64_t)spp;
@@ -156,7 +156,7 @@ int sail_render_until(sail_ctx* c, const double mvp[16], const float eye[3], int
   memset(out, 0, sizeof *out);
   out->mean = out->max_tile = INFINITY;  // until the first estimate
   out->k = out->k_mark = k;
-  out->tiles_x = (c->W + 15) / 16; out->tiles_y = (c->H + 15) / 16;
+  out->tiles_x = (c->share.W + 15) / 16; out->tiles_y = (c->share.H + 15) / 16;
   int nlooks = 0, conv = 0;
   bool marked = false;
   for (;;) {
@@ -190,7 +190,7 @@ int sail_render_until(sail_ctx* c, const double mvp[16], const float eye[3], int
 // ---- adaptive sampling: the tile mask and render-until-every-tile-converged (include/sail_hip.h) ---------------------------
 int sail_set_active_tiles(sail_ctx* c, const uint8_t* active, int count) {
   if (!c) return SAIL_E_INVALID;
-  const int tx = (c->W + 63) / 64, ty = (c->H + 63) / 64, tiles = tx * ty;
+  const int tx = (c->share.W + 63) / 64, ty = (c->share.H + 63) / 64, tiles = tx * ty;
   const bool clear = !active && count == 0;
   // everything is checked before anything changes
   if (!clear && (!active || count != tiles))
@@ -232,14 +232,14 @@ int sail_set_active_tiles(sail_ctx* c, const uint8_t* active, int count) {
   std::vector<uint8_t> m((size_t)tiles);
   for (int t = 0; t < tiles; t++) m[(size_t)t] = active[t] ? 1 : 0;
   // this rank's active tiles, ascending, and their in-frame pixels
-  const int w = (c->partMode == SAIL_PART_SAMPLES) ? 1 : c->world, r = (c->partMode == SAIL_PART_SAMPLES) ? 0 : c->rank;
+  const int w = (c->share.partMode == SAIL_PART_SAMPLES) ? 1 : c->share.world, r = (c->share.partMode == SAIL_PART_SAMPLES) ? 0 : c->share.rank;
   std::vector<int32_t> table;
   long long px = 0;
   for (int t = r; t < tiles; t += w) {
     if (!m[(size_t)t]) continue;
     table.push_back(t);
     const int x0 = (t % tx) * 64, y0 = (t / tx) * 64;
-    const int cw = (c->W - x0) < 64 ? (c->W - x0) : 64, ch = (c->H - y0) < 64 ? (c->H - y0) : 64;
+    const int cw = (c->share.W - x0) < 64 ? (c->share.W - x0) : 64, ch = (c->share.H - y0) < 64 ? (c->share.H - y0) : 64;
     px += (long long)cw * ch;
   }
   if (!table.empty())
@@ -259,7 +259,7 @@ int sail_set_active_tiles(sail_ctx* c, const uint8_t* active, int count) {
 
 int sail_get_active_tiles(sail_ctx* c, uint8_t* active, int count, int* n_active) {
   if (!c) return SAIL_E_INVALID;
-  const int tiles = ((c->W + 63) / 64) * ((c->H + 63) / 64);
+  const int tiles = ((c->share.W + 63) / 64) * ((c->share.H + 63) / 64);
   if (!active || count != tiles)
     return fail(c, SAIL_E_INVALID, "sail_get_active_tiles: count %d, the frame has %d tiles", count, tiles);
   const sail_ctx* h = c->subs.empty() ? c : c->subs[0];  // every device of a multi-device context holds the whole mask
@@ -336,11 +336,11 @@ int sail_render_adaptive(sail_ctx* c, const double mvp[16], const float eye[3], 
   if (!c->haveScene) return fail(c, SAIL_E_STATE, "sail_render_adaptive before sail_set_scene");
   if (int rc = loadIncomplete(c, "sail_render_adaptive")) return rc;
   const sail_ctx* h = c->subs.empty() ? c : c->subs[0];  // holds the sample index, the whole mask and the mark
-  const int tx = (c->W + 63) / 64, ty = (c->H + 63) / 64, tiles = tx * ty;
-  const int tx16 = (c->W + 15) / 16, ty16 = (c->H + 15) / 16;
+  const int tx = (c->share.W + 63) / 64, ty = (c->share.H + 63) / 64, tiles = tx * ty;
+  const int tx16 = (c->share.W + 15) / 16, ty16 = (c->share.H + 15) / 16;
   auto tilePixels = [&](int t) {
     const int x0 = (t % tx) * 64, y0 = (t / tx) * 64;
-    return (uint64_t)((c->W - x0) < 64 ? (c->W - x0) : 64) * (uint64_t)((c->H - y0) < 64 ? (c->H - y0) : 64);
+    return (uint64_t)((c->share.W - x0) < 64 ? (c->share.W - x0) : 64) * (uint64_t)((c->share.H - y0) < 64 ? (c->share.H - y0) : 64);
   };
   std::vector<uint8_t> active((size_t)tiles);
   int nActive = 0;
@@ -376,7 +376,7 @@ int sail_render_adaptive(sail_ctx* c, const double mvp[16], const float eye[3], 
     } else {
       if (int rc = sail_noise_estimate(c, &out->noise, err16.data(), nullptr, 0)) return rc;
       step.mean = out->noise.mean; step.max_tile = out->noise.max_tile;
-      if (int rc = sail_plan_adaptive(c->W, c->H, err16.data(), p.target, p.dilate, active.data(), active.data(), nullptr, &nActive))
+      if (int rc = sail_plan_adaptive(c->share.W, c->share.H, err16.data(), p.target, p.dilate, active.data(), active.data(), nullptr, &nActive))
         return fail(c, rc, "sail_render_adaptive: %s", sail_last_error(nullptr));
       if (int rc = sail_set_active_tiles(c, active.data(), tiles)) return rc;
       // the look it stops at leaves the mark at the look before, for sail_denoise; every other look moves the active
@@ -391,7 +391,7 @@ int sail_render_adaptive(sail_ctx* c, const double mvp[16], const float eye[3], 
   if (int rc = sail_get_stats(c, &st1)) return rc;
   out->converged = nActive == 0;
   out->active_tiles = nActive;
-  out->frame_pixel_samples = (uint64_t)c->W * (uint64_t)c->H * (k - k0);
+  out->frame_pixel_samples = (uint64_t)c->share.W * (uint64_t)c->share.H * (k - k0);
   out->kernel_ms = st1.kernel_ms - st0.kernel_ms;
   if (tile_samples)
     for (int t = 0; t < tiles; t++)

@@ -1,6 +1,7 @@
 // sail_ctx.h — what the host files of libsail_hip.so share: the context, its run-time-kernel slot, the error, allocation
 // and event helpers, and the launch wrappers defined beside the kernels. Internal; the C ABI is include/sail_hip.h.
-//   sail_capi.cpp      context life cycle, scene decode and upload, run-time-kernel policy, render, readback, filter, pick
+//   sail_capi.cpp      context life cycle, scene decode and upload, the kernel slots, render, readback, filter, pick
+//   sail_plan.cpp      kernel choice and launch shape as pure functions of plain facts (sail_plan.h; no context, no HIP)
 //   sail_multi.cpp     RCCL binding, multi-device reduce, checkpoint parts
 //   sail_converge.cpp  noise estimate, render-until, tile mask, adaptive sampling
 //   sail_post.cpp      a-trous denoiser, reprojection, moment tracking, temporal filter, albedo map
@@ -18,6 +19,7 @@
 hipError_t sail_launch_trace(const SailTraceArgs& A, int blocks, hipStream_t s);
 // sail_jit.cpp: the trace kernel pair compiled at run time for exactly one plugin set (on the current device)
 #include "sail_jit.h"
+#include "sail_plan.h"
 hipError_t sail_launch_filter(const SailFilterArgs& A, hipStream_t s);
 hipError_t sail_launch_accum(const SailTraceArgs& A, int blocks, hipStream_t s);
 hipError_t sail_launch_math(int fn, const float* x, const float* y, float* out, int count);
@@ -144,7 +146,11 @@ struct JitSlot {
 };
 
 struct sail_ctx {
-  int device = 0, W = 0, H = 0;
+  int device = 0;
+  // what the policy of sail_plan.h reads: the scene (counts, plugin masks, row shape ids), the switches, the share
+  SceneFacts facts;
+  PlanSwitches sw;
+  ShareFacts share;
   uint32_t flags = 0;
   hipStream_t stream = nullptr;
   float4* accum = nullptr;
@@ -164,8 +170,6 @@ struct sail_ctx {
   std::vector<SailSample> hostSamples;
   std::vector<float> objectsRows;
   std::vector<float> tpRows;  // host copy of texParams (category words of updated objects)
-  int n = 0, tn = 0, ln = 0;
-  sail_plugins plugins{};
   bool haveScene = false;
   int shadowAnyHit = 0;
   // the rows' last-bounce classes (lastBounceRows) for a kernel without ([0]) and with ([1]) a light plugin compiled in,
@@ -174,31 +178,20 @@ struct sail_ctx {
   uint32_t lastQuietRows[2] = {0u, 0u};
   int lastSkipSort[2] = {0, 0};
   std::vector<unsigned long long> typeMasksHost;  // staging for the per-chunk type masks (async copy source)
-  int cullMinPrims = 8;  // scenes with at least this many primitives use the padded-box pre-cull
   int lastGroups = 1;         // the last trace launch: sample groups (sail_kernel_name)
   bool lastWavefront = false;
-  int flatGroupRounds = 36;  // sample groups: residency rounds queued per launch (flat kernels, SAIL_DEBUG_GROUP_ROUNDS)
-  int cullGroupRounds = 64;  // the same for the pre-cull kernel's 1,024-thread workgroups
   int cullFma = 1;       // SAIL_CULL_FMA=0: always the plain pre-cull form (tests)
   double primExtent = INFINITY;  // largest |padded bound| coordinate (inf: some primitive is unbounded)
   SceneBox scene{};              // union of the primitives' finite bounds (padPrimBounds)
-  int forceGeneric = 0;  // SAIL_FORCE_GENERIC=1: always launch the all-plugin kernel (tests)
-  int forceGroups = 0;   // SAIL_SAMPLE_GROUPS=g: fixed sample-group count (tests); 0 = by occupancy
-  int wavefront = 0;     // SAIL_DEBUG_WAVEFRONT: the pre-cull path by the wavefront split (study)
-  int jit = 59;  // SAIL_DEBUG_JIT bits: which scenes get a run-time kernel (jitSpecFor; instrumented in the phase build)
   // The scene's run-time kernel (refreshJit), compiled for its plugin set and its rows' types. Until it is loaded the
   // precompiled kernel of the scene's set serves (same results); a launch waits up to jitWait ms for it
   // (SAIL_DEBUG_JIT_WAIT; -1 until it is built). Its error is the one sail_get_kernel_info reports.
   JitSlot typesSlot;
   int jitWait = 0;
-  int jitNt = 0;  // SAIL_DEBUG_JIT_NT: threads per workgroup of the run-time kernels (0: the form's own)
-  int jitNs = 0;  // SAIL_DEBUG_JIT_NS: samples in flight of the run-time kernels (0: the form's default, jitNsFor)
   // The value kernel, a second tier on top of the scene's run-time kernel (refreshValues): the same spec with the rows'
   // and the texParams table's words compiled in, asked for once `settled` samples were rendered since the rows last
   // changed (rowsChanged in sail_capi.cpp, a new types spec; not sail_reset or the camera). A launch uses it when
-  // it is loaded and never waits for it. jitValuesAfter (SAIL_DEBUG_JIT_VALUES_AFTER): 0 at once, < 0 never; 256 is a
-  // policy value, not tuned -- it only has to keep scenes in motion and few-sample renders from compiling.
-  int jitValuesAfter = 256;
+  // it is loaded and never waits for it (sw.jitValuesAfter).
   uint64_t settled = 0;
   std::vector<uint32_t> rowWords;  // the decoded rows as uploaded (uploadPrims), 32 words each
   JitSlot valueSlot;
@@ -211,17 +204,11 @@ struct sail_ctx {
   bool lastJit = false;  // the last trace launch ran a run-time compiled kernel (sail_kernel_name)
   int lastJitMode = 0;
   uint64_t lastBuildId = 0;  // the run-time kernel's build identity (sail_get_kernel_info)
-  std::vector<int> primTypes;  // decoded shape id of each row (run-time kernels compiled for the scene's rows)
-  float4* wf = nullptr;  // its path state: 11 float4 arrays of wfSlots
+  float4* wf = nullptr;  // the wavefront split's path state: 11 float4 arrays of wfSlots
   size_t wfSlots = 0;
-  int numCUs = 256;
   float* stage = nullptr;    // sample-group staging, allocated on first use
   size_t stageBytes = 0;
   int accumMode = SAIL_ACCUM_SUM;
-  int rank = 0, world = 1, partMode = SAIL_PART_TILES;
-  // samples per launch (sail_set_launch_samples); 0 = by form (launchSamples): 64 measured C2 +0.7 %, C3 +0.5 %, C4/C5
-  // +-0.2 % over 32 (profiles/r04_launch_spp*)
-  int launchSpp = 0;
   uint64_t k = 0;  // global sample index of the next sample (the reference's sampleCount)
   uint64_t samplesThisRank = 0;
   uint64_t nominalSegments = 0;
@@ -393,6 +380,6 @@ inline const float4* shownAccum(const sail_ctx* c) { return c->reduced ? c->fram
 inline const float4* shownAovN(const sail_ctx* c) { return c->reduced && c->frameN ? c->frameN : c->aovN; }
 inline const float4* shownAovP(const sail_ctx* c) { return c->reduced && c->frameP ? c->frameP : c->aovP; }
 // the frame's 16x16 tiles (the post passes keep a count or more per tile)
-inline size_t tiles16(const sail_ctx* c) { return (size_t)((c->W + 15) / 16) * (size_t)((c->H + 15) / 16); }
+inline size_t tiles16(const sail_ctx* c) { return (size_t)((c->share.W + 15) / 16) * (size_t)((c->share.H + 15) / 16); }
 
 #pragma GCC visibility pop

@@ -53,7 +53,6 @@ extern const char* const sail_jit_src_texts[];
 extern const int sail_jit_src_count;
 extern const int sail_trace_phase_timing;  // sail_frame.hip: 1 in the phase-timing build (libsail_hip_phase.so)
 
-int sailJitThreads(const SailJitSpec& s) { return s.nt ? s.nt : (s.mode == 1 ? 1024 : 256); }
 bool sailJitSpecEqual(const SailJitSpec& a, const SailJitSpec& b) {
   const auto t = [](const SailJitSpec& x) {
     return std::tie(x.ks, x.km, x.kt, x.kl, x.mode, x.waves, x.rows, x.ldsFit, x.tn, x.ns, x.nt, x.types[0], x.types[1], x.types[2],

@@ -1,4 +1,4 @@
-// sail_jit.h — what one run-time compiled trace kernel pair is specialised to (sail_jit.cpp, used by sail_capi.cpp).
+// sail_jit.h — what one run-time compiled trace kernel pair is specialised to (sail_jit.cpp, used by sail_plan.cpp and sail_capi.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -26,7 +26,7 @@ struct SailJitSpec {
   // rowForm 1: a value kernel of at most kSailJitRowRecordMax rows in the row-shading form (SAIL_JIT_ROWSHADE in
   // sail_geom.h; SAIL_DEBUG_JIT bit 32). rowShade: the rows (bit i: row i) whose row-uniform waves run the rest of the
   // bounce in their row's branch, on the row's material constants; rowQuiet: those of them whose copy leaves the
-  // radiance alone (quiet rows, sail_capi.cpp lastBounceRows). Both 0: the kernel is the plain value kernel's code.
+  // radiance alone (quiet rows, sail_plan.cpp lastBounceRows). Both 0: the kernel is the plain value kernel's code.
   // All 0 in every types spec.
   int rowForm = 0, rowShade = 0, rowQuiet = 0;
   // >= 0: a value kernel that defers this Sphere row's root solve past the path sort (SAIL_JIT_ROWDEFER in sail_geom.h;
@@ -37,7 +37,8 @@ struct SailJitSpec {
   int masked = 0;
 };
 bool sailJitSpecEqual(const SailJitSpec& a, const SailJitSpec& b);
-int sailJitThreads(const SailJitSpec& s);  // threads per workgroup of the spec's kernels
+// threads per workgroup of the spec's kernels
+inline int sailJitThreads(const SailJitSpec& s) { return s.nt ? s.nt : (s.mode == 1 ? 1024 : 256); }
 
 // A loaded kernel pair and where its code object came from.
 struct SailJitKernel {

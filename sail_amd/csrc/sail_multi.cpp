@@ -13,7 +13,7 @@ constexpr int kNcclFloat32 = 7, kNcclSum = 0;
 
 // ---- reduced frame (sail_reduce, multi-device contexts) -----------------------------------------------------------
 int ensureFrame(sail_ctx* c) {
-  const size_t bytes = (size_t)c->W * c->H * sizeof(float4);
+  const size_t bytes = (size_t)c->share.W * c->share.H * sizeof(float4);
   float4** bufs[3] = {&c->frame, c->aovN ? &c->frameN : nullptr, c->aovP ? &c->frameP : nullptr};
   for (float4** b : bufs) {
     if (!b) continue;
@@ -104,11 +104,11 @@ int groupReduce(sail_ctx* g) {
   if ((nd == 1 && g->groupComms.empty()) || !g->dirty) return SAIL_OK;
   HIPCHK(g, hipSetDevice(r->device));
   if (int rc = ensureFrame(r)) return relay(g, rc, r);
-  const bool tiles = g->partMode == SAIL_PART_TILES;
-  const size_t np = (size_t)g->W * g->H, bytes = np * sizeof(float4);
+  const bool tiles = g->share.partMode == SAIL_PART_TILES;
+  const size_t np = (size_t)g->share.W * g->share.H, bytes = np * sizeof(float4);
   // every device's share of the exchange (sail_plan_reduce: device i = rank i of nd, root 0)
   std::vector<sail_reduce_plan> plan((size_t)nd);
-  for (int i = 0; i < nd; i++) plan[i] = planReduce(g->W, g->H, i, nd, g->partMode, r->k, 0);
+  for (int i = 0; i < nd; i++) plan[i] = planReduce(g->share.W, g->share.H, i, nd, g->share.partMode, r->k, 0);
   const int owner = tiles ? 0 : plan[0].aov_owner;
   if (g->groupLocal) {  // every "device" is the same GPU: wait for the others' streams, sum in rank order
     for (sail_ctx* s : g->subs) HIPCHK(g, hipStreamSynchronize(s->stream));
@@ -178,7 +178,7 @@ int sail_accum_device_ptr(sail_ctx* c, void** ptr, size_t* bytes) {
   if (!c->subs.empty()) return relay(c, sail_accum_device_ptr(c->subs[0], ptr, bytes), c->subs[0]);
   if (int rc = flushQueued(c)) return rc;  // the sums the caller's collective will read are queued on this stream
   *ptr = c->accum;
-  *bytes = (size_t)c->W * c->H * sizeof(float4);
+  *bytes = (size_t)c->share.W * c->share.H * sizeof(float4);
   return SAIL_OK;
 }
 
@@ -226,9 +226,9 @@ int sail_reduce(sail_ctx* c, int root) {
   const bool isRoot = c->commRank == root;
   const bool aov = c->aovN || c->aovP;
   // a sample split shows the AOVs of the rank that rendered the last sample: the others send -0 maps
-  const bool own = planReduce(c->W, c->H, c->rank, c->world, c->partMode, c->k, root).send_own_aovs != 0;
+  const bool own = planReduce(c->share.W, c->share.H, c->share.rank, c->share.world, c->share.partMode, c->k, root).send_own_aovs != 0;
   if (isRoot || (aov && !own)) { if (int rc = ensureFrame(c)) return rc; }
-  const size_t np = (size_t)c->W * c->H, count = np * 4;
+  const size_t np = (size_t)c->share.W * c->share.H, count = np * 4;
   if (aov && !own) {
     if (c->frameN) HIPCHK(c, fillNegZero(c->frameN, np, c->stream));
     if (c->frameP) HIPCHK(c, fillNegZero(c->frameP, np, c->stream));
@@ -263,7 +263,7 @@ int sail_save_accum(sail_ctx* c, int part, float* sums, uint64_t* k) {
   }
   if (part != 0) return fail(c, SAIL_E_INVALID, "sail_save_accum: part %d of 1", part);
   if (int rc = sail_sync(c)) return rc;
-  HIPCHK(c, hipMemcpy(sums, c->accum, (size_t)c->W * c->H * sizeof(float4), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(sums, c->accum, (size_t)c->share.W * c->share.H * sizeof(float4), hipMemcpyDeviceToHost));
   *k = c->k;
   return SAIL_OK;
 }
@@ -294,7 +294,7 @@ int sail_load_accum(sail_ctx* c, int part, const float* sums, uint64_t k) {
     return SAIL_OK;
   }
   if (part != 0 && part != -1) return fail(c, SAIL_E_INVALID, "sail_load_accum: part %d of 1", part);
-  if (part == -1 && c->world > 1 && c->partMode == SAIL_PART_SAMPLES && c->accumMode != SAIL_ACCUM_SUM)
+  if (part == -1 && c->share.world > 1 && c->share.partMode == SAIL_PART_SAMPLES && c->accumMode != SAIL_ACCUM_SUM)
     return fail(c, SAIL_E_INVALID, "sail_load_accum: a running mean cannot be split by samples");
   HIPCHK(c, hipSetDevice(c->device));
   const bool marked = c->noiseHave;
@@ -302,16 +302,16 @@ int sail_load_accum(sail_ctx* c, int part, const float* sums, uint64_t k) {
   c->noiseHave = marked;  // a loaded checkpoint continues a render: the noise estimate's mark stays
   std::vector<float> mine;
   const float* src = sums;
-  if (part == -1 && c->world > 1) {
-    mine.resize((size_t)c->W * c->H * 4);
-    keepPart(c->W, c->H, c->rank, c->world, c->partMode, sums, mine.data());
+  if (part == -1 && c->share.world > 1) {
+    mine.resize((size_t)c->share.W * c->share.H * 4);
+    keepPart(c->share.W, c->share.H, c->share.rank, c->share.world, c->share.partMode, sums, mine.data());
     src = mine.data();
   }
-  HIPCHK(c, hipMemcpyAsync(c->accum, src, (size_t)c->W * c->H * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->accum, src, (size_t)c->share.W * c->share.H * sizeof(float4), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->k = k;
   // this rank's samples among 0 .. k-1 (every one, or those k' = rank mod world of a sample split)
-  c->samplesThisRank = planReduce(c->W, c->H, c->rank, c->world, c->partMode, k, 0).samples;
+  c->samplesThisRank = planReduce(c->share.W, c->share.H, c->share.rank, c->share.world, c->share.partMode, k, 0).samples;
   return SAIL_OK;
 }
 

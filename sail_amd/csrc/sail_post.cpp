@@ -13,7 +13,7 @@ namespace {
 // the a-trous passes' work buffers (sail_denoise and sail_temporal_filter share them), allocated on first use:
 // cvA | cvB | g0 (16 B each) | g1 (8 B) | var (4 B) | rgba8 (4 B) per pixel, then a count per 16x16 tile
 int ensureDenoiseWork(sail_ctx* c) {
-  const size_t nt = tiles16(c), np = (size_t)c->W * c->H;
+  const size_t nt = tiles16(c), np = (size_t)c->share.W * c->share.H;
   return allocOnce(c, &c->denoiseWork, np * 64 + nt * 4, "denoise work buffers");
 }
 
@@ -26,7 +26,7 @@ struct DenoiseWork {
   uint32_t* bad;
 };
 DenoiseWork denoiseWork(const sail_ctx* c) {
-  const size_t np = (size_t)c->W * c->H;
+  const size_t np = (size_t)c->share.W * c->share.H;
   char* base = (char*)c->denoiseWork;
   return {{(float4*)base, (float4*)(base + np * 16)}, (float4*)(base + np * 32), (float2*)(base + np * 48),
           (float*)(base + np * 56), (uint32_t*)(base + np * 60), (uint32_t*)(base + np * 64)};
@@ -40,7 +40,7 @@ template <class Prepare>
 hipError_t runAtrous(sail_ctx* c, const DenoiseWork& w, Prepare prepare, int iterations, float sigma_l, float sigma_x,
                      int display, float gamma_c, float* out_rgba, float* out_var, uint8_t* out_rgba8, float ms[8],
                      float* total, int* rc, const float4* alb = nullptr, float amin = 0.0f) {
-  const size_t np = (size_t)c->W * c->H;
+  const size_t np = (size_t)c->share.W * c->share.H;
   const int nev = iterations + 2;  // before the prepare pass, then after every pass
   PooledEvents ev(c, nev);
   if ((*rc = ev.rc)) return hipSuccess;
@@ -57,7 +57,7 @@ hipError_t runAtrous(sail_ctx* c, const DenoiseWork& w, Prepare prepare, int ite
     B.g0 = w.g0; B.g1 = w.g1;
     B.outVar = (last && out_var) ? w.var : nullptr;
     B.out8 = (last && out_rgba8) ? w.u8 : nullptr;
-    B.W = c->W; B.H = c->H;
+    B.W = c->share.W; B.H = c->share.H;
     B.step = 1 << it;
     B.last = last;
     B.sl2 = sigma_l * sigma_l;
@@ -89,7 +89,7 @@ hipError_t runAtrous(sail_ctx* c, const DenoiseWork& w, Prepare prepare, int ite
 // the three moment maps of a context that tracks them (sail_temporal_moments), zeroed on its stream
 hipError_t zeroMoments(sail_ctx* c) {
   if (!c->tpMom) return hipSuccess;
-  return hipMemsetAsync(c->tpMom, 0, (size_t)c->W * c->H * 48, c->stream);
+  return hipMemsetAsync(c->tpMom, 0, (size_t)c->share.W * c->share.H * 48, c->stream);
 }
 
 // nothing is pending for the next sail_temporal_begin any more (sail_move_objects)
@@ -158,7 +158,7 @@ int denoiseCall(sail_ctx* c, const char* who, bool demod, const sail_denoise_par
   memset(&A, 0, sizeof A);
   A.S = shownAccum(c); A.P = c->noiseMark; A.N = shownAovN(c); A.X = shownAovP(c);
   A.cv = w.cv[0]; A.g0 = w.g0; A.g1 = w.g1; A.tileBad = w.bad;
-  A.W = c->W; A.H = c->H;
+  A.W = c->share.W; A.H = c->share.H;
   A.mix = c->accumMode == SAIL_ACCUM_MIX;
   A.kf = (float)c->k; A.hf = (float)c->noiseK;
   float ms[8] = {}, total = 0.0f;
@@ -232,12 +232,12 @@ int temporalState(sail_ctx* c, const char* who) {
   return SAIL_OK;
 }
 
-uint32_t* temporalOut8(const sail_ctx* c) { return (uint32_t*)((char*)c->tpWork + (size_t)c->W * c->H * 80); }
-uint32_t* temporalCounts(const sail_ctx* c) { return temporalOut8(c) + (size_t)c->W * c->H; }
+uint32_t* temporalOut8(const sail_ctx* c) { return (uint32_t*)((char*)c->tpWork + (size_t)c->share.W * c->share.H * 80); }
+uint32_t* temporalCounts(const sail_ctx* c) { return temporalOut8(c) + (size_t)c->share.W * c->share.H; }
 
 int ensureTemporal(sail_ctx* c) {
   if (c->tpWork) return SAIL_OK;
-  const size_t np = (size_t)c->W * c->H;
+  const size_t np = (size_t)c->share.W * c->share.H;
   // five float4 maps (16 B each) | rgba8 (4 B) per pixel, then three counts per tile
   if (int rc = allocOnce(c, &c->tpWork, np * 84 + tiles16(c) * 12, "temporal maps")) return rc;
   float4* base = (float4*)c->tpWork;
@@ -248,13 +248,13 @@ int ensureTemporal(sail_ctx* c) {
 // the G-buffer pass's arguments for a view: the corner directions of a sample without jitter
 int gbufferArgs(sail_ctx* c, const char* who, const double mvp[16], const float eye[3], SailGbufferArgs* A) {
   float inv[16];
-  if (sail_jitter_inverse(mvp, 0.0, 0.0, c->W, c->H, inv) != SAIL_OK)
+  if (sail_jitter_inverse(mvp, 0.0, 0.0, c->share.W, c->share.H, inv) != SAIL_OK)
     return fail(c, SAIL_E_INVALID, "%s: the camera matrix is singular", who);
   memset(A, 0, sizeof *A);
-  A->prims = c->prims; A->n = c->n;
+  A->prims = c->prims; A->n = c->facts.n;
   cornerDirs(inv, eye, A->d);
   memcpy(A->eye, eye, sizeof A->eye);
-  A->W = c->W; A->H = c->H;
+  A->W = c->share.W; A->H = c->share.H;
   return SAIL_OK;
 }
 
@@ -277,7 +277,7 @@ int sail_gbuffer(sail_ctx* c, const double mvp[16], const float eye[3], float* r
   if (int rc = gbufferArgs(c, "sail_gbuffer", mvp, eye, &A)) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   if (int rc = sail_sync(c)) return rc;
-  const size_t np = (size_t)c->W * c->H;
+  const size_t np = (size_t)c->share.W * c->share.H;
   void* work = nullptr;  // G (16 B) | rays (24 B) | t (4 B) per pixel
   if (hipMalloc(&work, np * 44) != hipSuccess) return fail(c, SAIL_E_OOM, "G-buffer scratch");
   A.G = (float4*)work;
@@ -316,7 +316,7 @@ int sail_temporal_begin(sail_ctx* c, const double mvp[16], const float eye[3], c
   if (int rc = ensureTemporal(c)) return rc;
   const bool moved = c->tpMotionPending;
   if (moved) {  // before anything is committed: a begin that fails keeps it all
-    const int rows = c->n > 0 ? c->n : 1;
+    const int rows = c->facts.n > 0 ? c->facts.n : 1;
     if (int rc = growBuffer(c, &c->tpMotionDev, &c->tpMotionDevRows, rows, sizeof(float4) * (size_t)rows, "object motion table"))
       return rc;
   }
@@ -328,7 +328,7 @@ int sail_temporal_begin(sail_ctx* c, const double mvp[16], const float eye[3], c
     c->tpHavePrev = true;
     c->tpHaveCur = false;
   }
-  const size_t nt = tiles16(c), np = (size_t)c->W * c->H;
+  const size_t nt = tiles16(c), np = (size_t)c->share.W * c->share.H;
   uint32_t* cnt = temporalCounts(c);
   A.G = c->tpGcur;
   SailReprojectArgs B;
@@ -338,10 +338,10 @@ int sail_temporal_begin(sail_ctx* c, const double mvp[16], const float eye[3], c
   for (int j = 0; j < 4; j++) { B.Mp[0][j] = c->tpPrev.m[j]; B.Mp[1][j] = c->tpPrev.m[4 + j]; B.Mp[2][j] = c->tpPrev.m[12 + j]; }
   memcpy(B.eyePrev, c->tpPrev.eye, sizeof B.eyePrev);
   B.tol2 = p.pos_tol * p.pos_tol;
-  B.W = c->W; B.H = c->H;
+  B.W = c->share.W; B.H = c->share.H;
   B.haveHist = c->tpHavePrev;
   // an object motion is pending (sail_move_objects): the moved kernels, with the table uploaded ahead of them
-  B.motion = c->tpMotionDev; B.n = c->n; B.mc = c->tpMotionCap;
+  B.motion = c->tpMotionDev; B.n = c->facts.n; B.mc = c->tpMotionCap;
   c->tpResolved = false;
   // moment tracking: the same gather over Mhist, timed with the reproject pass
   const int nev = c->tpMom ? 4 : 3;
@@ -351,8 +351,8 @@ int sail_temporal_begin(sail_ctx* c, const double mvp[16], const float eye[3], c
   PooledEvents ev(c, nev);
   if (ev.rc) return ev.rc;
   hipError_t e = hipSuccess;
-  if (moved && c->n > 0)
-    e = hipMemcpyAsync(c->tpMotionDev, c->tpMotion.data(), sizeof(float4) * (size_t)c->n, hipMemcpyHostToDevice, c->stream);
+  if (moved && c->facts.n > 0)
+    e = hipMemcpyAsync(c->tpMotionDev, c->tpMotion.data(), sizeof(float4) * (size_t)c->facts.n, hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = hipEventRecord(ev[0], c->stream);
   if (e == hipSuccess) e = sail_launch_gbuffer(A, c->stream);
   if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
@@ -401,14 +401,14 @@ int sail_temporal_resolve(sail_ctx* c, const sail_temporal_params* params, float
     return fail(c, SAIL_E_STATE, "sail_temporal_resolve: no current view (sail_temporal_begin first; a new scene drops it)");
   HIPCHK(c, hipSetDevice(c->device));
   if (int rc = sail_sync(c)) return rc;
-  const size_t nt = tiles16(c), np = (size_t)c->W * c->H;
+  const size_t nt = tiles16(c), np = (size_t)c->share.W * c->share.H;
   uint32_t* cnt = temporalCounts(c);
   SailResolveArgs A;
   memset(&A, 0, sizeof A);
   A.S = shownAccum(c); A.R = c->tpR; A.Out = c->tpOut;
   A.out8 = out_rgba8 ? temporalOut8(c) : nullptr;
   A.tileHist = cnt + nt; A.tileBad = cnt + 2 * nt;
-  A.W = c->W; A.H = c->H;
+  A.W = c->share.W; A.H = c->share.H;
   A.mix = c->accumMode == SAIL_ACCUM_MIX;
   A.kf = (float)c->k;
   A.cap = p.cap; A.display = p.display; A.gammaC = p.gamma_c;
@@ -421,7 +421,7 @@ int sail_temporal_resolve(sail_ctx* c, const sail_temporal_params* params, float
     SailMomentResolveArgs M;
     memset(&M, 0, sizeof M);
     M.S = A.S; M.MR = c->tpMR; M.Mout = c->tpMout;
-    M.W = c->W; M.H = c->H; M.mix = A.mix; M.kf = A.kf; M.cap = A.cap;
+    M.W = c->share.W; M.H = c->share.H; M.mix = A.mix; M.kf = A.kf; M.cap = A.cap;
     e = sail_launch_moment_resolve(M, c->stream);
   }
   if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
@@ -457,7 +457,7 @@ int sail_temporal_read(sail_ctx* c, int which, float* out) {
   const float4* maps[5] = {c->tpGcur, c->tpGprev, c->tpHist, c->tpR, c->tpOut};
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(out, maps[which], (size_t)c->W * c->H * 16, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(out, maps[which], (size_t)c->share.W * c->share.H * 16, hipMemcpyDeviceToHost));
   return SAIL_OK;
 }
 
@@ -470,7 +470,7 @@ int sail_temporal_load_history(sail_ctx* c, const float* hist, const float* g, c
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (int rc = ensureTemporal(c)) return rc;
-  const size_t bytes = (size_t)c->W * c->H * 16;
+  const size_t bytes = (size_t)c->share.W * c->share.H * 16;
   HIPCHK(c, hipMemcpy(c->tpHist, hist, bytes, hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(c->tpGprev, g, bytes, hipMemcpyHostToDevice));
   for (int i = 0; i < 16; i++) c->tpPrev.m[i] = (float)mvp_prev[i];
@@ -489,7 +489,7 @@ int sail_temporal_load_history(sail_ctx* c, const float* hist, const float* g, c
 int sail_temporal_pending_motion(sail_ctx* c, float* motion, float* hist_cap, int* pending) {
   if (!c) return SAIL_E_INVALID;
   if (!c->subs.empty()) return relay(c, sail_temporal_pending_motion(c->subs[0], motion, hist_cap, pending), c->subs[0]);
-  for (int r = 0; motion && r < c->n; r++)
+  for (int r = 0; motion && r < c->facts.n; r++)
     for (int j = 0; j < 3; j++) motion[r * 3 + j] = c->tpMotionPending ? c->tpMotion[(size_t)r * 4 + j] : 0.0f;
   if (hist_cap) *hist_cap = c->tpMotionPending ? c->tpMotionCap : INFINITY;
   if (pending) *pending = c->tpMotionPending ? 1 : 0;
@@ -511,7 +511,7 @@ int sail_temporal_moments(sail_ctx* c, int on) {
     return SAIL_OK;
   }
   if (c->tpMom) return SAIL_OK;
-  const size_t np = (size_t)c->W * c->H;
+  const size_t np = (size_t)c->share.W * c->share.H;
   // three float4 maps (16 B each) per pixel, then the filter's count of temporal pixels per tile
   if (int rc = allocOnce(c, &c->tpMom, np * 48 + tiles16(c) * 4, "moment maps")) return rc;
   float4* base = (float4*)c->tpMom;
@@ -531,7 +531,7 @@ int sail_temporal_load_moments(sail_ctx* c, const float* mom) {
     return fail(c, SAIL_E_STATE, "sail_temporal_load_moments: needs a committed history and no current view (right after sail_temporal_load_history)");
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(c->tpMhist, mom, (size_t)c->W * c->H * 16, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->tpMhist, mom, (size_t)c->share.W * c->share.H * 16, hipMemcpyHostToDevice));
   return SAIL_OK;
 }
 
@@ -549,7 +549,7 @@ int sail_temporal_read_moments(sail_ctx* c, int which, float* out) {
   const float4* maps[3] = {c->tpMhist, c->tpMR, c->tpMout};
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(out, maps[which], (size_t)c->W * c->H * 16, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(out, maps[which], (size_t)c->share.W * c->share.H * 16, hipMemcpyDeviceToHost));
   return SAIL_OK;
 }
 
@@ -604,7 +604,7 @@ int tfilterCall(sail_ctx* c, const char* who, bool demod, const sail_tfilter_par
     return fail(c, SAIL_E_STATE, "%s: no albedo map (sail_albedo or sail_albedo_load first; new rows drop it)", who);
   if (demod && memcmp(&c->albView, &c->tpCur, sizeof c->albView) != 0)
     return fail(c, SAIL_E_STATE, "%s: the albedo map belongs to another view than the current temporal view", who);
-  const size_t nt = tiles16(c), np = (size_t)c->W * c->H;
+  const size_t nt = tiles16(c), np = (size_t)c->share.W * c->share.H;
   if (int rc = ensureDenoiseWork(c)) return rc;
   const DenoiseWork w = denoiseWork(c);  // sail_denoise's work buffers; the count of temporal pixels sits behind the moments
   uint32_t* dTmp = (uint32_t*)((char*)c->tpMom + np * 48);
@@ -612,7 +612,7 @@ int tfilterCall(sail_ctx* c, const char* who, bool demod, const sail_tfilter_par
   memset(&A, 0, sizeof A);
   A.Out = c->tpOut; A.Mout = c->tpMout; A.S = shownAccum(c); A.N = shownAovN(c); A.X = shownAovP(c);
   A.cv = w.cv[0]; A.g0 = w.g0; A.g1 = w.g1; A.tileBad = w.bad; A.tileTemporal = dTmp;
-  A.W = c->W; A.H = c->H;
+  A.W = c->share.W; A.H = c->share.H;
   A.mix = c->accumMode == SAIL_ACCUM_MIX;
   A.kf = (float)c->k;
   A.minHist = p.min_hist;
@@ -645,11 +645,11 @@ int tfilterCall(sail_ctx* c, const char* who, bool demod, const sail_tfilter_par
   return SAIL_OK;
 }
 
-uint32_t* albedoCounts(const sail_ctx* c) { return (uint32_t*)(c->albMap + (size_t)c->W * c->H); }
+uint32_t* albedoCounts(const sail_ctx* c) { return (uint32_t*)(c->albMap + (size_t)c->share.W * c->share.H); }
 
 // the albedo map and its two counts per tile, allocated on first use
 int ensureAlbedo(sail_ctx* c) {
-  return allocOnce(c, &c->albMap, (size_t)c->W * c->H * 16 + tiles16(c) * 8, "albedo map");
+  return allocOnce(c, &c->albMap, (size_t)c->share.W * c->share.H * 16 + tiles16(c) * 8, "albedo map");
 }
 
 void albedoView(sail_ctx* c, const double mvp[16], const float eye[3]) {
@@ -684,14 +684,14 @@ int sail_albedo(sail_ctx* c, const double mvp[16], const float eye[3], int grid,
   HIPCHK(c, hipSetDevice(c->device));
   if (int rc = sail_sync(c)) return rc;
   if (int rc = ensureAlbedo(c)) return rc;
-  const size_t nt = tiles16(c), np = (size_t)c->W * c->H;
+  const size_t nt = tiles16(c), np = (size_t)c->share.W * c->share.H;
   SailAlbedoArgs A;
   memset(&A, 0, sizeof A);
-  A.prims = c->prims; A.texparams = c->tp; A.n = c->n; A.tn = c->tn;
-  A.texMask = c->plugins.texture_mask;
+  A.prims = c->prims; A.texparams = c->tp; A.n = c->facts.n; A.tn = c->facts.tn;
+  A.texMask = c->facts.plugins.texture_mask;
   memcpy(A.d, G.d, sizeof A.d);
   memcpy(A.eye, eye, sizeof A.eye);
-  A.W = c->W; A.H = c->H; A.grid = grid;
+  A.W = c->share.W; A.H = c->share.H; A.grid = grid;
   A.A = c->albMap;
   A.tileHit = albedoCounts(c); A.tilePartial = A.tileHit + nt;
   c->albHave = false;  // a call that fails leaves no map
@@ -726,7 +726,7 @@ int sail_albedo_load(sail_ctx* c, const float* map, const double mvp[16], const 
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (int rc = ensureAlbedo(c)) return rc;
-  HIPCHK(c, hipMemcpy(c->albMap, map, (size_t)c->W * c->H * 16, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->albMap, map, (size_t)c->share.W * c->share.H * 16, hipMemcpyHostToDevice));
   albedoView(c, mvp, eye);
   c->albHave = true;
   return SAIL_OK;
@@ -740,7 +740,7 @@ int sail_albedo_read(sail_ctx* c, float* out) {
     return fail(c, SAIL_E_STATE, "sail_albedo_read: no albedo map (sail_albedo or sail_albedo_load first; new rows drop it)");
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(out, c->albMap, (size_t)c->W * c->H * 16, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(out, c->albMap, (size_t)c->share.W * c->share.H * 16, hipMemcpyDeviceToHost));
   return SAIL_OK;
 }
 
