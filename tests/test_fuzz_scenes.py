@@ -32,9 +32,15 @@ W, H, SPP, B = 24, 16, 3, 6
 
 
 def bit_equal(a, b):
-    a = np.ascontiguousarray(a, dtype=np.float32)
-    b = np.ascontiguousarray(b, dtype=np.float32)
-    return (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
+    """Raw uint32 equality: a NaN equals only the same NaN, sign and payload. One case is admitted by name: the default
+    NaN (quiet, payload 0: 0x7fc00000 or 0xffc00000), whose sign may differ. It is what an invalid operation (0 * inf,
+    0 / 0, inf - inf) creates, and IEEE 754 leaves its sign to the implementation: x86 SSE sets it, the GPU and most
+    JS engines clear it, so the C++ oracle, its JS twin and the kernels cannot agree on it by arithmetic. A NaN that
+    carries a payload (a scene row's, propagated) must match in every bit."""
+    a = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+    b = np.ascontiguousarray(b, dtype=np.float32).view(np.uint32)
+    default_nan = ((a & 0x7FFFFFFF) == 0x7FC00000) & ((b & 0x7FFFFFFF) == 0x7FC00000)
+    return (a == b) | default_nan
 
 
 def schedule(sc, w, h, spp):

@@ -232,9 +232,12 @@ def _hostile(fixtures, which):
     return _variant(fixtures, rows=r, tp=tp)
 
 
+HOSTILE = ["neg_zero_bound_zero_radius_kd0", "negative_radius_nan_emission_kd_inf", "infinite_radius", "nan_centre",
+           "denormal_radius"]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("which", ["neg_zero_bound_zero_radius_kd0", "negative_radius_nan_emission_kd_inf", "infinite_radius",
-                                   "nan_centre", "denormal_radius"])
+@pytest.mark.parametrize("which", HOSTILE)
 def test_hostile_rows(gpu, fixtures, which):
     _check_both_tiers(_hostile(fixtures, which))
 

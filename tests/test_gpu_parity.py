@@ -433,13 +433,18 @@ def test_sample_groups(gpu, fixtures, monkeypatch, name, groups, mode):
 
 # ---- category words outside the compiled sets (unknown, negative, NaN, huge): the zero material / texture paths,
 # through the host-evaluated SailPrim.cats -------------------------------------------------------------------------
-def test_odd_category_words(gpu, fixtures):
+def odd_category_scene(fixtures):
     sc = dict(fixtures["scenes"]["ALL"])
     tp = list(sc["texparams"])
     odd = [99.0, -5.0, float("nan"), 3e9, 31.0]
     for i, row in enumerate(range(0, sc["tn"], 2)):
         tp[row * 16] = odd[i % len(odd)]
     sc["texparams"] = tp
+    return sc
+
+
+def test_odd_category_words(gpu, fixtures):
+    sc = odd_category_scene(fixtures)
     got, want, st, segs, _, _ = _render_both({"scenes": {"ODD": sc}}, "ODD", 24, 20, 3, 6, launch=2)
     assert bit_equal(got, want).all()
     assert st.segments == segs
@@ -514,11 +519,16 @@ VIEWS = [("inside sphere", [2.0, 1.25, 2.7], [2.78, 2.73, 2.79]),
          ("outside", [2.78, 2.73, -20.0], [2.78, 2.73, 2.79])]
 
 
-@pytest.mark.parametrize("label,eye,center", VIEWS)
-def test_unusual_viewpoints(gpu, fixtures, label, eye, center):
+def view_scene(fixtures, eye, center):
     sc = dict(fixtures["scenes"]["C1"])
     sc["eye"] = eye
     sc["mvp_rowmajor"] = capi.camera(eye, center, [0, 1, 0], 55.0, 1.0, 1.0, 100.0).tolist()
+    return sc
+
+
+@pytest.mark.parametrize("label,eye,center", VIEWS)
+def test_unusual_viewpoints(gpu, fixtures, label, eye, center):
+    sc = view_scene(fixtures, eye, center)
     got, want, st, segs, gaov, waov = _render_both({"scenes": {"V": sc}}, "V", 33, 21, 3, 6, aov=True, launch=2)
     assert bit_equal(got, want).all(), label
     assert bit_equal(gaov[0], waov[0]).all() and bit_equal(gaov[1], waov[1]).all(), label
@@ -589,13 +599,18 @@ LAST_BOUNCE_MATS = {
 }
 
 
-@pytest.mark.parametrize("variant", sorted(LAST_BOUNCE_MATS))
-@pytest.mark.parametrize("B", [1, 3])
-def test_last_bounce_shortcut_edge_materials(gpu, fixtures, variant, B):
+def last_bounce_scene(fixtures, variant):
     sc = dict(fixtures["scenes"]["C1"])
     tp = np.array(sc["texparams"], dtype=np.float32).reshape(sc["tn"], 16)
     LAST_BOUNCE_MATS[variant](tp)
     sc["texparams"] = tp.reshape(-1).tolist()
+    return sc
+
+
+@pytest.mark.parametrize("variant", sorted(LAST_BOUNCE_MATS))
+@pytest.mark.parametrize("B", [1, 3])
+def test_last_bounce_shortcut_edge_materials(gpu, fixtures, variant, B):
+    sc = last_bounce_scene(fixtures, variant)
     W, H, spp = 24, 20, 3
     inv, seeds = capi.schedule(np.array(sc["mvp_rowmajor"]), W, H, 0, spp)
     ctx = capi.Context(W, H)

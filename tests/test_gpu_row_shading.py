@@ -216,31 +216,43 @@ def test_row_material_edges(gpu, fixtures, row, what):
     _check_arms(sc, mask)
 
 
+def row_variant(fixtures, which):
+    """the row variants of the three tests below (tests/parity_cases.py lists them by these names)"""
+    r = _rows(fixtures)
+    if which == "cube_reversed":
+        r[CUBE][7] = 1.0  # rev
+    elif which == "categories_swapped":
+        r[SPHERE][MATROW[SPHERE]], r[CUBE][MATROW[CUBE]] = r[CUBE][MATROW[CUBE]], r[SPHERE][MATROW[SPHERE]]
+    elif which == "two_spheres":
+        a, b = r[SPHERE].copy(), r[SPHERE].copy()
+        a[1:5] = (1.6, 1.0, 2.2, 0.9)
+        b[1:5] = (3.9, 3.6, 1.4, 0.8)
+        b[MATROW[SPHERE]] = 0.0              # matte
+        b[EMISSION[SPHERE]] = (6.0, 5.0, 4.0)  # the light
+        return _variant(fixtures, rows=np.stack([a, r[CORNELL], b]))
+    else:
+        raise KeyError(which)
+    return _variant(fixtures, rows=r)
+
+
+ROW_VARIANTS = ["cube_reversed", "categories_swapped", "two_spheres"]
+
+
 @pytest.mark.gpu
 def test_cube_reversed(gpu, fixtures):
-    r = _rows(fixtures)
-    r[CUBE][7] = 1.0  # rev
-    _check_arms(_variant(fixtures, rows=r), 6)
+    _check_arms(row_variant(fixtures, "cube_reversed"), 6)
 
 
 @pytest.mark.gpu
 def test_categories_swapped(gpu, fixtures):
     """the sphere a matte (the light's material row), the light cube a mirror (the sphere's)"""
-    r = _rows(fixtures)
-    r[SPHERE][MATROW[SPHERE]], r[CUBE][MATROW[CUBE]] = r[CUBE][MATROW[CUBE]], r[SPHERE][MATROW[SPHERE]]
-    _check_arms(_variant(fixtures, rows=r), 6)
+    _check_arms(row_variant(fixtures, "categories_swapped"), 6)
 
 
 # ---- 4. two rows of one type with different materials must not share a copy -------------------------------------------
 @pytest.mark.gpu
 def test_two_spheres_one_mirror_one_emitting_matte(gpu, fixtures):
-    r = _rows(fixtures)
-    a, b = r[SPHERE].copy(), r[SPHERE].copy()
-    a[1:5] = (1.6, 1.0, 2.2, 0.9)
-    b[1:5] = (3.9, 3.6, 1.4, 0.8)
-    b[MATROW[SPHERE]] = 0.0              # matte
-    b[EMISSION[SPHERE]] = (6.0, 5.0, 4.0)  # the light
-    _check_arms(_variant(fixtures, rows=np.stack([a, r[CORNELL], b])), 3)
+    _check_arms(row_variant(fixtures, "two_spheres"), 3)
 
 
 # ---- 5. above kRowRecordMax: no row-shading form, and the value tier still loads -----------------------------------------

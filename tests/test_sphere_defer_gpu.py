@@ -50,6 +50,50 @@ def _variant(fixtures, rows):
     return sc
 
 
+def _two_spheres(fixtures):
+    r = _rows(fixtures)
+    a, b = r[SPHERE].copy(), r[SPHERE].copy()
+    a[1:5] = (1.6, 1.0, 2.2, 0.9)
+    b[1:5] = (3.9, 3.6, 1.4, 0.8)
+    b[MATROW_SPHERE] = 0.0                 # matte
+    b[EMISSION_SPHERE] = (6.0, 5.0, 4.0)   # a light
+    return r, a, b
+
+
+def row_variant(fixtures, which):
+    """the row variants of C1 that the tests below render (tests/parity_cases.py lists them by these names)"""
+    r = _rows(fixtures)
+    if which in ("sphere_row0", "sphere_row1"):
+        return _variant(fixtures, r[[SPHERE, CUBE, CORNELL] if which == "sphere_row0" else [CUBE, SPHERE, CORNELL]])
+    if which == "no_cornellbox":
+        return _variant(fixtures, r[[CUBE, SPHERE]])
+    if which == "around_the_eye_and_the_box":
+        r[SPHERE][1:5] = (2.78, 2.73, 0.0, 40.0)
+    elif which == "half_through_the_floor":
+        r[SPHERE][2] = 0.0  # centre y: the floor
+    elif which == "half_behind_the_light":  # the light is the slab x 2.13..3.43, y 5.487..5.488, z 2.27..3.32 under the ceiling
+        r[SPHERE][1:5] = (2.78, 5.3, 2.8, 0.45)
+    elif which in ("two_spheres_mirror", "two_spheres_emitter", "four_rows"):
+        r, a, b = _two_spheres(fixtures)
+        rows = {"two_spheres_mirror": [a, r[CORNELL], b], "two_spheres_emitter": [b, r[CORNELL], a],
+                "four_rows": [r[CUBE], r[CORNELL], a, b]}[which]
+        return _variant(fixtures, np.stack(rows))
+    elif which == "radius_zero":
+        r[SPHERE][4] = 0.0
+    elif which == "radius_nan":
+        r[SPHERE][4] = _f32(0x7fc00abc)
+    elif which == "centre_inf":
+        r[SPHERE][1] = np.inf
+    else:
+        raise KeyError(which)
+    return _variant(fixtures, r)
+
+
+ROW_VARIANTS = ["sphere_row0", "sphere_row1", "no_cornellbox", "around_the_eye_and_the_box", "half_through_the_floor",
+                "half_behind_the_light", "two_spheres_mirror", "two_spheres_emitter", "four_rows", "radius_zero", "radius_nan",
+                "centre_inf"]
+
+
 def _schedule(sc, w=W, h=H):
     return capi.schedule(np.array(sc["mvp_rowmajor"]), w, h, 0, SPP)
 
@@ -122,9 +166,9 @@ def test_bounce_counts(gpu, fixtures, bounces):
 
 # ---- 3. the sphere's row index: the tie rule (t == best and the lower row) from both sides -------------------------------
 @pytest.mark.gpu
-@pytest.mark.parametrize("order", [[SPHERE, CUBE, CORNELL], [CUBE, SPHERE, CORNELL]], ids=["sphere_row0", "sphere_row1"])
+@pytest.mark.parametrize("order", ["sphere_row0", "sphere_row1"])
 def test_row_order(gpu, fixtures, order):
-    _check_arms(_variant(fixtures, _rows(fixtures)[order]))
+    _check_arms(row_variant(fixtures, order))
 
 
 # ---- 4. candidates whose provisional result is a miss --------------------------------------------------------------------
@@ -132,8 +176,7 @@ def test_row_order(gpu, fixtures, order):
 def test_no_cornellbox(gpu, fixtures):
     """the light cube and the sphere alone, seen from outside: a candidate that misses the sphere after all has no winner
     and ends after the gather; one that hits it goes on from a provisional miss"""
-    r = _rows(fixtures)
-    on = _check_arms(_variant(fixtures, r[[CUBE, SPHERE]]))
+    on = _check_arms(row_variant(fixtures, "no_cornellbox"))
     assert (on[..., :3] != 0).any()  # the mirror shows the light
 
 
@@ -141,45 +184,26 @@ def test_no_cornellbox(gpu, fixtures):
 @pytest.mark.gpu
 def test_sphere_around_the_eye_and_the_box(gpu, fixtures):
     """every ray starts inside (cc < 0, t1 < kEps) and is a candidate; the box is nearer everywhere"""
-    r = _rows(fixtures)
-    r[SPHERE][1:5] = (2.78, 2.73, 0.0, 40.0)
-    _check_arms(_variant(fixtures, r))
+    _check_arms(row_variant(fixtures, "around_the_eye_and_the_box"))
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("where", ["half_through_the_floor", "half_behind_the_light"])
 def test_sphere_partly_hidden(gpu, fixtures, where):
-    r = _rows(fixtures)
-    if where == "half_through_the_floor":
-        r[SPHERE][2] = 0.0  # centre y: the floor
-    else:  # the light is the slab x 2.13..3.43, y 5.487..5.488, z 2.27..3.32 under the ceiling
-        r[SPHERE][1:5] = (2.78, 5.3, 2.8, 0.45)
-    _check_arms(_variant(fixtures, r))
+    _check_arms(row_variant(fixtures, where))
 
 
 # ---- 6. more than one sphere: the first is deferred, the second tested in the sweep --------------------------------------
-def _two_spheres(fixtures):
-    r = _rows(fixtures)
-    a, b = r[SPHERE].copy(), r[SPHERE].copy()
-    a[1:5] = (1.6, 1.0, 2.2, 0.9)
-    b[1:5] = (3.9, 3.6, 1.4, 0.8)
-    b[MATROW_SPHERE] = 0.0                 # matte
-    b[EMISSION_SPHERE] = (6.0, 5.0, 4.0)   # a light
-    return r, a, b
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("first", ["mirror", "emitter"])  # which of the two is deferred; the other is tested in the sweep
 def test_two_spheres_with_the_box(gpu, fixtures, first):
-    r, a, b = _two_spheres(fixtures)
-    _check_arms(_variant(fixtures, np.stack([a, r[CORNELL], b] if first == "mirror" else [b, r[CORNELL], a])))
+    _check_arms(row_variant(fixtures, "two_spheres_" + first))
 
 
 @pytest.mark.gpu
 def test_four_rows(gpu, fixtures):
     """above kRowRecordMax: no row-shading form, one generic record; the deferral rides on the value kernel all the same"""
-    r, a, b = _two_spheres(fixtures)
-    sc = _variant(fixtures, np.stack([r[CUBE], r[CORNELL], a, b]))
+    sc = row_variant(fixtures, "four_rows")
     assert "SAIL_JIT_ROWSHADE" not in capi.jit_value_key(sc, jit=ON)[1]
     _check_arms(sc)
 
@@ -188,14 +212,7 @@ def test_four_rows(gpu, fixtures):
 @pytest.mark.gpu
 @pytest.mark.parametrize("what", ["radius_zero", "radius_nan", "centre_inf"])
 def test_degenerate_sphere(gpu, fixtures, what):
-    r = _rows(fixtures)
-    if what == "radius_zero":
-        r[SPHERE][4] = 0.0
-    elif what == "radius_nan":
-        r[SPHERE][4] = _f32(0x7fc00abc)
-    else:
-        r[SPHERE][1] = np.inf
-    _check_arms(_variant(fixtures, r))
+    _check_arms(row_variant(fixtures, what))
 
 
 # ---- 8. the other instances of the kernel --------------------------------------------------------------------------------
