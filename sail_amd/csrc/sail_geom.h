@@ -107,9 +107,14 @@ D bool quadratic(float A, float B, float C, float& t0, float& t1) {
   return quadratic<0>(A, B, C, t0, t1, discrim);
 }
 
+// A path segment: origin and direction. It is what the path loop carries from bounce to bounce, what the packed path
+// state moves through LDS, and all that a hit record or the shading reads of a ray.
+struct Seg { V3 o, d; };
 // A ray carries the reciprocals of its direction: every slab test divides by the same three components, and
 // under the GLSL division spec a / d.x is a * RN(1/d.x), so a slab is six subtractions and six multiplies.
-struct Ray { V3 o, d; float rx, ry, rz; };
+// In the flat forms it is built (mkRay) where it is swept and lives no longer than the sweep; the pre-cull form carries
+// it (PathRay below).
+struct Ray : Seg { float rx, ry, rz; };
 D Ray mkRay(V3 o, V3 d) {
   Ray r; r.o = o; r.d = d;
   // one range guard for the three components (rcp_rn guards each)
@@ -125,6 +130,23 @@ D Ray mkRay(V3 o, V3 d) {
   }
   return r;
 }
+// What a path carries from bounce to bounce, by kernel form (traceTileCompact):
+//  * flat forms (Cornell, room, all-plugin): the segment alone. The reciprocals are built inside the sweep's `if (alive)`
+//    and die there, so the sort and the shading hold no registers for them and nothing zeroes them (value kernel of
+//    the Cornell box: 161 VALU and 18 v_rcp_f32 fewer in the code, 1 spilled VGPR fewer; C2 +0.8 % on top of the
+//    all-lane gather, C5 +1.8 % and C3 +0.5 % with it: DESIGN.md, round 19). The same rcp_rn of the same three values
+//    once per traced segment; the last bounce's shading no longer computes a dead ray's.
+//  * pre-cull form: the ray with its reciprocals, built by the shading (mkRay) and zeroed after the gather, as before.
+//    Its kernel spills 80 VGPRs as it is, and the segment form raised that to 98 and lost 0.75 % on C4 (spread 0.6 %).
+// One text serves both through these overloads: the segment's next value, the ray to sweep, the end of the reciprocals.
+template <bool CARRY_RCP> struct PathRay { using type = Seg; };
+template <> struct PathRay<true> { using type = Ray; };
+D void nextRay(Seg& r, V3 o, V3 d) { r.o = o; r.d = d; }
+D void nextRay(Ray& r, V3 o, V3 d) { r = mkRay(o, d); }
+D Ray sweptRay(const Seg& r) { return mkRay(r.o, r.d); }
+D const Ray& sweptRay(const Ray& r) { return r; }
+D void dropRcp(Seg&) {}
+D void dropRcp(Ray& r) { r.rx = r.ry = r.rz = 0.0f; }  // not used past the sweep: the next ray is rebuilt by mkRay
 struct Hit {
   float d; V3 hit, normal, dpdu, dpdv; bool into; int matRow; V3 sc, emission; int matCategory;
   float nd;  // dot(geometric normal before the into flip, ray direction)
@@ -333,7 +355,7 @@ D void dpdBox(V3 normal, V3& dpdu, V3& dpdv) {
   else dpdu = v3(fma_(n.y, 0.0f, -n.z), fma_(n.z, 0.0f, n.x * -0.0f), fma_(n.y, -0.0f, n.x));
   dpdv = cross(normal, dpdu);
 }
-D void cubeHit(const Ctx& c, const SailPrim& p, const Ray& r, float t, Hit& h) {
+D void cubeHit(const Ctx& c, const SailPrim& p, const Seg& r, float t, Hit& h) {
   h.hit = r.o + t * r.d;
   h.normal = normalForCube(r.o + t * r.d, p);
   dpdBox(h.normal, h.dpdu, h.dpdv);
@@ -352,7 +374,7 @@ D void cubeHit(const Ctx& c, const SailPrim& p, const Ray& r, float t, Hit& h) {
 // both (z < t excludes z > t; after it the colour test is made as written). Same values, each face test once:
 // 1 = one branch chain, 2 = branch-free selects. Bit-identical but slower (C2 -4.7 % / -3.8 %: more constant moves per
 // branch and more spills), so the default keeps the reference's two chains.
-D void cornellHit(const SailPrim& p, const Ray& r, float t, Hit& h) {
+D void cornellHit(const SailPrim& p, const Seg& r, float t, Hit& h) {
   h.hit = r.o + t * r.d;
   h.normal = -normalForCornellbox(r.o + t * r.d, p);
   dpdBox(h.normal, h.dpdu, h.dpdv);
@@ -370,7 +392,7 @@ D void cornellHit(const SailPrim& p, const Ray& r, float t, Hit& h) {
 // Cornellbox's is -n == -1 * n bit for bit (zeros included); only the surface colour differs (texture vs wall chain).
 // Measured (bit-identical, profiles/r03_variants_box_unified*.jsonl): room kernel C3 +0.7 %; every kernel C2 -0.8 %,
 // C4 +0.1 %; only in mixed waves C2 +-0.2 %, C3 -0.7 %, so the room kernel alone takes it.
-D void boxHit(const Ctx& c, const SailPrim& p, const Ray& r, float t, Hit& h, bool cornell) {
+D void boxHit(const Ctx& c, const SailPrim& p, const Seg& r, float t, Hit& h, bool cornell) {
   h.hit = r.o + t * r.d;
   const float s = cornell ? -1.0f : sgn(p.rev);
   h.normal = s * normalForCornellbox(r.o + t * r.d, p);
@@ -1126,10 +1148,10 @@ D Sweep sweepRayDefer(const Ctx& c, const Ray& r, bool defer, bool& cand) {
   return sw;
 }
 // A gathered candidate's tail, on the ray it was sorted with: the head's expressions again (the packed path state
-// carries the ray, not a, b, cc), the ray's reciprocals again (mkRay: the gather leaves them out), then the tail. The
+// carries the segment, not a, b, cc), the ray's reciprocals again (mkRay: the path carries none), then the tail. The
 // sphere wins iff the in-order sweep would have taken it: nearer than the provisional winner, or as near with a
 // lower row index (the candidate sweep's rule for a row visited out of order, candType).
-D void sphereResolve(const Ctx& c, const Ray& r, Sweep& sw) {
+D void sphereResolve(const Ctx& c, const Seg& r, Sweep& sw) {
   const SailPrim& p = PRIM(c, kDeferRow);
   const Ray rr = mkRay(r.o, r.d);
   // the discriminant is the sweep's, bit for bit (the same operations on the same operands): not negative, so the whole
@@ -1143,11 +1165,11 @@ D void sphereResolve(const Ctx& c, const Ray& r, Sweep& sw) {
 // hit = o + t * d on the same local o and d (W2L of the ray for the quadrics and the disk, the rectangle's frame), so
 // this is the sweep's own value bit for bit -- the compacting kernels recompute it instead of moving it through LDS
 // (packed path state, traceTileCompact).
-D V3 quadLocalHit(const SailPrim& p, const Ray& r, float t) {
+D V3 quadLocalHit(const SailPrim& p, const Seg& r, float t) {
   const V3 d = W2L(r.d), o = W2L(r.o - P3(p, 0));
   return o + t * d;
 }
-D V3 rectLocalHit(const SailPrim& p, const Ray& r, float t) {
+D V3 rectLocalHit(const SailPrim& p, const Seg& r, float t) {
   const RectFrame f = rectFrame(p);
   const V3 d = worldToLocal(r.d, f.normal, f.ss, f.ts);
   const V3 o = worldToLocal(r.o - P3(p, 0), f.normal, f.ss, f.ts);
@@ -1155,7 +1177,7 @@ D V3 rectLocalHit(const SailPrim& p, const Ray& r, float t) {
 }
 // BOXU: the room family's one box record for Cube and Cornellbox (boxHit)
 template <bool RECOMP_HL = false, bool BOXU = false>
-D Hit hitRecord(const Ctx& c, const Ray& r, const Sweep& sw) {
+D Hit hitRecord(const Ctx& c, const Seg& r, const Sweep& sw) {
   const float best = sw.best;
   const int bi = sw.bi;
   Hit h;
@@ -1214,7 +1236,7 @@ D Hit hitRecord(const Ctx& c, const Ray& r, const Sweep& sw) {
 constexpr int kRowRecordMax = 3;
 // the record of row I for the lanes whose winner it is: pick by the scalar row index (U) or per lane
 template <int I, bool U, bool RECOMP_HL, bool BOXU>
-D void hitRecordRows(const Ctx& c, const Ray& r, const Sweep& sw, int b0, Hit& h) {
+D void hitRecordRows(const Ctx& c, const Seg& r, const Sweep& sw, int b0, Hit& h) {
   if constexpr (I + 1 < kRows) {
     if ((U ? b0 : sw.bi) != I) { hitRecordRows<I + 1, U, RECOMP_HL, BOXU>(c, r, sw, b0, h); return; }
   }
@@ -1224,7 +1246,7 @@ D void hitRecordRows(const Ctx& c, const Ray& r, const Sweep& sw, int b0, Hit& h
 }
 #endif
 template <bool RECOMP_HL = false, bool BOXU = false>
-D Hit hitRecordU(const Ctx& c, const Ray& r, const Sweep& sw) {
+D Hit hitRecordU(const Ctx& c, const Seg& r, const Sweep& sw) {
   const int b0 = __builtin_amdgcn_readfirstlane(sw.bi);
 #if SAIL_ROWVALS
   if constexpr (kRows <= kRowRecordMax) {
@@ -1262,7 +1284,7 @@ static_assert(kRowQuietMask == 0u || SAIL_JIT_KL == 0u, "quiet rows: no light pl
 static_assert((kRowQuietMask & ~kRowShadeMask) == 0u, "quiet rows are rows with a copy of their own");
 template <bool Q> struct QuietTag { static constexpr bool value = Q; };
 template <int I, bool RECOMP_HL, bool BOXU, class Rest>
-D bool bounceRows(const Ctx& c, const Ray& r, const Sweep& sw, int b0, Hit& h, Rest&& rest) {
+D bool bounceRows(const Ctx& c, const Seg& r, const Sweep& sw, int b0, Hit& h, Rest&& rest) {
   if constexpr (I + 1 < kRows) {
     if (b0 != I) return bounceRows<I + 1, RECOMP_HL, BOXU>(c, r, sw, b0, h, rest);
   }
@@ -1276,7 +1298,7 @@ D bool bounceRows(const Ctx& c, const Ray& r, const Sweep& sw, int b0, Hit& h, R
   return false;
 }
 template <bool RECOMP_HL, bool BOXU, class Rest>
-D void bounceU(const Ctx& c, const Ray& r, const Sweep& sw, Rest&& rest) {
+D void bounceU(const Ctx& c, const Seg& r, const Sweep& sw, Rest&& rest) {
   const int b0 = __builtin_amdgcn_readfirstlane(sw.bi);
   Hit h;
   if (__all(sw.bi == b0)) {

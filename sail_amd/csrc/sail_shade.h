@@ -444,20 +444,23 @@ D bool shadeLast(const Ctx& c, const Hit& ins, float seed, const V3& fpdf, V3& e
 struct ShadowPending { bool pending; V3 toLight, hit, eLit; };
 // DEFER: a lit matte path's shadow ray is handed to onShadow(hit, toLight, eLit) where it is made (so that nothing of it
 // stays live through the rest of the bounce) and e takes the blocked outcome
-template <bool DEFER, class OnShadow>
-D void shadeBounceT(const Ctx& c, const Hit& ins, Ray& ray, float seed, V3& fpdf, V3& e, PhaseClock& pc, OnShadow&& onShadow);
-D void shadeBounce(const Ctx& c, const Hit& ins, Ray& ray, float seed, V3& fpdf, V3& e, PhaseClock& pc) {
+// R: what the path carries, a Seg or a Ray (PathRay, sail_geom.h); the bounce ends with nextRay
+template <bool DEFER, class R, class OnShadow>
+D void shadeBounceT(const Ctx& c, const Hit& ins, R& ray, float seed, V3& fpdf, V3& e, PhaseClock& pc, OnShadow&& onShadow);
+template <class R>
+D void shadeBounce(const Ctx& c, const Hit& ins, R& ray, float seed, V3& fpdf, V3& e, PhaseClock& pc) {
   shadeBounceT<false>(c, ins, ray, seed, fpdf, e, pc, [](const V3&, const V3&, const V3&) {});
 }
 // the deferred shadow ray into a ShadowPending (the pre-cull kernel's compacted shadow rays, the wavefront split)
-D void shadeBounceP(const Ctx& c, const Hit& ins, Ray& ray, float seed, V3& fpdf, V3& e, PhaseClock& pc, ShadowPending& sp) {
+template <class R>
+D void shadeBounceP(const Ctx& c, const Hit& ins, R& ray, float seed, V3& fpdf, V3& e, PhaseClock& pc, ShadowPending& sp) {
   sp.pending = false;
   shadeBounceT<true>(c, ins, ray, seed, fpdf, e, pc, [&](const V3& hit, const V3& toLight, const V3& eLit) {
     sp.pending = true; sp.hit = hit; sp.toLight = toLight; sp.eLit = eLit;
   });
 }
-template <bool DEFER, class OnShadow>
-D void shadeBounceT(const Ctx& c, const Hit& ins, Ray& ray, float seed, V3& fpdf, V3& e, PhaseClock& pc, OnShadow&& onShadow) {
+template <bool DEFER, class R, class OnShadow>
+D void shadeBounceT(const Ctx& c, const Hit& ins, R& ray, float seed, V3& fpdf, V3& e, PhaseClock& pc, OnShadow&& onShadow) {
   {
     // shade()
     // box faces have axis-aligned unit dpdu: dot == 1 exactly, sqrt(1) == 1 and v / 1 == v bit for bit
@@ -507,7 +510,7 @@ D void shadeBounceT(const Ctx& c, const Hit& ins, Ray& ray, float seed, V3& fpdf
     }
     fpdf = fpdf * _fpdf;
     const float outdot = ins.axis ? dotX(ins.normal, wi) : dot(ins.normal, wi);
-    ray = mkRay(ins.hit + ins.normal * (outdot > kEps ? 0.0001f : -0.0001f), wi);
+    nextRay(ray, ins.hit + ins.normal * (outdot > kEps ? 0.0001f : -0.0001f), wi);
     PHASE_MARK(pc, 6);  // next ray
   }
 }

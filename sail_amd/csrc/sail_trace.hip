@@ -202,6 +202,7 @@ __device__ __forceinline__ void traceTileCompact(const SailTraceArgs& A) {
   int shph = 0;
   constexpr bool twoBar = CULL || FAM;
   constexpr bool kSort1 = CULL || FAM;  // sort the paths at the first bounce too
+  constexpr bool kGatherAll = !CULL;    // after a sort every lane gathers, live or not (the gather below says why)
   __shared__ int sCnt2[twoBar ? 2 : 1][kKeys];  // [0] alone in the three-barrier sort
   __shared__ int sStart[twoBar ? 1 : kKeys + 1];
   const TileWork tw = tileWork<GROUPED, kPX>(A);
@@ -315,11 +316,14 @@ __device__ __forceinline__ void traceTileCompact(const SailTraceArgs& A) {
     bool alive = valid && inRange;
     int pixel = li;  // the path's home slot
     auto pathSeed = [&](int h) { if constexpr (NS == 1) return S.seed; else return sSeed[h / kPX]; };
-    Ray ray;
+    // a flat form's path carries its segment (origin, direction) alone: the reciprocals of a direction are built where
+    // the segment is swept, below, and die with the sweep, so neither the sort nor the shading holds registers for
+    // them. The pre-cull form carries the ray with its reciprocals (PathRay in sail_geom.h says why).
+    typename PathRay<CULL>::type ray;
     {
       const V3 d0 = v3(S.d[0][0], S.d[0][1], S.d[0][2]), d1 = v3(S.d[1][0], S.d[1][1], S.d[1][2]);
       const V3 d2 = v3(S.d[2][0], S.d[2][1], S.d[2][2]), d3 = v3(S.d[3][0], S.d[3][1], S.d[3][2]);
-      ray = mkRay(eye, tri0 ? (d0 + (d2 - d0) * s + (d1 - d0) * t) : (d3 + (d1 - d3) * (1.0f - s) + (d2 - d3) * (1.0f - t)));
+      nextRay(ray, eye, tri0 ? (d0 + (d2 - d0) * s + (d1 - d0) * t) : (d3 + (d1 - d3) * (1.0f - s) + (d2 - d3) * (1.0f - t)));
     }
     V3 fpdf = v3s(1.0f);
     // the path's radiance lives in LDS at its pixel: one path per pixel, updated in bounce order
@@ -340,10 +344,11 @@ __device__ __forceinline__ void traceTileCompact(const SailTraceArgs& A) {
 #endif
       if (alive) {
         if constexpr (!CULL) segs++;
+        const Ray& rr = sweptRay(ray);  // flat forms: rcp_rn of the three components here, once per traced segment
 #if SAIL_ROWDEFER
-        sw = sweepRayDefer(c, ray, deferB, cand);
+        sw = sweepRayDefer(c, rr, deferB, cand);
 #else
-        sw = sweepRay(c, ray, depth == 1);
+        sw = sweepRay(c, rr, depth == 1);
 #endif
 #if SAIL_ROWDEFER
         if (cand) {
@@ -403,13 +408,16 @@ __device__ __forceinline__ void traceTileCompact(const SailTraceArgs& A) {
       // ---- counting sort of the live paths by key (LDS atomics for the per-key rank, one wave scans)
       int rank = 0;
       int nAlive;
-      // a path's state into sorted slot d
-      // after the scatter a lane's old path state is dead (a live lane gathers a new one, a dead lane reads none): say
-      // so, or the compiler keeps it live across the sort for the lanes that gather nothing
+      // the pre-cull form alone gathers under `if (alive)` (see the gather below): there a lane's old path state is dead
+      // after the scatter (a live lane gathers a new one, a dead lane reads none), and says so, or the compiler keeps it
+      // live across the sort for the lanes that gather nothing
       auto dropState = [&]() {
-        ray.o = v3s(0.0f); ray.d = v3s(0.0f); ray.rx = ray.ry = ray.rz = 0.0f;
-        fpdf = v3s(0.0f); sw.best = 0.0f; sw.bi = 0; pixel = 0;
+        if constexpr (!kGatherAll) {
+          ray.o = v3s(0.0f); ray.d = v3s(0.0f); dropRcp(ray);
+          fpdf = v3s(0.0f); sw.best = 0.0f; sw.bi = 0; pixel = 0;
+        }
       };
+      // a path's state into sorted slot d
       auto scatterTo = [&](int d) {
         if constexpr (kPack == 2) {
           sSt4[0][d] = make_float4(ray.o.x, ray.o.y, ray.o.z, ray.d.x);
@@ -482,33 +490,52 @@ __device__ __forceinline__ void traceTileCompact(const SailTraceArgs& A) {
       V3 eLit = v3s(0.0f);
       int keyG = 0;  // the gathered path's sort key
       PHASE_MARK(pc, 9);
-      if (alive) {
-        if (!sortNow) {
-          keyG = key;
-        } else if constexpr (kPack == 2) {
-          const float4 q0 = sSt4[0][li], q1 = sSt4[1][li], q2 = sSt4[2][li];
-          const int pk = __float_as_int(q2.z);
-          keyG = __float_as_int(q2.w);
-          ray.o = v3(q0.x, q0.y, q0.z);
-          ray.d = v3(q0.w, q1.x, q1.y);
-          fpdf = v3(q1.z, q1.w, q2.x);
-          sw.best = q2.y;
-          pixel = pk & 1023;
-          sw.bi = pk >> 10;
-          sw.bhl = v3s(0.0f);  // recomputed by hitRecord<true>
-        } else {
-          const float2 q0 = sSt2[0][li], q1 = sSt2[1][li], q2 = sSt2[2][li], q3 = sSt2[3][li], q4 = sSt2[4][li];
-          const int pk = __float_as_int(sSt2[5][li].x);
-          keyG = __float_as_int(sSt2[5][li].y);
-          ray.o = v3(q0.x, q0.y, q1.x);
-          ray.d = v3(q1.y, q2.x, q2.y);
-          fpdf = v3(q3.x, q3.y, q4.x);
-          sw.best = q4.y;
-          pixel = pk & 1023;
-          sw.bi = pk >> 10;
-          sw.bhl = v3s(0.0f);  // recomputed by hitRecord<true>
+      // After a sort every lane of a flat form (Cornell, room, all-plugin) reads and unpacks the packed state of its sorted
+      // slot, the lanes past the live range too: theirs is a slot nobody wrote this bounce (stale or never-written LDS,
+      // inside the array), and nothing reads what they unpack -- every use of the state is under `if (alive)` below. A
+      // gather under `if (alive)` leaves those lanes their old state, which the compiler keeps live across the sort and
+      // merges with the gathered one unless fifteen zero moves per sorted bounce end it (dropState). An unsorted bounce
+      // keeps its registers. Measured: C2 +0.9 % by this alone, C3 +0.5 % with the segment-only
+      // path; the room form's spills did not move. The pre-cull form keeps its gather under `if (alive)` and its
+      // dropState: with every lane gathering (and the segment-only path) its grouped kernel spilled 86 VGPRs for 80
+      // and C4 lost 1.3 % (spread 0.6 %), and a fully dead wave there would issue six LDS reads it now skips.
+      // (a macro, one text for both places: as a lambda the same text cost the pre-cull kernel 9 more spilled VGPRs
+      // and C4 0.7 %)
+#define SAIL_GATHER()                                                                                            \
+        if constexpr (kPack == 2) {                                                                              \
+          const float4 q0 = sSt4[0][li], q1 = sSt4[1][li], q2 = sSt4[2][li];                                     \
+          const int pk = __float_as_int(q2.z);                                                                   \
+          keyG = __float_as_int(q2.w);                                                                           \
+          ray.o = v3(q0.x, q0.y, q0.z);                                                                          \
+          ray.d = v3(q0.w, q1.x, q1.y);                                                                          \
+          fpdf = v3(q1.z, q1.w, q2.x);                                                                           \
+          sw.best = q2.y;                                                                                        \
+          pixel = pk & 1023;                                                                                     \
+          sw.bi = pk >> 10;                                                                                      \
+          sw.bhl = v3s(0.0f);  /* recomputed by hitRecord<true> */                                               \
+        } else {                                                                                                 \
+          const float2 q0 = sSt2[0][li], q1 = sSt2[1][li], q2 = sSt2[2][li], q3 = sSt2[3][li], q4 = sSt2[4][li]; \
+          const int pk = __float_as_int(sSt2[5][li].x);                                                          \
+          keyG = __float_as_int(sSt2[5][li].y);                                                                  \
+          ray.o = v3(q0.x, q0.y, q1.x);                                                                          \
+          ray.d = v3(q1.y, q2.x, q2.y);                                                                          \
+          fpdf = v3(q3.x, q3.y, q4.x);                                                                           \
+          sw.best = q4.y;                                                                                        \
+          pixel = pk & 1023;                                                                                     \
+          sw.bi = pk >> 10;                                                                                      \
+          sw.bhl = v3s(0.0f);  /* recomputed by hitRecord<true> */                                               \
         }
-        ray.rx = ray.ry = ray.rz = 0.0f;  // not used past the sweep: the next ray is rebuilt by mkRay
+      if constexpr (kGatherAll) {
+        if (!sortNow) keyG = key;
+        else { SAIL_GATHER() }
+      }
+      if (alive) {
+        if constexpr (!kGatherAll) {
+          if (!sortNow) keyG = key;
+          else { SAIL_GATHER() }
+          dropRcp(ray);
+        }
+#undef SAIL_GATHER
         {  // a wave whose live paths have different sort keys runs several hit-record / material branches: raise its
            // issue priority so that its workgroup's next barrier is not held up by it (the other waves wait there)
           const int k0 = __builtin_amdgcn_readfirstlane(keyG);

@@ -23,7 +23,7 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-
          "--offload-arch=gfx950", "--cuda-device-only", "-gline-tables-only"]
 
 # part of the bounce <- the first inlined function under traceTileCompact (then refined by the one under it)
-PARTS = [("sweepRay", "sweep"), ("sphereResolve", "sweep: the deferred row's tail, after the gather"),("closestT", "light + shadow"), ("hitRecord", "hit record"), ("quadLocalHit", "hit record"),
+PARTS = [("sweepRay", "sweep"), ("sweptRay", "sweep: the ray's reciprocals (mkRay)"), ("sphereResolve", "sweep: the deferred row's tail, after the gather"),("closestT", "light + shadow"), ("hitRecord", "hit record"), ("quadLocalHit", "hit record"),
          ("rectLocalHit", "hit record"), ("shadeLast", "last bounce (shadeLast)"), ("accumulateSample", "sample end"),
          ("stageSample", "sample end"), ("keyRank", "sort"), ("waveScanIncl", "sort"), ("atomicAdd", "sort"),
          ("__shfl", "sort")]
