@@ -641,6 +641,78 @@ int sail_denoise_albedo(sail_ctx* ctx, const sail_denoise_params* p, float amin,
 int sail_temporal_filter_albedo(sail_ctx* ctx, const sail_tfilter_params* p, float amin, float* out_rgba, float* out_var,
                                 uint8_t* out_rgba8, sail_tfilter_info* info);
 
+/* ---- guide maps of a view: the denoiser's normals and positions followed through mirror and glass (no reference
+ * counterpart) ----
+ * Both a-trous filters read the normal and position AOVs, which show a specular surface's own normal and position, while the
+ * picture on such a pixel is whatever the mirror or the glass shows: a sphere's normals turn smoothly, so nothing stops
+ * the filter at the reflected room's edges, and its normal stop cuts the footprint on the reflected flat walls. The guide
+ * maps hold, per pixel, the normal and the position of the first surface that scatters, reached by walking the pixel-centre
+ * ray through mirror and smooth glass with the material's random pair fixed.
+ *
+ * The maps Ng, Xg of a view (mvp, eye) with follow depth D in 0..8; pixel (x, y), row 0 = bottom; every operation an f32
+ * IEEE one, in the trace kernels' order:
+ *   ray = the G-buffer pass's ray at s = (x + 0.5) / W, t = (y + 0.5) / H            (bit for bit sail_gbuffer's)
+ *   depth = 0
+ *   loop:
+ *     ins = the trace kernels' intersection of ray with every row (the sweep of sail_pick: the first row with the smallest
+ *           d) and its full hit record (normal, hit, dpdu, into, material row and category, surface colour with the
+ *           scene's own texture plugins)
+ *     a miss: depth == 0 -> the pixel is a miss; else the surface recorded last stays. stop.
+ *     record n = ins.normal, p = ins.hit, id = ins.index
+ *     followable = the category is MIRROR, or GLASS whose row gives ur < 1e-5 and vr < 1e-5 (the smooth branch), and the
+ *                  scene's material plugins hold the category
+ *     not followable -> stop;   depth == D -> the pixel is truncated, stop
+ *     ss = normalize(ins.dpdu);  ts = cross(ins.normal, ss);  wo = worldToLocal(-ray.dir, ins.normal, ss, ts)
+ *     wi = the material's sampled direction with u = (0.5, 0.5) in the place of the hash pair
+ *          (mirror: (-wo.x, -wo.y, wo.z); smooth glass: Fd = frDielectric(wo.z, 1, eta); 0.5 < Fd reflects like the
+ *          mirror, else refract(-wo, (0, 0, 1), into ? 1 / eta : eta / 1))
+ *     wi = localToWorld(wi, ins.normal, ss, ts)
+ *     ray.origin = ins.hit + ins.normal * (dot(ins.normal, wi) > 1e-5 ? 1e-4 : -1e-4);  ray.dir = wi;  depth = depth + 1
+ *   Ng[p] = (n / 2 + 0.5, (float)depth)           -- the normal AOV's encoding
+ *   Xg[p] = (normalize(p), (float)id)             -- the position AOV's encoding
+ *   a miss: Ng = (0.5, 0.5, 0.5, 0), Xg = (NaN, NaN, NaN, -1): a non-finite position gives every tap with it weight 0
+ * This is the path loop with the random pair fixed: it carries no radiance and stops at the first surface that scatters. A
+ * pane of smooth glass follows one branch of its reflect/refract mix. With D = 0 the xyz of both maps equal the AOVs of a
+ * one-sample render without jitter wherever that sample hits. hit_pixels counts Xg.w >= 0, followed_pixels Ng.w > 0,
+ * truncated_pixels the pixels that stopped at depth D on a followable surface.
+ *
+ * State. sail_guides follows the albedo call's rules: a depth outside 0..8 is SAIL_E_INVALID before anything else; it
+ * needs a scene (SAIL_E_STATE), refuses a singular mvp (SAIL_E_INVALID) and launches queued samples first; a multi-device
+ * context works on device 0's scene. It keeps both maps as the context's guide maps together with their view, stored as
+ * the temporal views are (each double of P*MV rounded to f32, and the eye); the maps are allocated on first use (device 0
+ * of a multi-device context). sail_guides_load installs a caller's maps (W H 4 f32 each) for the view the caller passes. A
+ * new scene, updated rows and moved rows invalidate the maps; a reset, a loaded checkpoint, the accumulation mode, the
+ * partition and the temporal calls keep them. Without valid maps sail_guides_read returns SAIL_E_STATE.
+ *
+ * sail_use_guides(ctx, 1): sail_denoise, sail_denoise_albedo, sail_temporal_filter and sail_temporal_filter_albedo read
+ * Ng and Xg wherever their text reads N and X; nothing else of their text changes. They then return SAIL_E_STATE without
+ * valid maps, the two temporal filters also unless the maps' stored view equals the current temporal view bit for bit, and
+ * none of them needs SAIL_FLAG_AOV: guide maps belong to a view, not to a launch, so a context that filters with them
+ * spares the two AOV stores per pixel of every launch. on = 0, the default, restores today's calls exactly; another value
+ * is SAIL_E_INVALID. The switch survives everything but sail_destroy. Reprojection (sail_temporal_begin) keeps using the
+ * first hit, and the albedo map stays a first-hit map: the mirror's tint and the Fresnel mix are not part of a followed
+ * surface colour, and dividing by it measured worse. A context that never calls these functions allocates nothing,
+ * launches nothing new and produces the same bits as before. */
+typedef struct sail_guides_info {
+  uint64_t hit_pixels;        /* pixels whose first ray hit the scene */
+  uint64_t followed_pixels;   /* pixels that left their first surface (depth > 0) */
+  uint64_t truncated_pixels;  /* pixels stopped by `depth` on a surface that could be followed */
+  int depth;                  /* D of the call */
+  int max_depth;              /* the largest depth any pixel walked */
+  double kernel_ms;           /* HIP events */
+} sail_guides_info;
+enum sail_guide_map { SAIL_GUIDE_N = 0, SAIL_GUIDE_X = 1 };
+/* compute the maps of a view and keep them; out_n, out_x (W H 4 f32 each) and info may each be NULL */
+int sail_guides(sail_ctx* ctx, const double mvp_rowmajor[16], const float eye[3], int depth, float* out_n, float* out_x,
+                sail_guides_info* info);
+/* install n_map and x_map (W H 4 f32 each) as the context's guide maps of the view (mvp, eye) */
+int sail_guides_load(sail_ctx* ctx, const float* n_map, const float* x_map, const double mvp_rowmajor[16],
+                     const float eye[3]);
+/* copy one of the context's guide maps (sail_guide_map) into out (W H 4 f32); another `which`: SAIL_E_INVALID */
+int sail_guides_read(sail_ctx* ctx, int which, float* out);
+/* on = 1: the four filters read the guide maps in the AOVs' place; on = 0 (the default): the AOVs */
+int sail_use_guides(sail_ctx* ctx, int on);
+
 /* ---- checkpoint / resume of a progressive render (no reference counterpart: the reference restarts its
  * accumulation on every camera or object change, src/core/renderer.js:57-60, src/scene/scene.js:65-68) ----
  * A context's accumulation is `parts` raw accumulators (1 for sail_create, one per device for sail_create_multi),

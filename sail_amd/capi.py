@@ -61,6 +61,7 @@ EXPORTS = (
     "sail_temporal_filter_defaults", "sail_temporal_filter",
     "sail_move_objects", "sail_temporal_pending_motion",
     "sail_albedo", "sail_albedo_load", "sail_albedo_read", "sail_denoise_albedo", "sail_temporal_filter_albedo",
+    "sail_guides", "sail_guides_load", "sail_guides_read", "sail_use_guides",
 )
 
 
@@ -173,6 +174,13 @@ class AlbedoInfo(ctypes.Structure):
                 ("kernel_ms", ctypes.c_double)]
 
 
+class GuidesInfo(ctypes.Structure):
+    _fields_ = [("hit_pixels", ctypes.c_uint64), ("followed_pixels", ctypes.c_uint64),
+                ("truncated_pixels", ctypes.c_uint64), ("depth", ctypes.c_int), ("max_depth", ctypes.c_int),
+                ("kernel_ms", ctypes.c_double)]
+
+
+GUIDE_N, GUIDE_X = 0, 1         # sail_guide_map
 ALBEDO_AMIN_DEFAULT = 0.01      # SAIL_ALBEDO_AMIN_DEFAULT: a guard, not a tuned value
 
 
@@ -307,6 +315,10 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
         "sail_albedo": (ctypes.c_int, [vp, f64p, f32p, ctypes.c_int, f32p, ctypes.POINTER(AlbedoInfo)]),
         "sail_albedo_load": (ctypes.c_int, [vp, f32p, f64p, f32p]),
         "sail_albedo_read": (ctypes.c_int, [vp, f32p]),
+        "sail_guides": (ctypes.c_int, [vp, f64p, f32p, ctypes.c_int, f32p, f32p, ctypes.POINTER(GuidesInfo)]),
+        "sail_guides_load": (ctypes.c_int, [vp, f32p, f32p, f64p, f32p]),
+        "sail_guides_read": (ctypes.c_int, [vp, ctypes.c_int, f32p]),
+        "sail_use_guides": (ctypes.c_int, [vp, ctypes.c_int]),
         "sail_denoise_albedo": (ctypes.c_int, [vp, ctypes.POINTER(DenoiseParams), ctypes.c_float, f32p, f32p,
                                                ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(DenoiseInfo)]),
         "sail_temporal_filter_albedo": (ctypes.c_int, [vp, ctypes.POINTER(TfilterParams), ctypes.c_float, f32p, f32p,
@@ -959,6 +971,43 @@ class Context:
         out = np.zeros((self.H, self.W, 4), dtype=np.float32)
         self._check(self.lib.sail_albedo_read(self.h, _ptr(out)), "sail_albedo_read")
         return out
+
+    def guides(self, mvp, eye, depth: int = 4) -> dict:
+        """The guide maps of a view (sail_guides): the normal and position of the first surface that scatters, reached
+        through at most `depth` mirror or smooth-glass surfaces, kept by the context for the filters under
+        use_guides(True). Returns "n" (H, W, 4) f32 (the normal AOV's encoding, .w: the depth walked), "x" (H, W, 4) f32
+        (the position AOV's encoding, .w: the object row; a miss is (NaN, NaN, NaN, -1)), hit_pixels, followed_pixels,
+        truncated_pixels, depth, max_depth and kernel_ms."""
+        m = np.ascontiguousarray(np.asarray(mvp, dtype=np.float64).reshape(16))
+        e = _f32(eye)
+        n = np.zeros((self.H, self.W, 4), dtype=np.float32)
+        x = np.zeros((self.H, self.W, 4), dtype=np.float32)
+        info = GuidesInfo()
+        self._check(self.lib.sail_guides(self.h, _ptr(m, ctypes.c_double), _ptr(e), int(depth), _ptr(n), _ptr(x),
+                                         ctypes.byref(info)), "sail_guides")
+        return {"n": n, "x": x, "hit_pixels": int(info.hit_pixels), "followed_pixels": int(info.followed_pixels),
+                "truncated_pixels": int(info.truncated_pixels), "depth": info.depth, "max_depth": info.max_depth,
+                "kernel_ms": info.kernel_ms}
+
+    def guides_load(self, n_map, x_map, mvp, eye):
+        """Install guide maps (H, W, 4) f32 each for the view (mvp, eye) (sail_guides_load)."""
+        n, x = _f32(n_map), _f32(x_map)
+        if n.shape != (self.H, self.W, 4) or x.shape != (self.H, self.W, 4):
+            raise SailError(f"guides_load: both maps must have shape {(self.H, self.W, 4)}")
+        m = np.ascontiguousarray(np.asarray(mvp, dtype=np.float64).reshape(16))
+        e = _f32(eye)
+        self._check(self.lib.sail_guides_load(self.h, _ptr(n), _ptr(x), _ptr(m, ctypes.c_double), _ptr(e)),
+                    "sail_guides_load")
+
+    def guides_read(self, which: int) -> np.ndarray:
+        """One of the context's guide maps (GUIDE_N, GUIDE_X) as (H, W, 4) f32 (sail_guides_read)."""
+        out = np.zeros((self.H, self.W, 4), dtype=np.float32)
+        self._check(self.lib.sail_guides_read(self.h, int(which), _ptr(out)), "sail_guides_read")
+        return out
+
+    def use_guides(self, on: bool = True):
+        """The four filters read the guide maps in the AOVs' place (sail_use_guides); off by default."""
+        self._check(self.lib.sail_use_guides(self.h, 1 if on else 0), "sail_use_guides")
 
     def gbuffer(self, mvp, eye, rays: bool = False) -> dict:
         """The G-buffer pass for a view (sail_gbuffer): "id" (H, W) int32 object row of the first hit or -1, "t" (H, W)

@@ -914,7 +914,7 @@ static DecodedScene decodeRows(sail_ctx* c, const float* objects, int n, const f
 }
 
 // What a context forgets when its rows change (sail_set_scene, sail_update_objects, sail_move_objects), written once.
-// The albedo map shows the rows as they were, whoever moved them. The temporal views' ids and positions are stale, and
+// The albedo map and the guide maps show the rows as they were, whoever moved them. The temporal views' ids and positions are stale, and
 // with them the pending motion and the moments, unless the caller records how the rows moved (keepTemporal:
 // sail_move_objects on a context with temporal state). The value kernel has the old rows' words compiled in: it goes and
 // the settle count restarts; a drag keeps the types kernel, a changed shape type or plugin set starts the new rows'
@@ -922,6 +922,7 @@ static DecodedScene decodeRows(sail_ctx* c, const float* objects, int n, const f
 // kernel of the set serves. The accumulation restarts (resetAccum: the mark, the tile mask, "resolved").
 static int rowsChanged(sail_ctx* c, bool keepTemporal) {
   c->albHave = false;
+  c->guideHave = false;
   if (!keepTemporal) {
     c->tpHaveCur = c->tpHavePrev = c->tpResolved = false;
     clearMotion(c);

@@ -4,7 +4,7 @@
 //   sail_plan.cpp      kernel choice and launch shape as pure functions of plain facts (sail_plan.h; no context, no HIP)
 //   sail_multi.cpp     RCCL binding, multi-device reduce, checkpoint parts
 //   sail_converge.cpp  noise estimate, render-until, tile mask, adaptive sampling
-//   sail_post.cpp      a-trous denoiser, reprojection, moment tracking, temporal filter, albedo map
+//   sail_post.cpp      a-trous denoiser, reprojection, moment tracking, temporal filter, albedo map, guide maps
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -52,6 +52,9 @@ hipError_t sail_launch_albedo(const SailAlbedoArgs& A, hipStream_t s);
 hipError_t sail_launch_denoise_prepare_demod(const SailDenoisePrepareDemodArgs& A, hipStream_t s);
 hipError_t sail_launch_denoise_atrous_remod(const SailDenoiseAtrousRemodArgs& A, hipStream_t s);
 hipError_t sail_launch_tfilter_prepare_demod(const SailTfilterPrepareDemodArgs& A, hipStream_t s);
+// sail_guides.hip: the guide maps of a view
+#include "sail_guides.h"
+hipError_t sail_launch_guides(const SailGuidesArgs& A, hipStream_t s);
 
 // what follows is shared between the host files only: none of it is exported from the library
 #pragma GCC visibility push(hidden)
@@ -272,6 +275,14 @@ struct sail_ctx {
   float4* albMap = nullptr;
   bool albHave = false;
   TpView albView{};
+  // Guide maps (sail_guides / sail_guides_load): two float4 maps (Ng, then Xg) and three counts per 16x16 tile in one
+  // block, allocated on first use, with the view they belong to, kept and invalidated as the albedo map is. useGuides
+  // (sail_use_guides): the four filters read them in the AOVs' place. On a multi-device context device 0's sub-context
+  // holds both.
+  float4* guideMaps = nullptr;
+  bool guideHave = false;
+  bool useGuides = false;
+  TpView guideView{};
   nccl_comm_t comm = nullptr;
   int commRanks = 0, commRank = 0;
   // Reduced frame (root of sail_reduce / device 0 of a multi-device context): the sum of every rank's

@@ -8,3 +8,4 @@
 #include "sail_frame.hip"
 #include "sail_temporal.hip"
 #include "sail_albedo.hip"
+#include "sail_guides.hip"

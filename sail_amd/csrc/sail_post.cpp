@@ -1,6 +1,6 @@
 // sail_post.cpp — the passes over a rendered frame: the a-trous denoiser (sail_denoise.hip), camera- and object-motion
 // reprojection (sail_temporal.hip), moment tracking and the temporal filter (sail_tfilter.hip), the albedo map
-// (sail_albedo.hip). The context is sail_ctx.h's; sail_capi.cpp's rowsChanged says what of this new rows invalidate.
+// (sail_albedo.hip), the guide maps (sail_guides.hip). The context is sail_ctx.h's; sail_capi.cpp's rowsChanged says what of this new rows invalidate.
 #include <math.h>
 #include <string.h>
 #include <algorithm>
@@ -100,7 +100,7 @@ void clearMotion(sail_ctx* c) {
 }
 
 void freePost(sail_ctx* c) {
-  for (void* b : {c->denoiseWork, c->tpWork, c->tpMom, (void*)c->tpMotionDev, (void*)c->albMap}) if (b) (void)hipFree(b);
+  for (void* b : {c->denoiseWork, c->tpWork, c->tpMom, (void*)c->tpMotionDev, (void*)c->albMap, (void*)c->guideMaps}) if (b) (void)hipFree(b);
 }
 
 extern "C" {
@@ -122,6 +122,21 @@ namespace {
 
 bool aminOk(float amin) { return std::isfinite(amin) && amin > 0.0f; }
 
+// The normal and position maps a filter reads: the shown AOVs, or with sail_use_guides the guide maps (Ng, then Xg)
+const float4* guideN(const sail_ctx* c) { return c->guideMaps; }
+const float4* guideX(const sail_ctx* c) { return c->guideMaps + (size_t)c->share.W * c->share.H; }
+const float4* filterN(const sail_ctx* c) { return c->useGuides ? guideN(c) : shownAovN(c); }
+const float4* filterX(const sail_ctx* c) { return c->useGuides ? guideX(c) : shownAovP(c); }
+// what a filter refuses about them (temporal: the maps must belong to the current temporal view)
+int filterGuides(sail_ctx* c, const char* who, bool temporal) {
+  if (!c->useGuides) return SAIL_OK;
+  if (!c->guideHave || !c->guideMaps)
+    return fail(c, SAIL_E_STATE, "%s: no guide maps (sail_guides or sail_guides_load first; new rows drop them)", who);
+  if (temporal && memcmp(&c->guideView, &c->tpCur, sizeof c->guideView) != 0)
+    return fail(c, SAIL_E_STATE, "%s: the guide maps belong to another view than the current temporal view", who);
+  return SAIL_OK;
+}
+
 // sail_denoise (demod = false: amin is not read, no map is needed) and sail_denoise_albedo
 int denoiseCall(sail_ctx* c, const char* who, bool demod, const sail_denoise_params* params, float amin, float* out_rgba,
                 float* out_var, uint8_t* out_rgba8, sail_denoise_info* info) {
@@ -138,7 +153,7 @@ int denoiseCall(sail_ctx* c, const char* who, bool demod, const sail_denoise_par
     if (int rc = reducedFrame(c, who)) return rc;
     return relay(c, denoiseCall(c->subs[0], who, demod, &p, amin, out_rgba, out_var, out_rgba8, info), c->subs[0]);
   }
-  if (!c->aovN || !c->aovP)
+  if (!c->useGuides && (!c->aovN || !c->aovP))
     return fail(c, SAIL_E_STATE, "%s: reads the normal and position AOVs (create with SAIL_FLAG_AOV)", who);
   if (c->accumMode == SAIL_ACCUM_COMPAT8)
     return fail(c, SAIL_E_STATE, "%s: SAIL_ACCUM_COMPAT8 stores 8-bit frames, whose halves cannot be compared", who);
@@ -151,12 +166,13 @@ int denoiseCall(sail_ctx* c, const char* who, bool demod, const sail_denoise_par
                 (unsigned long long)c->k, (unsigned long long)c->noiseK);
   if (demod && (!c->albHave || !c->albMap))
     return fail(c, SAIL_E_STATE, "%s: no albedo map (sail_albedo or sail_albedo_load first; new rows drop it)", who);
+  if (int rc = filterGuides(c, who, false)) return rc;
   const size_t nt = tiles16(c);
   if (int rc = ensureDenoiseWork(c)) return rc;
   const DenoiseWork w = denoiseWork(c);
   SailDenoisePrepareArgs A;
   memset(&A, 0, sizeof A);
-  A.S = shownAccum(c); A.P = c->noiseMark; A.N = shownAovN(c); A.X = shownAovP(c);
+  A.S = shownAccum(c); A.P = c->noiseMark; A.N = filterN(c); A.X = filterX(c);
   A.cv = w.cv[0]; A.g0 = w.g0; A.g1 = w.g1; A.tileBad = w.bad;
   A.W = c->share.W; A.H = c->share.H;
   A.mix = c->accumMode == SAIL_ACCUM_MIX;
@@ -590,7 +606,7 @@ int tfilterCall(sail_ctx* c, const char* who, bool demod, const sail_tfilter_par
   if (int rc = sail_sync(c)) return rc;
   if (!c->tpMom)
     return fail(c, SAIL_E_STATE, "%s: moment tracking is off (sail_temporal_moments first)", who);
-  if (!c->aovN || !c->aovP)
+  if (!c->useGuides && (!c->aovN || !c->aovP))
     return fail(c, SAIL_E_STATE, "%s: reads the normal and position AOVs (create with SAIL_FLAG_AOV)", who);
   if (c->accumMode == SAIL_ACCUM_COMPAT8)
     return fail(c, SAIL_E_STATE, "%s: SAIL_ACCUM_COMPAT8 stores 8-bit frames, which carry no sample count to blend with", who);
@@ -604,13 +620,14 @@ int tfilterCall(sail_ctx* c, const char* who, bool demod, const sail_tfilter_par
     return fail(c, SAIL_E_STATE, "%s: no albedo map (sail_albedo or sail_albedo_load first; new rows drop it)", who);
   if (demod && memcmp(&c->albView, &c->tpCur, sizeof c->albView) != 0)
     return fail(c, SAIL_E_STATE, "%s: the albedo map belongs to another view than the current temporal view", who);
+  if (int rc = filterGuides(c, who, true)) return rc;
   const size_t nt = tiles16(c), np = (size_t)c->share.W * c->share.H;
   if (int rc = ensureDenoiseWork(c)) return rc;
   const DenoiseWork w = denoiseWork(c);  // sail_denoise's work buffers; the count of temporal pixels sits behind the moments
   uint32_t* dTmp = (uint32_t*)((char*)c->tpMom + np * 48);
   SailTfilterPrepareArgs A;
   memset(&A, 0, sizeof A);
-  A.Out = c->tpOut; A.Mout = c->tpMout; A.S = shownAccum(c); A.N = shownAovN(c); A.X = shownAovP(c);
+  A.Out = c->tpOut; A.Mout = c->tpMout; A.S = shownAccum(c); A.N = filterN(c); A.X = filterX(c);
   A.cv = w.cv[0]; A.g0 = w.g0; A.g1 = w.g1; A.tileBad = w.bad; A.tileTemporal = dTmp;
   A.W = c->share.W; A.H = c->share.H;
   A.mix = c->accumMode == SAIL_ACCUM_MIX;
@@ -741,6 +758,118 @@ int sail_albedo_read(sail_ctx* c, float* out) {
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipMemcpy(out, c->albMap, (size_t)c->share.W * c->share.H * 16, hipMemcpyDeviceToHost));
+  return SAIL_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+uint32_t* guideCounts(const sail_ctx* c) { return (uint32_t*)(c->guideMaps + (size_t)c->share.W * c->share.H * 2); }
+
+// the two guide maps and their three counts per tile, allocated on first use
+int ensureGuides(sail_ctx* c) {
+  return allocOnce(c, &c->guideMaps, (size_t)c->share.W * c->share.H * 32 + tiles16(c) * 12, "guide maps");
+}
+
+void guidesView(sail_ctx* c, const double mvp[16], const float eye[3]) {
+  memset(&c->guideView, 0, sizeof c->guideView);
+  for (int i = 0; i < 16; i++) c->guideView.m[i] = (float)mvp[i];
+  memcpy(c->guideView.eye, eye, sizeof c->guideView.eye);
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- the guide maps of a view (include/sail_hip.h; the kernel is sail_guides.hip) ----------------------------------------------
+int sail_guides(sail_ctx* c, const double mvp[16], const float eye[3], int depth, float* out_n, float* out_x,
+                sail_guides_info* info) {
+  if (depth < 0 || depth > 8) return fail(c, SAIL_E_INVALID, "sail_guides: depth %d of 0..8", depth);
+  if (!c) return fail(c, SAIL_E_INVALID, "sail_guides: a context is required");
+  if (!mvp || !eye) return fail(c, SAIL_E_INVALID, "sail_guides: mvp and eye are required");
+  if (!c->subs.empty()) return relay(c, sail_guides(c->subs[0], mvp, eye, depth, out_n, out_x, info), c->subs[0]);
+  if (!c->haveScene) return fail(c, SAIL_E_STATE, "sail_guides: no scene (call sail_set_scene first)");
+  SailGbufferArgs G;
+  if (int rc = gbufferArgs(c, "sail_guides", mvp, eye, &G)) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = sail_sync(c)) return rc;
+  if (int rc = ensureGuides(c)) return rc;
+  const size_t nt = tiles16(c), np = (size_t)c->share.W * c->share.H;
+  SailGuidesArgs A;
+  memset(&A, 0, sizeof A);
+  A.prims = c->prims; A.texparams = c->tp; A.n = c->facts.n; A.tn = c->facts.tn;
+  A.matMask = c->facts.plugins.material_mask; A.texMask = c->facts.plugins.texture_mask;
+  memcpy(A.d, G.d, sizeof A.d);
+  memcpy(A.eye, eye, sizeof A.eye);
+  A.W = c->share.W; A.H = c->share.H; A.depth = depth;
+  A.Ng = c->guideMaps; A.Xg = c->guideMaps + np;
+  A.tileHit = guideCounts(c); A.tileFollowed = A.tileHit + nt; A.tileTruncated = A.tileHit + 2 * nt;
+  c->guideHave = false;  // a call that fails leaves no maps
+  PooledEvents ev(c, 2);
+  if (ev.rc) return ev.rc;
+  float ms = 0.0f;
+  hipError_t e = hipEventRecord(ev[0], c->stream);
+  if (e == hipSuccess) e = sail_launch_guides(A, c->stream);
+  if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+  std::vector<uint32_t> host(nt * 3);
+  if (e == hipSuccess) e = hipMemcpy(host.data(), A.tileHit, nt * 12, hipMemcpyDeviceToHost);
+  std::vector<float> ng((info && !out_n) ? np * 4 : 0);  // max_depth is read off Ng.w
+  float* hn = out_n ? out_n : (ng.empty() ? nullptr : ng.data());
+  if (e == hipSuccess && hn) e = hipMemcpy(hn, A.Ng, np * 16, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && out_x) e = hipMemcpy(out_x, A.Xg, np * 16, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(c, SAIL_E_HIP, "sail_guides: %s", hipGetErrorString(e));
+  guidesView(c, mvp, eye);
+  c->guideHave = true;
+  if (info) {
+    memset(info, 0, sizeof *info);
+    info->hit_pixels = sumTiles(host, 0, nt);
+    info->followed_pixels = sumTiles(host, nt, nt);
+    info->truncated_pixels = sumTiles(host, 2 * nt, nt);
+    info->depth = depth;
+    for (size_t i = 0; i < np; i++) info->max_depth = std::max(info->max_depth, (int)hn[4 * i + 3]);
+    info->kernel_ms = ms;
+  }
+  return SAIL_OK;
+}
+
+int sail_guides_load(sail_ctx* c, const float* n_map, const float* x_map, const double mvp[16], const float eye[3]) {
+  if (!c) return SAIL_E_INVALID;
+  if (!n_map || !x_map || !mvp || !eye) return fail(c, SAIL_E_INVALID, "sail_guides_load: n_map, x_map, mvp and eye are required");
+  if (!c->subs.empty()) return relay(c, sail_guides_load(c->subs[0], n_map, x_map, mvp, eye), c->subs[0]);
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (int rc = ensureGuides(c)) return rc;
+  const size_t np = (size_t)c->share.W * c->share.H;
+  c->guideHave = false;
+  HIPCHK(c, hipMemcpy(c->guideMaps, n_map, np * 16, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->guideMaps + np, x_map, np * 16, hipMemcpyHostToDevice));
+  guidesView(c, mvp, eye);
+  c->guideHave = true;
+  return SAIL_OK;
+}
+
+int sail_guides_read(sail_ctx* c, int which, float* out) {
+  if (!c) return SAIL_E_INVALID;
+  if (!out || which < SAIL_GUIDE_N || which > SAIL_GUIDE_X)
+    return fail(c, SAIL_E_INVALID, "sail_guides_read: map %d of 0..1 and an output are required", which);
+  if (!c->subs.empty()) return relay(c, sail_guides_read(c->subs[0], which, out), c->subs[0]);
+  if (!c->guideHave || !c->guideMaps)
+    return fail(c, SAIL_E_STATE, "sail_guides_read: no guide maps (sail_guides or sail_guides_load first; new rows drop them)");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const size_t np = (size_t)c->share.W * c->share.H;
+  HIPCHK(c, hipMemcpy(out, c->guideMaps + (which == SAIL_GUIDE_X ? np : 0), np * 16, hipMemcpyDeviceToHost));
+  return SAIL_OK;
+}
+
+int sail_use_guides(sail_ctx* c, int on) {
+  if (on != 0 && on != 1) return fail(c, SAIL_E_INVALID, "sail_use_guides: on must be 0 or 1, not %d", on);
+  if (!c) return fail(c, SAIL_E_INVALID, "sail_use_guides: a context is required");
+  if (!c->subs.empty()) return relay(c, sail_use_guides(c->subs[0], on), c->subs[0]);
+  c->useGuides = on != 0;
   return SAIL_OK;
 }
 

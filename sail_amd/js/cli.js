@@ -4,7 +4,8 @@
 // assigns `scene`, then Renderer.update(scene)), render N samples on the GPU and write the frame to disk.
 //
 //   node sail_amd/js/cli.js scene.js [--width 512] [--height 512] [--spp 64] [--bounces 5] [--device -1]
-//        [--noise X [--adaptive] [--min-spp 16] [--max-spp 65536]] [--denoise [--denoise-iterations 4] [--albedo [--albedo-grid 2]]]
+//        [--noise X [--adaptive] [--min-spp 16] [--max-spp 65536]] [--denoise [--denoise-iterations 4] [--albedo [--albedo-grid 2]]
+//         [--guides [--guide-depth 4]]]
 //        [--filter <name>] [--filter-r 'vec2(2.0,2.0)'] [--gamma 2.2] [--deterministic]
 //        [--png out.png] [--pfm out.pfm] [--exr out.exr] [--stats]
 //
@@ -16,6 +17,8 @@
 // floor(N/2) samples, with --noise X it uses the mark of the look before the last. --stats then also prints denoise_ms.
 // --albedo divides the frame by the albedo map of the view before the denoiser and multiplies it back afterwards, so that
 // procedural textures survive; --albedo-grid N (1..4) is the map's sub-pixel grid. --stats then also prints albedo_ms.
+// --guides makes the denoiser read the guide maps of the view, the normal and position of the surface behind mirror and smooth
+// glass, in the AOVs' place; --guide-depth N (0..8) is how many such surfaces are followed. --stats then also prints guides_ms.
 // The script sees `Sail` (the full API) and must assign `scene` (a Sail.Scene with a camera), exactly as the
 // editor text does. --filter overrides scene.filter for the PNG (with --denoise it becomes the denoiser's display transform:
 // color, gamma or tonemapping); without --denoise the PFM and EXR are always the unfiltered mean image.
@@ -43,6 +46,8 @@ function parse(argv) {
       case '--denoise-iterations': opt.denoiseIterations = parseInt(val(), 10); break;
       case '--albedo': opt.albedo = true; break;
       case '--albedo-grid': opt.albedoGrid = parseInt(val(), 10); break;
+      case '--guides': opt.guides = true; break;
+      case '--guide-depth': opt.guideDepth = parseInt(val(), 10); break;
       case '--bounces': opt.bounces = parseInt(val(), 10); break;
       case '--device': opt.device = parseInt(val(), 10); break;
       case '--filter': opt.filter = val(); break;
@@ -70,6 +75,10 @@ function parse(argv) {
   if (opt.albedoGrid !== undefined && !opt.albedo) throw new Error('--albedo-grid needs --albedo');
   if (opt.albedoGrid !== undefined && !(opt.albedoGrid >= 1 && opt.albedoGrid <= 4))
     throw new Error('--albedo-grid needs a number from 1 to 4');
+  if (opt.guides && !opt.denoise) throw new Error('--guides needs --denoise');
+  if (opt.guideDepth !== undefined && !opt.guides) throw new Error('--guide-depth needs --guides');
+  if (opt.guideDepth !== undefined && !(opt.guideDepth >= 0 && opt.guideDepth <= 8))
+    throw new Error('--guide-depth needs a number from 0 to 8');
   if (opt.denoise && opt.noise === undefined && !(opt.spp >= 2))
     throw new Error('--denoise needs --spp 2 or more: it compares the two halves of the samples');
   opt.script = rest[0];
@@ -88,7 +97,7 @@ function loadScene(file) {
 function main() {
   const opt = parse(process.argv.slice(2));
   if (opt.help || !opt.script) {
-    process.stdout.write(fs.readFileSync(__filename, 'utf8').split('\n').slice(2, 21).map((l) => l.replace(/^\/\/ ?/, '')).join('\n') + '\n');
+    process.stdout.write(fs.readFileSync(__filename, 'utf8').split('\n').slice(2, 24).map((l) => l.replace(/^\/\/ ?/, '')).join('\n') + '\n');
     return opt.help ? 0 : 2;
   }
   const scene = loadScene(opt.script);
@@ -98,7 +107,7 @@ function main() {
   const pointwise = ['color', 'gamma', 'tonemapping'].includes(scene.filter.name);
   if (opt.denoise && opt.png && !pointwise)
     throw new Error(`--denoise --png applies the filter to the denoised texel: it needs --filter color, gamma or tonemapping, not ${scene.filter.name}`);
-  const needAov = opt.denoise || ['wavelet', 'normal', 'position'].includes(scene.filter.name);
+  const needAov = (opt.denoise && !opt.guides) || ['wavelet', 'normal', 'position'].includes(scene.filter.name);
   const r = new Sail.Renderer({ width: opt.width, height: opt.height, device: opt.device, maxBounces: opt.bounces,
     deterministic: opt.deterministic, accumulation: 'sum', aov: needAov, display: false });
   r.update(scene);
@@ -111,13 +120,14 @@ function main() {
     r.noiseMark();
     r.renderSamples(scene, opt.spp - Math.floor(opt.spp / 2));
   } else r.renderSamples(scene, opt.spp);
-  let mean, den = null, alb = null;
+  let mean, den = null, alb = null, gui = null;
   if (opt.denoise) {
     if (until && until.history.length < 2)
       throw new Error(`--denoise: the render stopped at its first look (${until.k} spp), which only marks the frame: no second look, so there are no two halves to compare (raise --max-spp above --min-spp)`);
     if (opt.albedo) alb = r.albedo(scene, { grid: opt.albedoGrid === undefined ? 2 : opt.albedoGrid });
+    if (opt.guides) gui = r.guides(scene, { depth: opt.guideDepth === undefined ? 4 : opt.guideDepth });
     den = r.denoise({ iterations: opt.denoiseIterations, display: opt.png ? r.filter.kind : undefined, gamma: r.filter.gamma,
-      albedo: opt.albedo ? { grid: alb.grid } : undefined });
+      albedo: opt.albedo ? { grid: alb.grid } : undefined, guides: opt.guides ? { depth: gui.depth } : undefined });
     mean = den.rgba;
   } else mean = r.readPixels();
   const ms = Number(process.hrtime.bigint() - t0) / 1e6;
@@ -133,6 +143,7 @@ function main() {
     if (opt.adaptive) Object.assign(out, { pixel_samples: until.pixelSamples, frame_pixel_samples: until.framePixelSamples, active_tiles: until.activeTiles });
     if (den) out.denoise_ms = den.info.kernelMs;
     if (alb) Object.assign(out, { albedo_ms: alb.kernelMs, albedo_grid: alb.grid });
+    if (gui) Object.assign(out, { guides_ms: gui.kernelMs, guide_depth: gui.depth });
     process.stdout.write(JSON.stringify(out) + '\n');
   }
   r.destroy();

@@ -938,6 +938,82 @@ napi_value AlbedoRead(napi_env env, napi_callback_info info) {
   if (rc) return throwSail(env, "sail_albedo_read", rc, h->ctx);
   return f;
 }
+// (ctx, mvp f64[16] row-major, eye f32[3], depth) -> {n, x: Float32Array (4 per pixel), hitPixels, followedPixels,
+// truncatedPixels, depth, maxDepth, kernelMs}: the guide maps of a view, kept by the context (sail_guides)
+napi_value Guides(napi_env env, napi_callback_info info) {
+  napi_value a[4];
+  if (!args(env, info, 4, a)) return nullptr;
+  Handle* h;
+  double* m;
+  float* eye;
+  int depth = 0;
+  if (!getHandle(env, a[0], &h) || !viewArgs(env, a[1], a[2], &m, &eye) || !getInt(env, a[3], &depth)) return nullptr;
+  void *pn = nullptr, *px = nullptr;
+  napi_value fn = makeTyped(env, napi_float32_array, (size_t)h->W * h->H * 4, 4, &pn);
+  napi_value fx = makeTyped(env, napi_float32_array, (size_t)h->W * h->H * 4, 4, &px);
+  sail_guides_info n;
+  const int rc = sail_guides(h->ctx, m, eye, depth, (float*)pn, (float*)px, &n);
+  if (rc) return throwSail(env, "sail_guides", rc, h->ctx);
+  napi_value out;
+  NAPI_OK(napi_create_object(env, &out));
+  NAPI_OK(napi_set_named_property(env, out, "n", fn));
+  NAPI_OK(napi_set_named_property(env, out, "x", fx));
+  napi_set_named_property(env, out, "hitPixels", num(env, (double)n.hit_pixels));
+  napi_set_named_property(env, out, "followedPixels", num(env, (double)n.followed_pixels));
+  napi_set_named_property(env, out, "truncatedPixels", num(env, (double)n.truncated_pixels));
+  napi_set_named_property(env, out, "depth", num(env, n.depth));
+  napi_set_named_property(env, out, "maxDepth", num(env, n.max_depth));
+  napi_set_named_property(env, out, "kernelMs", num(env, n.kernel_ms));
+  return out;
+}
+// (ctx, n f32[W H 4], x f32[W H 4], mvp, eye): install a caller's guide maps for a view (sail_guides_load)
+napi_value GuidesLoad(napi_env env, napi_callback_info info) {
+  napi_value a[5];
+  if (!args(env, info, 5, a)) return nullptr;
+  Handle* h;
+  float *nm, *xm;
+  size_t ln, lx;
+  double* m;
+  float* eye;
+  if (!getHandle(env, a[0], &h) || !getArray(env, a[1], napi_float32_array, &nm, &ln) ||
+      !getArray(env, a[2], napi_float32_array, &xm, &lx) || !viewArgs(env, a[3], a[4], &m, &eye))
+    return nullptr;
+  if (ln < (size_t)h->W * h->H * 4 || lx < (size_t)h->W * h->H * 4) {
+    napi_throw_range_error(env, nullptr, "each map needs W * H * 4 floats");
+    return nullptr;
+  }
+  const int rc = sail_guides_load(h->ctx, nm, xm, m, eye);
+  if (rc) return throwSail(env, "sail_guides_load", rc, h->ctx);
+  return undef(env);
+}
+// (ctx, which: 0 Ng, 1 Xg) -> Float32Array (4 per pixel): one of the context's guide maps (sail_guides_read)
+napi_value GuidesRead(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  if (!args(env, info, 2, a)) return nullptr;
+  Handle* h;
+  int which = 0;
+  if (!getHandle(env, a[0], &h) || !getInt(env, a[1], &which)) return nullptr;
+  void* pf = nullptr;
+  napi_value f = makeTyped(env, napi_float32_array, (size_t)h->W * h->H * 4, 4, &pf);
+  const int rc = sail_guides_read(h->ctx, which, (float*)pf);
+  if (rc) return throwSail(env, "sail_guides_read", rc, h->ctx);
+  return f;
+}
+// (ctx, on): the four filters read the guide maps in the AOVs' place (sail_use_guides)
+napi_value UseGuides(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  if (!args(env, info, 2, a)) return nullptr;
+  Handle* h;
+  bool on = false;
+  if (!getHandle(env, a[0], &h)) return nullptr;
+  if (napi_get_value_bool(env, a[1], &on) != napi_ok) {
+    napi_throw_type_error(env, nullptr, "on must be a boolean");
+    return nullptr;
+  }
+  const int rc = sail_use_guides(h->ctx, on ? 1 : 0);
+  if (rc) return throwSail(env, "sail_use_guides", rc, h->ctx);
+  return undef(env);
+}
 // (ctx, timeoutMs) -> whether the scene's run-time kernel is loaded (sail_kernel_ready; -1 waits for its build)
 napi_value KernelReady(napi_env env, napi_callback_info info) {
   napi_value a[2];
@@ -1113,6 +1189,10 @@ napi_value Init(napi_env env, napi_value exports) {
       {"albedo", 0, Albedo, 0, 0, 0, napi_enumerable, 0},
       {"albedoLoad", 0, AlbedoLoad, 0, 0, 0, napi_enumerable, 0},
       {"albedoRead", 0, AlbedoRead, 0, 0, 0, napi_enumerable, 0},
+      {"guides", 0, Guides, 0, 0, 0, napi_enumerable, 0},
+      {"guidesLoad", 0, GuidesLoad, 0, 0, 0, napi_enumerable, 0},
+      {"guidesRead", 0, GuidesRead, 0, 0, 0, napi_enumerable, 0},
+      {"useGuides", 0, UseGuides, 0, 0, 0, napi_enumerable, 0},
       {"kernelReady", 0, KernelReady, 0, 0, 0, napi_enumerable, 0},
       {"kernelInfo", 0, KernelInfo, 0, 0, 0, napi_enumerable, 0},
       {"pick", 0, Pick, 0, 0, 0, napi_enumerable, 0},

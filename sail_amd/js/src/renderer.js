@@ -25,6 +25,9 @@
 // albedo(scene, {grid}) is the albedo map of a view (sail_albedo); denoise({albedo: true}) and
 // temporalFilter({albedo: true}) filter the picture divided by it, so that procedural textures survive
 // (sail_denoise_albedo / sail_temporal_filter_albedo); the map is computed when the option is set and it is stale.
+// guides(scene, {depth}) are the guide maps of a view (sail_guides): the normal and position of the surface behind mirror
+// and smooth glass; denoise({guides: true}) and temporalFilter({guides: true}) read them in the AOVs' place
+// (sail_use_guides) and then need no aov: true; the maps are computed when the option is set and they are stale.
 const native = require('./native');
 const { filterConfig } = require('./filter');
 
@@ -102,6 +105,8 @@ class Renderer {
     // (null: none, or the rows have changed since)
     this._view = null;
     this._albedoKey = null;
+    // the guide maps (sail_guides): the view and depth the context's maps were made for (null as above)
+    this._guidesKey = null;
   }
 
   update(scene) {
@@ -114,10 +119,12 @@ class Renderer {
     scene.sampleCount = 0;
     this._temporalView = false;  // a new scene drops the temporal state
     this._albedoKey = null;      // and the albedo map
+    this._guidesKey = null;      // and the guide maps
   }
 
   updateObjects(scene) {
     this._albedoKey = null;  // new rows drop the albedo map, whichever call brings them
+    this._guidesKey = null;  // and the guide maps
     if (this.objectHistCap !== null) {
       // the motion first: serializeObjects applies and zeroes it. The current view stays; the _restart that follows begins
       // the same view again with the motion pending
@@ -239,16 +246,43 @@ class Renderer {
   // albedo: true, or {amin, grid}: the frame is divided by the albedo map of its view before the filter and multiplied
   // by it afterwards, so that procedural textures survive (sail_denoise_albedo); the map is computed here when the
   // context has none for this view and grid.
-  denoise({ iterations, sigmaL, sigmaX, display, gamma, albedo } = {}) {
-    if (!this.aov) throw new Error('Renderer.denoise reads the normal and position AOVs: create the Renderer with aov: true');
+  // guides: true, or {depth}: the filter reads the guide maps of the frame's view in the AOVs' place (sail_use_guides), so
+  // that a mirror or a pane of glass is filtered by the surface it shows; the maps are computed here when the context has
+  // none for this view and depth. No aov: true is needed then.
+  denoise({ iterations, sigmaL, sigmaX, display, gamma, albedo, guides } = {}) {
+    if (!this.aov && !guides)
+      throw new Error('Renderer.denoise reads the normal and position AOVs: create the Renderer with aov: true, or pass guides');
     const kinds = { color: 0, gamma: 1, tonemapping: 2 };
     let kind;
     if (display !== undefined) {
       kind = typeof display === 'number' ? display : kinds[display];
       if (kind === undefined) throw new Error(`Renderer.denoise: unknown display '${display}' (color | gamma | tonemapping)`);
     }
+    this._useGuides(guides);
     if (albedo) return this.lib.denoise(this.ctx, iterations, sigmaL, sigmaX, kind, gamma, display !== undefined, this._albedoFor(albedo));
     return this.lib.denoise(this.ctx, iterations, sigmaL, sigmaX, kind, gamma, display !== undefined);
+  }
+
+  // The guide maps of a view (sail_guides): per pixel the normal and position of the first surface that scatters, reached
+  // through at most `depth` (0..8; 4 is a policy value) mirror or smooth-glass surfaces, kept by the context for
+  // denoise({guides}) and temporalFilter({guides}). `scene` left out: the view last rendered. Returns {n, x: Float32Array
+  // (4 per pixel: the AOVs' encodings; n.w the depth walked, x.w the object row, -1 = miss), hitPixels, followedPixels,
+  // truncatedPixels, depth, maxDepth, kernelMs}.
+  guides(scene, { depth = 4 } = {}) {
+    if (scene) this._see(scene);
+    if (!this._view) throw new Error('Renderer.guides: no view yet (pass the scene, or render first)');
+    this._guidesKey = null;
+    const r = this.lib.guides(this.ctx, this._view.mvp, this._view.eye, depth);
+    this._guidesKey = this._viewKey(depth);
+    return r;
+  }
+  // set the context's switch for the filter call that follows; computes the maps first when they are stale
+  _useGuides(opt) {
+    if (!opt) { this.lib.useGuides(this.ctx, false); return; }
+    const depth = opt === true || opt.depth === undefined ? 4 : opt.depth;
+    if (!this._view) throw new Error('Renderer: the guides option needs a rendered view');
+    if (this._guidesKey !== this._viewKey(depth)) this.guides(null, { depth });
+    this.lib.useGuides(this.ctx, true);
   }
 
   // The albedo map of a view (sail_albedo): the mean surface colour of the first hits of grid x grid sub-pixel rays per
@@ -307,9 +341,10 @@ class Renderer {
   // 'color', gamma 2.2); display asks for rgba8 as well. Returns {rgba: Float32Array (row 0 = bottom), rgba8?, info: {k,
   // temporalPixels, spatialPixels, nonfinite, iterations, kernelMs, passMs}}. Neither the frame nor the history changes.
   // albedo: true, or {amin, grid}: as in denoise (sail_temporal_filter_albedo); the history stays un-demodulated.
-  temporalFilter({ iterations, sigmaL, sigmaX, minHist, display, gamma, albedo } = {}) {
-    if (!this.aov)
-      throw new Error('Renderer.temporalFilter reads the normal and position AOVs: create the Renderer with aov: true');
+  // guides: true, or {depth}: as in denoise; reprojection keeps using the first hit.
+  temporalFilter({ iterations, sigmaL, sigmaX, minHist, display, gamma, albedo, guides } = {}) {
+    if (!this.aov && !guides)
+      throw new Error('Renderer.temporalFilter reads the normal and position AOVs: create the Renderer with aov: true, or pass guides');
     if (!(this.temporal && this.temporal.moments))
       throw new Error('Renderer.temporalFilter needs the tracked moments: create the Renderer with temporal: {moments: true}');
     const kinds = { color: 0, gamma: 1, tonemapping: 2 };
@@ -318,6 +353,7 @@ class Renderer {
       kind = typeof display === 'number' ? display : kinds[display];
       if (kind === undefined) throw new Error(`Renderer.temporalFilter: unknown display '${display}' (color | gamma | tonemapping)`);
     }
+    this._useGuides(guides);
     if (albedo)
       return this.lib.temporalFilter(this.ctx, iterations, sigmaL, sigmaX, minHist, kind, gamma, display !== undefined, this._albedoFor(albedo));
     return this.lib.temporalFilter(this.ctx, iterations, sigmaL, sigmaX, minHist, kind, gamma, display !== undefined);
