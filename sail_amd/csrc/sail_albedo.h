@@ -5,18 +5,14 @@
 #include <stdint.h>
 #include "sail_denoise.h"
 #include "sail_tfilter.h"
-
-struct SailPrim;
+#include "sail_temporal.h"
 
 struct SailAlbedoArgs {
-  const SailPrim* prims;    // the scene's rows, swept in order
+  SailViewArgs V;           // the rows and the view
   const float* texparams;   // the scene's texParams table
-  int n, tn;
+  int tn;
   uint32_t texMask;         // the scene's own texture plugins: a texture outside it gives 0, as in a render
-  float d[4][3];            // corner directions of the zero-jitter inverse (the host's cornerDirs)
-  float eye[3];
-  int W, H;
-  int grid;                 // g: g * g sub-pixel rays per pixel, 1..4
+  int grid;                // g: g * g sub-pixel rays per pixel, 1..4
   float4* A;                // out: (mean surface colour, rays that hit); no hit stores (1, 1, 1, 0)
   uint32_t* tileHit;        // out, per 16x16 tile: pixels with a hit (A.w > 0)
   uint32_t* tilePartial;    // out, per tile: pixels where some but not all rays hit (0 < A.w < g * g)

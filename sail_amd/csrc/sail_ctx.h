@@ -98,6 +98,8 @@ extern Rccl g_rccl;  // sail_multi.cpp
 
 // union of the primitives' finite bounds and its diagonal (sceneBox)
 struct SceneBox { double lo[3], hi[3]; double diag; };
+// the view a map of sail_post.cpp belongs to (setView, sameView): P*MV in f32, row-major, and the eye
+struct View { float m[16]; float eye[3]; };
 
 // One run-time kernel of a context: the spec it holds (sail_jit_hold), whether its code object is still being built, is
 // loaded or failed, the loaded pair, and why a build failed. The hold is what keeps the build worker from skipping the
@@ -252,7 +254,7 @@ struct sail_ctx {
   void* tpWork = nullptr;
   float4 *tpGcur = nullptr, *tpGprev = nullptr, *tpHist = nullptr, *tpR = nullptr, *tpOut = nullptr;
   bool tpHaveCur = false, tpHavePrev = false;
-  struct TpView { float m[16]; float eye[3]; } tpCur{}, tpPrev{};
+  View tpCur{}, tpPrev{};
   uint64_t tpHitPixels = 0;
   // Moment tracking (sail_temporal_moments): one block of three float4 maps (mu1, mu2, mm, 0) and a count per tile,
   // allocated when tracking is switched on and freed when it is switched off; the pointers are swapped with the colour
@@ -274,7 +276,7 @@ struct sail_ctx {
   // are gone); on a multi-device context device 0's sub-context holds it.
   float4* albMap = nullptr;
   bool albHave = false;
-  TpView albView{};
+  View albView{};
   // Guide maps (sail_guides / sail_guides_load): two float4 maps (Ng, then Xg) and three counts per 16x16 tile in one
   // block, allocated on first use, with the view they belong to, kept and invalidated as the albedo map is. useGuides
   // (sail_use_guides): the four filters read them in the AOVs' place. On a multi-device context device 0's sub-context
@@ -282,7 +284,7 @@ struct sail_ctx {
   float4* guideMaps = nullptr;
   bool guideHave = false;
   bool useGuides = false;
-  TpView guideView{};
+  View guideView{};
   nccl_comm_t comm = nullptr;
   int commRanks = 0, commRank = 0;
   // Reduced frame (root of sail_reduce / device 0 of a multi-device context): the sum of every rank's
@@ -390,7 +392,8 @@ void freePost(sail_ctx* c);
 inline const float4* shownAccum(const sail_ctx* c) { return c->reduced ? c->frame : c->accum; }
 inline const float4* shownAovN(const sail_ctx* c) { return c->reduced && c->frameN ? c->frameN : c->aovN; }
 inline const float4* shownAovP(const sail_ctx* c) { return c->reduced && c->frameP ? c->frameP : c->aovP; }
-// the frame's 16x16 tiles (the post passes keep a count or more per tile)
+// the frame's pixels and its 16x16 tiles (the post passes keep a count or more per tile)
+inline size_t pixels(const sail_ctx* c) { return (size_t)c->share.W * c->share.H; }
 inline size_t tiles16(const sail_ctx* c) { return (size_t)((c->share.W + 15) / 16) * (size_t)((c->share.H + 15) / 16); }
 
 #pragma GCC visibility pop

@@ -2,10 +2,12 @@
 // staged-sample accumulation (sail_accum_kernel), the multi-device sum and the -0 fill of unowned tiles, the display
 // filter (sail_filter_kernel: the reference's display pass, main/fsrender.glsl + filter/window.glsl:26-44,
 // tonemapping.glsl, gamma.glsl, color.glsl), the picker, the spec-math probe and the phase-timing readout. They use the
-// trace kernels' vector types, primT and accumulateSample (sail_geom.h, sail_shade.h) and sail_trace.hip's tile index
+// trace kernels' vector types and accumulateSample (sail_geom.h, sail_shade.h), the view passes' first-hit sweep
+// (sail_view.h: the picker; included here, never from sail_trace.hip) and sail_trace.hip's tile index
 // and g_sailPhase. No part of a run-time kernel's text: an edit here leaves the run-time kernels' cache keys alone.
 #include <hip/hip_runtime.h>
 #include "sail_trace.hip"
+#include "sail_view.h"
 
 // ---- sample groups: add the staged per-sample radiance to the accumulator in sample order ---------------------
 namespace {
@@ -221,7 +223,7 @@ extern "C" __global__ void __launch_bounds__(256) sail_filter_kernel(SailFilterA
   }
 }
 
-// ---- picking (replaces the CPU picker, src/core/pickup.js:46-66): the trace kernel's own primitive sweep
+// ---- picking (replaces the CPU picker, src/core/pickup.js:46-66): the view passes' first-hit sweep (sail_view.h)
 // for caller-supplied rays; index = the first object row with the smallest distance, -1 on a miss ---------------
 extern "C" __global__ void __launch_bounds__(64) sail_pick_kernel(const SailPrim* prims, int n, const float* rays,
                                                                    int count, int32_t* index, float* tOut) {
@@ -229,16 +231,9 @@ extern "C" __global__ void __launch_bounds__(64) sail_pick_kernel(const SailPrim
   if (i >= count) return;
   const float* q = rays + 6 * (size_t)i;
   const Ray r = mkRay(v3(q[0], q[1], q[2]), v3(q[3], q[4], q[5]));
-  Ctx c;
-  c.kShapes = ~0u;
-  float best = kMaxDistance;
-  int bi = -1;
-  for (int k = 0; k < n; k++) {
-    const float t = primT(c, constRow<SailPrim>(prims, k), r, nullptr);
-    if (t < best) { best = t; bi = k; }
-  }
-  index[i] = bi;
-  tOut[i] = best;
+  const Sweep sw = sv::firstHit(sv::flatCtx(prims, n, nullptr, 0, 0u, 0u, 0u), prims, n, r);
+  index[i] = sw.bi;
+  tOut[i] = sw.best;
 }
 
 // ---- spec-math probe for the CPU/GPU bit-parity test ----------------------------------------------------------------

@@ -3,19 +3,15 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-struct SailPrim;
+#include "sail_temporal.h"
 
 struct SailGuidesArgs {
-  const SailPrim* prims;    // the scene's rows, swept in order
+  SailViewArgs V;           // the rows and the view
   const float* texparams;   // the scene's texParams table: the material rows of the walk
-  int n, tn;
+  int tn;
   uint32_t matMask;         // the scene's own material plugins: a category outside it is not followed, as in a render
   uint32_t texMask;         // the scene's own texture plugins (the hit record's surface colour)
-  float d[4][3];            // corner directions of the zero-jitter inverse (the host's cornerDirs)
-  float eye[3];
-  int W, H;
-  int depth;                // D: mirror and smooth glass are followed at most this many times, 0..8
+  int depth;               // D: mirror and smooth glass are followed at most this many times, 0..8
   float4* Ng;               // out: (0.5 n + 0.5, depth walked); a miss stores (0.5, 0.5, 0.5, 0)
   float4* Xg;               // out: (normalize(p), row); a miss stores (NaN, NaN, NaN, -1)
   uint32_t* tileHit;        // out, per 16x16 tile: pixels whose first ray hit (Xg.w >= 0)

@@ -11,8 +11,7 @@
 //
 // MI355X design ("sail_guides_kernel"):
 //  * one 256-thread workgroup per 16x16 tile, one lane per pixel, each wave a 16x4 strip (the post kernels' shape);
-//  * the first ray is the G-buffer pass's; the sweep is sail_pick_kernel's: primT over all rows in order, a hit on a
-//    strict `<`; the row index is wave-uniform, so the rows arrive through the scalar cache (constRow);
+//  * the first ray is the G-buffer pass's and every sweep the view passes' first-hit sweep (sail_view.h);
 //  * the hit record is the generic one of all nine shapes (hitRecordU), the frame is shadeBounce's, the direction is
 //    material()'s with only the mirror and glass plugins compiled in: radiance, throughput and the hash are never made;
 //  * lanes leave the walk at different depths. The loop runs while any lane of the wave is alive, finished lanes masked:
@@ -23,41 +22,27 @@
 //    on the host;
 //  * lanes outside ragged tiles load nothing and store nothing;
 //  * plain vector stores only, no atomics: equal data give equal bits.
-// mkRay, primT, constRow and hitRecordU are sail_geom.h's, material() is sail_shade.h's. No part of a run-time kernel's
+// mkRay and hitRecordU are sail_geom.h's, material() is sail_shade.h's. No part of a run-time kernel's
 // text (sail_amd/gen_jit_src.py). Built with the library's flags (no contraction, no fast math: `/` is the IEEE divide).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "sail_geom.h"
+#include "sail_view.h"
 #include "sail_shade.h"
 #include "sail_post.h"
 #include "sail_guides.h"
 
 extern "C" __global__ void __launch_bounds__(256) sail_guides_kernel(SailGuidesArgs A) {
   __shared__ uint32_t sCnt[3][4];
+  const SailViewArgs& V = A.V;
   const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
-  const bool inside = x < A.W && y < A.H;
-  // a flat kernel's context: every shape and texture compiled in, of the materials the two that are followed; the
-  // scene's own masks decide what a row shows, as in a render
-  Ctx c;
-  c.tp = A.texparams; c.lt = nullptr; c.lightObjRow = nullptr; c.typeMasks = nullptr;
-  c.prims = A.prims; c.cprims = A.prims; c.tpl = A.texparams;
-  c.rowCopy = false; c.tpCopy = false;
-  c.n = A.n; c.tn = A.tn; c.ln = 0;
-  c.matMask = A.matMask; c.texMask = A.texMask; c.lightMask = 0u;
-  c.fcx = 0.0f; c.fcy = 0.0f;
-  c.shadowAnyHit = 0;
-  c.cullPrims = 0; c.cullFma = 0; c.cullPrimary = 0;
-  c.kShapes = ~0u; c.kMats = (1u << SAIL_MIRROR) | (1u << SAIL_GLASS); c.kTex = ~0u; c.kLights = 0u;
+  const bool inside = x < V.W && y < V.H;
+  // of the materials the two that are followed are compiled in
+  const Ctx c = sv::flatCtx(V.prims, V.n, A.texparams, A.tn, A.matMask, A.texMask, (1u << SAIL_MIRROR) | (1u << SAIL_GLASS));
   Seg ray;
-  ray.o = v3(A.eye[0], A.eye[1], A.eye[2]);
+  ray.o = sv::eye(V);
   ray.d = v3s(0.0f);
-  if (inside) {  // the G-buffer pass's ray (sail_gbuffer_kernel)
-    const float s = ((float)x + 0.5f) / (float)A.W, t = ((float)y + 0.5f) / (float)A.H;
-    const bool tri0 = s + t <= 1.0f;
-    const V3 d0 = v3(A.d[0][0], A.d[0][1], A.d[0][2]), d1 = v3(A.d[1][0], A.d[1][1], A.d[1][2]);
-    const V3 d2 = v3(A.d[2][0], A.d[2][1], A.d[2][2]), d3 = v3(A.d[3][0], A.d[3][1], A.d[3][2]);
-    ray.d = tri0 ? (d0 + (d2 - d0) * s + (d1 - d0) * t) : (d3 + (d1 - d3) * (1.0f - s) + (d2 - d3) * (1.0f - t));
-  }
+  // the G-buffer pass's ray (sail_gbuffer_kernel)
+  if (inside) ray.d = sv::pixelDir(V, ((float)x + 0.5f) / (float)V.W, ((float)y + 0.5f) / (float)V.H);
   V3 gn = v3s(0.0f), gp = v3s(0.0f);
   int id = -1, depth = 0;
   bool alive = inside, truncated = false;
@@ -65,13 +50,7 @@ extern "C" __global__ void __launch_bounds__(256) sail_guides_kernel(SailGuidesA
   while (__any(alive)) {
     if (alive) {
       const Ray r = mkRay(ray.o, ray.d);
-      // sail_pick_kernel's sweep: every row in order, the first row with the smallest distance
-      Sweep sw;
-      sw.best = kMaxDistance; sw.bi = -1; sw.bhl = v3s(0.0f);  // the local hit point is recomputed (hitRecord<true>)
-      for (int k = 0; k < A.n; k++) {
-        const float tk = primT(c, constRow<SailPrim>(A.prims, k), r, nullptr);
-        if (tk < sw.best) { sw.best = tk; sw.bi = k; }
-      }
+      const Sweep sw = sv::firstHit(c, V.prims, V.n, r);
       alive = false;  // a miss keeps the surface recorded last
       if (sw.bi >= 0) {
         const Hit ins = hitRecordU<true>(c, r, sw);
@@ -105,7 +84,7 @@ extern "C" __global__ void __launch_bounds__(256) sail_guides_kernel(SailGuidesA
   }
   const bool hit = id >= 0;
   if (inside) {
-    const size_t pix = (size_t)y * A.W + x;
+    const size_t pix = (size_t)y * V.W + x;
     float4 ng = make_float4(0.5f, 0.5f, 0.5f, 0.0f);
     float4 xg = make_float4(__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""), -1.0f);
     if (hit) {  // the AOVs' encoding (sail_trace_kernel)
@@ -121,6 +100,6 @@ extern "C" __global__ void __launch_bounds__(256) sail_guides_kernel(SailGuidesA
 }
 
 hipError_t sail_launch_guides(const SailGuidesArgs& A, hipStream_t s) {
-  hipLaunchKernelGGL(sail_guides_kernel, dim3((A.W + 15) / 16, (A.H + 15) / 16), dim3(256), 0, s, A);
+  hipLaunchKernelGGL(sail_guides_kernel, dim3((A.V.W + 15) / 16, (A.V.H + 15) / 16), dim3(256), 0, s, A);
   return hipGetLastError();
 }

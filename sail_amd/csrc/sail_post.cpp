@@ -10,45 +10,148 @@
 
 namespace {
 
-// the a-trous passes' work buffers (sail_denoise and sail_temporal_filter share them), allocated on first use:
-// cvA | cvB | g0 (16 B each) | g1 (8 B) | var (4 B) | rgba8 (4 B) per pixel, then a count per 16x16 tile
-int ensureDenoiseWork(sail_ctx* c) {
-  const size_t nt = tiles16(c), np = (size_t)c->share.W * c->share.H;
-  return allocOnce(c, &c->denoiseWork, np * 64 + nt * 4, "denoise work buffers");
+// ---- the work blocks' layouts ---------------------------------------------------------------------------------------------------
+// Every block is arrays of np pixels or nt 16x16 tiles, back to back, the widest element first (each array is aligned to
+// its own type). A block is described once, by a carve() that names its arrays in order: with a null base a Carve only
+// adds up the bytes, so the size that is allocated (workBytes) and the typed pointers (workAt) cannot disagree.
+struct Carve {
+  char* base;
+  size_t off = 0;
+  template <class T> constexpr void operator()(T*& p, size_t count) {
+    p = base ? (T*)(base + off) : nullptr;
+    off += count * sizeof(T);
+  }
+};
+template <class L> constexpr size_t workBytes(size_t np, size_t nt) {
+  Carve k{nullptr};
+  L l{};
+  l.carve(k, np, nt);
+  return k.off;
+}
+template <class L> L workAt(const sail_ctx* c, void* base) {
+  Carve k{(char*)base};
+  L l{};
+  l.carve(k, pixels(c), tiles16(c));
+  return l;
+}
+// allocated on first use and kept for the context's life
+template <class L, class T> int ensureWork(sail_ctx* c, T** block, const char* what) {
+  return allocOnce(c, block, workBytes<L>(pixels(c), tiles16(c)), what);
 }
 
+// the a-trous passes' work buffers (sail_denoise and sail_temporal_filter share them; sail_ctx.denoiseWork)
 struct DenoiseWork {
-  float4* cv[2];
-  float4* g0;
+  float4 *cv[2], *g0;
   float2* g1;
   float* var;
-  uint32_t* u8;
-  uint32_t* bad;
+  uint32_t *u8, *bad;
+  constexpr void carve(Carve& k, size_t np, size_t nt) { k(cv[0], np); k(cv[1], np); k(g0, np); k(g1, np); k(var, np); k(u8, np); k(bad, nt); }
 };
-DenoiseWork denoiseWork(const sail_ctx* c) {
-  const size_t np = (size_t)c->share.W * c->share.H;
-  char* base = (char*)c->denoiseWork;
-  return {{(float4*)base, (float4*)(base + np * 16)}, (float4*)(base + np * 32), (float2*)(base + np * 48),
-          (float*)(base + np * 56), (uint32_t*)(base + np * 60), (uint32_t*)(base + np * 64)};
+// the temporal maps (tpWork): `maps` in the order the context's pointers start in, G_cur, G_prev, Hist, R, Out (a
+// committed view swaps those, never these); the RGBA8 map; the counts of begin (hit, hist) and resolve (hist, bad)
+struct TemporalWork {
+  float4* maps[5];
+  uint32_t *out8, *tileHit, *tileHist, *tileBad;
+  constexpr void carve(Carve& k, size_t np, size_t nt) {
+    for (float4*& m : maps) k(m, np);
+    k(out8, np); k(tileHit, nt); k(tileHist, nt); k(tileBad, nt);
+  }
+};
+// the moment maps (tpMom) as the context's pointers start, Mhist, MR, Mout, and the filter's count of temporal pixels
+struct MomentWork {
+  float4* maps[3];
+  uint32_t* tileTemporal;
+  constexpr void carve(Carve& k, size_t np, size_t nt) {
+    for (float4*& m : maps) k(m, np);
+    k(tileTemporal, nt);
+  }
+};
+struct AlbedoWork {  // albMap
+  float4* map;
+  uint32_t *tileHit, *tilePartial;
+  constexpr void carve(Carve& k, size_t np, size_t nt) { k(map, np); k(tileHit, nt); k(tilePartial, nt); }
+};
+struct GuideWork {  // guideMaps
+  float4 *n, *x;
+  uint32_t *tileHit, *tileFollowed, *tileTruncated;
+  constexpr void carve(Carve& k, size_t np, size_t nt) { k(n, np); k(x, np); k(tileHit, nt); k(tileFollowed, nt); k(tileTruncated, nt); }
+};
+struct GbufferScratch {  // sail_gbuffer's own, freed by the call
+  float4* G;
+  float (*rays)[6];
+  float* t;
+  constexpr void carve(Carve& k, size_t np, size_t) { k(G, np); k(rays, np); k(t, np); }
+};
+template <class L> constexpr bool sized(size_t perPixel, size_t perTile) {
+  return workBytes<L>(1, 1) == perPixel + perTile && workBytes<L>(33 * 17, 3 * 2) == perPixel * (33 * 17) + perTile * (3 * 2);
 }
+static_assert(sized<DenoiseWork>(64, 4) && sized<TemporalWork>(84, 12) && sized<MomentWork>(48, 4) &&
+                  sized<AlbedoWork>(16, 8) && sized<GuideWork>(32, 12) && sized<GbufferScratch>(44, 0),
+              "a work block's size is part of what the context allocates per frame: it does not change");
+
+DenoiseWork denoiseWork(const sail_ctx* c) { return workAt<DenoiseWork>(c, c->denoiseWork); }
+TemporalWork temporalWork(const sail_ctx* c) { return workAt<TemporalWork>(c, c->tpWork); }
+MomentWork momentWork(const sail_ctx* c) { return workAt<MomentWork>(c, c->tpMom); }
+AlbedoWork albedoWork(const sail_ctx* c) { return workAt<AlbedoWork>(c, c->albMap); }
+GuideWork guideWork(const sail_ctx* c) { return workAt<GuideWork>(c, c->guideMaps); }
+
+// ---- what the calls share -------------------------------------------------------------------------------------------------------
+void setView(View* v, const double mvp[16], const float eye[3]) {
+  memset(v, 0, sizeof *v);
+  for (int i = 0; i < 16; i++) v->m[i] = (float)mvp[i];
+  memcpy(v->eye, eye, sizeof v->eye);
+}
+bool sameView(const View& a, const View& b) { return memcmp(&a, &b, sizeof a) == 0; }
+
+template <class T> hipError_t toHost(void* host, const T* dev, size_t count) {
+  return hipMemcpy(host, dev, count * sizeof(T), hipMemcpyDeviceToHost);
+}
+// the tail of every read and load call: the stream idle, then one blocking copy of `count` float4 texels
+int moveMap(sail_ctx* c, void* dst, const void* src, size_t count, hipMemcpyKind kind) {
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(dst, src, count * sizeof(float4), kind));
+  return SAIL_OK;
+}
+int readMap(sail_ctx* c, const float4* dev, float* host, size_t count) { return moveMap(c, host, dev, count, hipMemcpyDeviceToHost); }
+int loadMap(sail_ctx* c, float4* dev, const float* host, size_t count) { return moveMap(c, dev, host, count, hipMemcpyHostToDevice); }
+
+// Times the passes of one call on the context's stream, on top of PooledEvents: mark() records the next event, run()
+// launches or copies, and both do nothing once a step has failed (e carries the first failure). finish() synchronises
+// the stream and gives ms[i], the time between marks i and i + 1, and the time from the first mark to the last.
+struct PassTimer {
+  sail_ctx* c;
+  PooledEvents ev;
+  int marks = 0;
+  hipError_t e = hipSuccess;
+  PassTimer(sail_ctx* ctx, int want) : c(ctx), ev(ctx, want) {}
+  int rc() const { return ev.rc; }  // the pool could not give the events: nothing was started
+  void mark() { if (e == hipSuccess) e = hipEventRecord(ev[marks++], c->stream); }
+  template <class Step> void run(Step step) { if (e == hipSuccess) e = step(); }
+  hipError_t finish(float* ms, float* total = nullptr) {
+    run([&] { return hipStreamSynchronize(c->stream); });
+    for (int i = 0; i + 1 < marks; i++) run([&] { return hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]); });
+    if (total) run([&] { return hipEventElapsedTime(total, ev[0], ev[marks - 1]); });
+    return e;
+  }
+  template <class Step> hipError_t one(Step step, float* ms) { mark(); run(step); mark(); return finish(ms); }  // one span
+};
 
 // What sail_denoise and sail_temporal_filter share: `prepare` launches the pass that fills (cv[0], g0, g1) and the
 // per-tile counts, then the a-trous passes run with steps 1, 2, 4, ..., an event round every pass (ms[0] = prepare,
-// ms[1..] = the passes); the stream is synchronised and the outputs that are asked for are copied back.
+// ms[1..] = the passes; T holds iterations + 2 events); the stream is synchronised and the outputs that are asked for are
+// copied back.
 // With a map `alb` (the demodulated calls) the last pass is the remodulating instance.
 template <class Prepare>
-hipError_t runAtrous(sail_ctx* c, const DenoiseWork& w, Prepare prepare, int iterations, float sigma_l, float sigma_x,
-                     int display, float gamma_c, float* out_rgba, float* out_var, uint8_t* out_rgba8, float ms[8],
-                     float* total, int* rc, const float4* alb = nullptr, float amin = 0.0f) {
-  const size_t np = (size_t)c->share.W * c->share.H;
-  const int nev = iterations + 2;  // before the prepare pass, then after every pass
-  PooledEvents ev(c, nev);
-  if ((*rc = ev.rc)) return hipSuccess;
-  hipError_t e = hipEventRecord(ev[0], c->stream);
-  if (e == hipSuccess) e = prepare();
-  if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
+hipError_t runAtrous(sail_ctx* c, PassTimer& T, const DenoiseWork& w, Prepare prepare, int iterations, float sigma_l,
+                     float sigma_x, int display, float gamma_c, float* out_rgba, float* out_var, uint8_t* out_rgba8,
+                     float ms[8], float* total, const float4* alb = nullptr, float amin = 0.0f) {
+  const size_t np = pixels(c);
+  T.mark();
+  T.run(prepare);
+  T.mark();
   int cur = 0;
-  for (int it = 0; it < iterations && e == hipSuccess; it++) {
+  for (int it = 0; it < iterations && T.e == hipSuccess; it++) {
     const bool last = it == iterations - 1;
     SailDenoiseAtrousArgs B;
     memset(&B, 0, sizeof B);
@@ -64,23 +167,17 @@ hipError_t runAtrous(sail_ctx* c, const DenoiseWork& w, Prepare prepare, int ite
     const float sx = sigma_x * (float)B.step;
     B.sxs = sx * sx;
     B.display = display; B.gammaC = gamma_c;
-    if (last && alb) {
-      SailDenoiseAtrousRemodArgs R;
-      memset(&R, 0, sizeof R);
-      R.P = B; R.alb = alb; R.amin = amin;
-      e = sail_launch_denoise_atrous_remod(R, c->stream);
-    } else {
-      e = sail_launch_denoise_atrous(B, c->stream);
-    }
-    if (e == hipSuccess) e = hipEventRecord(ev[it + 2], c->stream);
+    SailDenoiseAtrousRemodArgs R;
+    memset(&R, 0, sizeof R);
+    R.P = B; R.alb = alb; R.amin = amin;
+    T.run([&] { return (last && alb) ? sail_launch_denoise_atrous_remod(R, c->stream) : sail_launch_denoise_atrous(B, c->stream); });
+    T.mark();
     cur ^= 1;
   }
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  for (int i = 0; i + 1 < nev && e == hipSuccess; i++) e = hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]);
-  if (e == hipSuccess) e = hipEventElapsedTime(total, ev[0], ev[nev - 1]);
-  if (e == hipSuccess && out_rgba) e = hipMemcpy(out_rgba, w.cv[cur], np * 16, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && out_var) e = hipMemcpy(out_var, w.var, np * 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && out_rgba8) e = hipMemcpy(out_rgba8, w.u8, np * 4, hipMemcpyDeviceToHost);
+  hipError_t e = T.finish(ms, total);
+  if (e == hipSuccess && out_rgba) e = toHost(out_rgba, w.cv[cur], np);
+  if (e == hipSuccess && out_var) e = toHost(out_var, w.var, np);
+  if (e == hipSuccess && out_rgba8) e = toHost(out_rgba8, w.u8, np);
   return e;
 }
 
@@ -89,7 +186,7 @@ hipError_t runAtrous(sail_ctx* c, const DenoiseWork& w, Prepare prepare, int ite
 // the three moment maps of a context that tracks them (sail_temporal_moments), zeroed on its stream
 hipError_t zeroMoments(sail_ctx* c) {
   if (!c->tpMom) return hipSuccess;
-  return hipMemsetAsync(c->tpMom, 0, (size_t)c->share.W * c->share.H * 48, c->stream);
+  return hipMemsetAsync(c->tpMom, 0, workBytes<MomentWork>(pixels(c), 0), c->stream);  // the maps, not the tile counts
 }
 
 // nothing is pending for the next sail_temporal_begin any more (sail_move_objects)
@@ -123,16 +220,14 @@ namespace {
 bool aminOk(float amin) { return std::isfinite(amin) && amin > 0.0f; }
 
 // The normal and position maps a filter reads: the shown AOVs, or with sail_use_guides the guide maps (Ng, then Xg)
-const float4* guideN(const sail_ctx* c) { return c->guideMaps; }
-const float4* guideX(const sail_ctx* c) { return c->guideMaps + (size_t)c->share.W * c->share.H; }
-const float4* filterN(const sail_ctx* c) { return c->useGuides ? guideN(c) : shownAovN(c); }
-const float4* filterX(const sail_ctx* c) { return c->useGuides ? guideX(c) : shownAovP(c); }
+const float4* filterN(const sail_ctx* c) { return c->useGuides ? guideWork(c).n : shownAovN(c); }
+const float4* filterX(const sail_ctx* c) { return c->useGuides ? guideWork(c).x : shownAovP(c); }
 // what a filter refuses about them (temporal: the maps must belong to the current temporal view)
 int filterGuides(sail_ctx* c, const char* who, bool temporal) {
   if (!c->useGuides) return SAIL_OK;
   if (!c->guideHave || !c->guideMaps)
     return fail(c, SAIL_E_STATE, "%s: no guide maps (sail_guides or sail_guides_load first; new rows drop them)", who);
-  if (temporal && memcmp(&c->guideView, &c->tpCur, sizeof c->guideView) != 0)
+  if (temporal && !sameView(c->guideView, c->tpCur))
     return fail(c, SAIL_E_STATE, "%s: the guide maps belong to another view than the current temporal view", who);
   return SAIL_OK;
 }
@@ -168,7 +263,7 @@ int denoiseCall(sail_ctx* c, const char* who, bool demod, const sail_denoise_par
     return fail(c, SAIL_E_STATE, "%s: no albedo map (sail_albedo or sail_albedo_load first; new rows drop it)", who);
   if (int rc = filterGuides(c, who, false)) return rc;
   const size_t nt = tiles16(c);
-  if (int rc = ensureDenoiseWork(c)) return rc;
+  if (int rc = ensureWork<DenoiseWork>(c, &c->denoiseWork, "denoise work buffers")) return rc;
   const DenoiseWork w = denoiseWork(c);
   SailDenoisePrepareArgs A;
   memset(&A, 0, sizeof A);
@@ -178,17 +273,17 @@ int denoiseCall(sail_ctx* c, const char* who, bool demod, const sail_denoise_par
   A.mix = c->accumMode == SAIL_ACCUM_MIX;
   A.kf = (float)c->k; A.hf = (float)c->noiseK;
   float ms[8] = {}, total = 0.0f;
-  int rc = SAIL_OK;
   SailDenoisePrepareDemodArgs D;
   memset(&D, 0, sizeof D);
   D.P = A; D.alb = c->albMap; D.amin = amin;
-  hipError_t e = runAtrous(c, w, [&] { return demod ? sail_launch_denoise_prepare_demod(D, c->stream)
-                                                      : sail_launch_denoise_prepare(A, c->stream); },
+  PassTimer T(c, p.iterations + 2);
+  if (T.rc()) return T.rc();
+  hipError_t e = runAtrous(c, T, w, [&] { return demod ? sail_launch_denoise_prepare_demod(D, c->stream)
+                                                         : sail_launch_denoise_prepare(A, c->stream); },
                            p.iterations, p.sigma_l, p.sigma_x, p.display, p.gamma_c, out_rgba, out_var, out_rgba8, ms, &total,
-                           &rc, demod ? c->albMap : nullptr, amin);
-  if (rc) return rc;
+                           demod ? c->albMap : nullptr, amin);
   std::vector<uint32_t> bad(nt);
-  if (e == hipSuccess) e = hipMemcpy(bad.data(), w.bad, nt * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = toHost(bad.data(), w.bad, nt);
   if (e != hipSuccess) return fail(c, SAIL_E_HIP, "%s: %s", who, hipGetErrorString(e));
   if (info) {
     memset(info, 0, sizeof *info);
@@ -248,29 +343,24 @@ int temporalState(sail_ctx* c, const char* who) {
   return SAIL_OK;
 }
 
-uint32_t* temporalOut8(const sail_ctx* c) { return (uint32_t*)((char*)c->tpWork + (size_t)c->share.W * c->share.H * 80); }
-uint32_t* temporalCounts(const sail_ctx* c) { return temporalOut8(c) + (size_t)c->share.W * c->share.H; }
-
 int ensureTemporal(sail_ctx* c) {
   if (c->tpWork) return SAIL_OK;
-  const size_t np = (size_t)c->share.W * c->share.H;
-  // five float4 maps (16 B each) | rgba8 (4 B) per pixel, then three counts per tile
-  if (int rc = allocOnce(c, &c->tpWork, np * 84 + tiles16(c) * 12, "temporal maps")) return rc;
-  float4* base = (float4*)c->tpWork;
-  c->tpGcur = base; c->tpGprev = base + np; c->tpHist = base + 2 * np; c->tpR = base + 3 * np; c->tpOut = base + 4 * np;
+  if (int rc = ensureWork<TemporalWork>(c, &c->tpWork, "temporal maps")) return rc;
+  const TemporalWork w = temporalWork(c);
+  c->tpGcur = w.maps[0]; c->tpGprev = w.maps[1]; c->tpHist = w.maps[2]; c->tpR = w.maps[3]; c->tpOut = w.maps[4];
   return SAIL_OK;
 }
 
-// the G-buffer pass's arguments for a view: the corner directions of a sample without jitter
-int gbufferArgs(sail_ctx* c, const char* who, const double mvp[16], const float eye[3], SailGbufferArgs* A) {
+// what a view pass takes (sail_view.h): the scene's rows and, for a view, the corner directions of a sample without jitter
+int viewArgs(sail_ctx* c, const char* who, const double mvp[16], const float eye[3], SailViewArgs* V) {
   float inv[16];
   if (sail_jitter_inverse(mvp, 0.0, 0.0, c->share.W, c->share.H, inv) != SAIL_OK)
     return fail(c, SAIL_E_INVALID, "%s: the camera matrix is singular", who);
-  memset(A, 0, sizeof *A);
-  A->prims = c->prims; A->n = c->facts.n;
-  cornerDirs(inv, eye, A->d);
-  memcpy(A->eye, eye, sizeof A->eye);
-  A->W = c->share.W; A->H = c->share.H;
+  memset(V, 0, sizeof *V);
+  V->prims = c->prims; V->n = c->facts.n;
+  cornerDirs(inv, eye, V->d);
+  memcpy(V->eye, eye, sizeof V->eye);
+  V->W = c->share.W; V->H = c->share.H;
   return SAIL_OK;
 }
 
@@ -290,26 +380,28 @@ int sail_gbuffer(sail_ctx* c, const double mvp[16], const float eye[3], float* r
   if (!c->subs.empty()) return relay(c, sail_gbuffer(c->subs[0], mvp, eye, rays6, id, t, xyz), c->subs[0]);
   if (!c->haveScene) return fail(c, SAIL_E_STATE, "sail_gbuffer: no scene (call sail_set_scene first)");
   SailGbufferArgs A;
-  if (int rc = gbufferArgs(c, "sail_gbuffer", mvp, eye, &A)) return rc;
+  memset(&A, 0, sizeof A);
+  if (int rc = viewArgs(c, "sail_gbuffer", mvp, eye, &A.V)) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   if (int rc = sail_sync(c)) return rc;
-  const size_t np = (size_t)c->share.W * c->share.H;
-  void* work = nullptr;  // G (16 B) | rays (24 B) | t (4 B) per pixel
-  if (hipMalloc(&work, np * 44) != hipSuccess) return fail(c, SAIL_E_OOM, "G-buffer scratch");
-  A.G = (float4*)work;
-  A.rays = rays6 ? (float*)((char*)work + np * 16) : nullptr;
-  A.t = t ? (float*)((char*)work + np * 40) : nullptr;
-  std::vector<float> g((id || xyz) ? np * 4 : 0);
+  const size_t np = pixels(c);
+  void* work = nullptr;
+  if (hipMalloc(&work, workBytes<GbufferScratch>(np, 0)) != hipSuccess) return fail(c, SAIL_E_OOM, "G-buffer scratch");
+  const GbufferScratch w = workAt<GbufferScratch>(c, work);
+  A.G = w.G;
+  A.rays = rays6 ? *w.rays : nullptr;
+  A.t = t ? w.t : nullptr;
+  std::vector<float4> g((id || xyz) ? np : 0);
   hipError_t e = sail_launch_gbuffer(A, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e == hipSuccess && !g.empty()) e = hipMemcpy(g.data(), A.G, np * 16, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && rays6) e = hipMemcpy(rays6, A.rays, np * 24, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && t) e = hipMemcpy(t, A.t, np * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && !g.empty()) e = toHost(g.data(), w.G, np);
+  if (e == hipSuccess && rays6) e = toHost(rays6, w.rays, np);
+  if (e == hipSuccess && t) e = toHost(t, w.t, np);
   (void)hipFree(work);
   if (e != hipSuccess) return fail(c, SAIL_E_HIP, "sail_gbuffer: %s", hipGetErrorString(e));
   for (size_t i = 0; i < np && !g.empty(); i++) {
-    if (id) id[i] = (int32_t)g[4 * i + 3];
-    if (xyz) { xyz[3 * i] = g[4 * i]; xyz[3 * i + 1] = g[4 * i + 1]; xyz[3 * i + 2] = g[4 * i + 2]; }
+    if (id) id[i] = (int32_t)g[i].w;
+    if (xyz) { xyz[3 * i] = g[i].x; xyz[3 * i + 1] = g[i].y; xyz[3 * i + 2] = g[i].z; }
   }
   return SAIL_OK;
 }
@@ -326,7 +418,8 @@ int sail_temporal_begin(sail_ctx* c, const double mvp[16], const float eye[3], c
   }
   if (int rc = temporalState(c, "sail_temporal_begin")) return rc;
   SailGbufferArgs A;
-  if (int rc = gbufferArgs(c, "sail_temporal_begin", mvp, eye, &A)) return rc;
+  memset(&A, 0, sizeof A);
+  if (int rc = viewArgs(c, "sail_temporal_begin", mvp, eye, &A.V)) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   if (int rc = sail_sync(c)) return rc;
   if (int rc = ensureTemporal(c)) return rc;
@@ -344,13 +437,13 @@ int sail_temporal_begin(sail_ctx* c, const double mvp[16], const float eye[3], c
     c->tpHavePrev = true;
     c->tpHaveCur = false;
   }
-  const size_t nt = tiles16(c), np = (size_t)c->share.W * c->share.H;
-  uint32_t* cnt = temporalCounts(c);
+  const size_t nt = tiles16(c), np = pixels(c);
+  const TemporalWork w = temporalWork(c);
   A.G = c->tpGcur;
   SailReprojectArgs B;
   memset(&B, 0, sizeof B);
   B.Gcur = c->tpGcur; B.Gprev = c->tpGprev; B.hist = c->tpHist; B.out = c->tpR;
-  B.tileHit = cnt; B.tileHist = cnt + nt;
+  B.tileHit = w.tileHit; B.tileHist = w.tileHist;
   for (int j = 0; j < 4; j++) { B.Mp[0][j] = c->tpPrev.m[j]; B.Mp[1][j] = c->tpPrev.m[4 + j]; B.Mp[2][j] = c->tpPrev.m[12 + j]; }
   memcpy(B.eyePrev, c->tpPrev.eye, sizeof B.eyePrev);
   B.tol2 = p.pos_tol * p.pos_tol;
@@ -360,35 +453,32 @@ int sail_temporal_begin(sail_ctx* c, const double mvp[16], const float eye[3], c
   B.motion = c->tpMotionDev; B.n = c->facts.n; B.mc = c->tpMotionCap;
   c->tpResolved = false;
   // moment tracking: the same gather over Mhist, timed with the reproject pass
-  const int nev = c->tpMom ? 4 : 3;
   SailReprojectArgs M = B;
   M.hist = c->tpMhist; M.out = c->tpMR;
   M.tileHit = nullptr; M.tileHist = nullptr;
-  PooledEvents ev(c, nev);
-  if (ev.rc) return ev.rc;
-  hipError_t e = hipSuccess;
+  PassTimer T(c, c->tpMom ? 4 : 3);
+  if (T.rc()) return T.rc();
+  const auto copyMap = [&](float4* dst, const float4* src) { return hipMemcpyAsync(dst, src, np * sizeof(float4), hipMemcpyDeviceToDevice, c->stream); };
   if (moved && c->facts.n > 0)
-    e = hipMemcpyAsync(c->tpMotionDev, c->tpMotion.data(), sizeof(float4) * (size_t)c->facts.n, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipEventRecord(ev[0], c->stream);
-  if (e == hipSuccess) e = sail_launch_gbuffer(A, c->stream);
-  if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
-  if (e == hipSuccess) e = sail_launch_reproject(B, moved, c->stream);
-  if (e == hipSuccess) e = hipEventRecord(ev[2], c->stream);
+    T.run([&] { return hipMemcpyAsync(c->tpMotionDev, c->tpMotion.data(), sizeof(float4) * (size_t)c->facts.n, hipMemcpyHostToDevice, c->stream); });
+  T.mark();
+  T.run([&] { return sail_launch_gbuffer(A, c->stream); });
+  T.mark();
+  T.run([&] { return sail_launch_reproject(B, moved, c->stream); });
+  T.mark();
   if (c->tpMom) {
-    if (e == hipSuccess) e = sail_launch_moment_reproject(M, moved, c->stream);
-    if (e == hipSuccess) e = hipEventRecord(ev[3], c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->tpMout, c->tpMR, np * 16, hipMemcpyDeviceToDevice, c->stream);
+    T.run([&] { return sail_launch_moment_reproject(M, moved, c->stream); });
+    T.mark();
+    T.run([&] { return copyMap(c->tpMout, c->tpMR); });
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(c->tpOut, c->tpR, np * 16, hipMemcpyDeviceToDevice, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  T.run([&] { return copyMap(c->tpOut, c->tpR); });
   float ms[3] = {};
-  for (int i = 0; i + 1 < nev && e == hipSuccess; i++) e = hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]);
+  hipError_t e = T.finish(ms);
   ms[1] += ms[2];  // the moment reproject, when it ran
   std::vector<uint32_t> host(nt * 2);
-  if (e == hipSuccess) e = hipMemcpy(host.data(), cnt, nt * 8, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = toHost(host.data(), w.tileHit, nt * 2);  // and tileHist behind it
   if (e != hipSuccess) return fail(c, SAIL_E_HIP, "sail_temporal_begin: %s", hipGetErrorString(e));
-  for (int i = 0; i < 16; i++) c->tpCur.m[i] = (float)mvp[i];
-  memcpy(c->tpCur.eye, eye, sizeof c->tpCur.eye);
+  setView(&c->tpCur, mvp, eye);
   c->tpHaveCur = true;
   clearMotion(c);  // consumed: the next begin is today's unless the rows move again
   c->tpHitPixels = sumTiles(host, 0, nt);
@@ -417,36 +507,32 @@ int sail_temporal_resolve(sail_ctx* c, const sail_temporal_params* params, float
     return fail(c, SAIL_E_STATE, "sail_temporal_resolve: no current view (sail_temporal_begin first; a new scene drops it)");
   HIPCHK(c, hipSetDevice(c->device));
   if (int rc = sail_sync(c)) return rc;
-  const size_t nt = tiles16(c), np = (size_t)c->share.W * c->share.H;
-  uint32_t* cnt = temporalCounts(c);
+  const size_t nt = tiles16(c), np = pixels(c);
+  const TemporalWork w = temporalWork(c);
   SailResolveArgs A;
   memset(&A, 0, sizeof A);
   A.S = shownAccum(c); A.R = c->tpR; A.Out = c->tpOut;
-  A.out8 = out_rgba8 ? temporalOut8(c) : nullptr;
-  A.tileHist = cnt + nt; A.tileBad = cnt + 2 * nt;
+  A.out8 = out_rgba8 ? w.out8 : nullptr;
+  A.tileHist = w.tileHist; A.tileBad = w.tileBad;
   A.W = c->share.W; A.H = c->share.H;
   A.mix = c->accumMode == SAIL_ACCUM_MIX;
   A.kf = (float)c->k;
   A.cap = p.cap; A.display = p.display; A.gammaC = p.gamma_c;
-  PooledEvents ev(c, 2);
-  if (ev.rc) return ev.rc;
+  SailMomentResolveArgs M;  // moment tracking: blended like the colour, timed with it
+  memset(&M, 0, sizeof M);
+  M.S = A.S; M.MR = c->tpMR; M.Mout = c->tpMout;
+  M.W = c->share.W; M.H = c->share.H; M.mix = A.mix; M.kf = A.kf; M.cap = A.cap;
+  PassTimer T(c, 2);
+  if (T.rc()) return T.rc();
   float ms = 0.0f;
-  hipError_t e = hipEventRecord(ev[0], c->stream);
-  if (e == hipSuccess) e = sail_launch_temporal_resolve(A, c->stream);
-  if (c->tpMom && e == hipSuccess) {  // moment tracking: blended like the colour, timed with it
-    SailMomentResolveArgs M;
-    memset(&M, 0, sizeof M);
-    M.S = A.S; M.MR = c->tpMR; M.Mout = c->tpMout;
-    M.W = c->share.W; M.H = c->share.H; M.mix = A.mix; M.kf = A.kf; M.cap = A.cap;
-    e = sail_launch_moment_resolve(M, c->stream);
-  }
-  if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+  hipError_t e = T.one([&] {
+    const hipError_t r = sail_launch_temporal_resolve(A, c->stream);
+    return (r == hipSuccess && c->tpMom) ? sail_launch_moment_resolve(M, c->stream) : r;
+  }, &ms);
   std::vector<uint32_t> host(nt * 2);
-  if (e == hipSuccess) e = hipMemcpy(host.data(), cnt + nt, nt * 8, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && out_rgba) e = hipMemcpy(out_rgba, c->tpOut, np * 16, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && out_rgba8) e = hipMemcpy(out_rgba8, A.out8, np * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = toHost(host.data(), w.tileHist, nt * 2);  // and tileBad behind it
+  if (e == hipSuccess && out_rgba) e = toHost(out_rgba, c->tpOut, np);
+  if (e == hipSuccess && out_rgba8) e = toHost(out_rgba8, w.out8, np);
   if (e != hipSuccess) return fail(c, SAIL_E_HIP, "sail_temporal_resolve: %s", hipGetErrorString(e));
   c->tpResolved = true;
   if (info) {
@@ -471,10 +557,7 @@ int sail_temporal_read(sail_ctx* c, int which, float* out) {
     return fail(c, SAIL_E_STATE, "sail_temporal_read: map %d needs a %s view (a new scene drops both)", which,
                 prev ? "committed" : "current");
   const float4* maps[5] = {c->tpGcur, c->tpGprev, c->tpHist, c->tpR, c->tpOut};
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(out, maps[which], (size_t)c->share.W * c->share.H * 16, hipMemcpyDeviceToHost));
-  return SAIL_OK;
+  return readMap(c, maps[which], out, pixels(c));
 }
 
 int sail_temporal_load_history(sail_ctx* c, const float* hist, const float* g, const double mvp_prev[16],
@@ -484,19 +567,16 @@ int sail_temporal_load_history(sail_ctx* c, const float* hist, const float* g, c
     return fail(c, SAIL_E_INVALID, "sail_temporal_load_history: hist, g, mvp_prev and eye_prev are required");
   if (!c->subs.empty()) return relay(c, sail_temporal_load_history(c->subs[0], hist, g, mvp_prev, eye_prev), c->subs[0]);
   HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
   if (int rc = ensureTemporal(c)) return rc;
-  const size_t bytes = (size_t)c->share.W * c->share.H * 16;
-  HIPCHK(c, hipMemcpy(c->tpHist, hist, bytes, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(c->tpGprev, g, bytes, hipMemcpyHostToDevice));
-  for (int i = 0; i < 16; i++) c->tpPrev.m[i] = (float)mvp_prev[i];
-  memcpy(c->tpPrev.eye, eye_prev, sizeof c->tpPrev.eye);
+  if (int rc = loadMap(c, c->tpHist, hist, pixels(c))) return rc;
+  if (int rc = loadMap(c, c->tpGprev, g, pixels(c))) return rc;
+  setView(&c->tpPrev, mvp_prev, eye_prev);
   c->tpHavePrev = true;
   c->tpHaveCur = false;
   c->tpResolved = false;
   clearMotion(c);  // a loaded history belongs to the rows as they are now
   if (c->tpMom) {  // the loaded history carries no moments
-    HIPCHK(c, hipMemsetAsync(c->tpMhist, 0, bytes, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->tpMhist, 0, pixels(c) * sizeof(float4), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   return SAIL_OK;
@@ -527,11 +607,9 @@ int sail_temporal_moments(sail_ctx* c, int on) {
     return SAIL_OK;
   }
   if (c->tpMom) return SAIL_OK;
-  const size_t np = (size_t)c->share.W * c->share.H;
-  // three float4 maps (16 B each) per pixel, then the filter's count of temporal pixels per tile
-  if (int rc = allocOnce(c, &c->tpMom, np * 48 + tiles16(c) * 4, "moment maps")) return rc;
-  float4* base = (float4*)c->tpMom;
-  c->tpMhist = base; c->tpMR = base + np; c->tpMout = base + 2 * np;
+  if (int rc = ensureWork<MomentWork>(c, &c->tpMom, "moment maps")) return rc;
+  const MomentWork w = momentWork(c);
+  c->tpMhist = w.maps[0]; c->tpMR = w.maps[1]; c->tpMout = w.maps[2];
   HIPCHK(c, zeroMoments(c));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return SAIL_OK;
@@ -545,10 +623,7 @@ int sail_temporal_load_moments(sail_ctx* c, const float* mom) {
     return fail(c, SAIL_E_STATE, "sail_temporal_load_moments: moment tracking is off (sail_temporal_moments first)");
   if (!c->tpHavePrev || c->tpHaveCur)
     return fail(c, SAIL_E_STATE, "sail_temporal_load_moments: needs a committed history and no current view (right after sail_temporal_load_history)");
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(c->tpMhist, mom, (size_t)c->share.W * c->share.H * 16, hipMemcpyHostToDevice));
-  return SAIL_OK;
+  return loadMap(c, c->tpMhist, mom, pixels(c));
 }
 
 int sail_temporal_read_moments(sail_ctx* c, int which, float* out) {
@@ -563,10 +638,7 @@ int sail_temporal_read_moments(sail_ctx* c, int which, float* out) {
     return fail(c, SAIL_E_STATE, "sail_temporal_read_moments: map %d needs a %s view (a new scene drops both)", which,
                 prev ? "committed" : "current");
   const float4* maps[3] = {c->tpMhist, c->tpMR, c->tpMout};
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(out, maps[which], (size_t)c->share.W * c->share.H * 16, hipMemcpyDeviceToHost));
-  return SAIL_OK;
+  return readMap(c, maps[which], out, pixels(c));
 }
 
 int sail_temporal_filter_defaults(sail_tfilter_params* p) {
@@ -618,13 +690,13 @@ int tfilterCall(sail_ctx* c, const char* who, bool demod, const sail_tfilter_par
     return fail(c, SAIL_E_STATE, "%s: no sample of the current view (k = 0: the AOVs belong to another view)", who);
   if (demod && (!c->albHave || !c->albMap))
     return fail(c, SAIL_E_STATE, "%s: no albedo map (sail_albedo or sail_albedo_load first; new rows drop it)", who);
-  if (demod && memcmp(&c->albView, &c->tpCur, sizeof c->albView) != 0)
+  if (demod && !sameView(c->albView, c->tpCur))
     return fail(c, SAIL_E_STATE, "%s: the albedo map belongs to another view than the current temporal view", who);
   if (int rc = filterGuides(c, who, true)) return rc;
-  const size_t nt = tiles16(c), np = (size_t)c->share.W * c->share.H;
-  if (int rc = ensureDenoiseWork(c)) return rc;
+  const size_t nt = tiles16(c), np = pixels(c);
+  if (int rc = ensureWork<DenoiseWork>(c, &c->denoiseWork, "denoise work buffers")) return rc;
   const DenoiseWork w = denoiseWork(c);  // sail_denoise's work buffers; the count of temporal pixels sits behind the moments
-  uint32_t* dTmp = (uint32_t*)((char*)c->tpMom + np * 48);
+  uint32_t* dTmp = momentWork(c).tileTemporal;
   SailTfilterPrepareArgs A;
   memset(&A, 0, sizeof A);
   A.Out = c->tpOut; A.Mout = c->tpMout; A.S = shownAccum(c); A.N = filterN(c); A.X = filterX(c);
@@ -636,18 +708,18 @@ int tfilterCall(sail_ctx* c, const char* who, bool demod, const sail_tfilter_par
   const float sx2 = p.sigma_x * 2.0f;
   A.sx0 = sx2 * sx2;
   float ms[8] = {}, total = 0.0f;
-  int rc = SAIL_OK;
   SailTfilterPrepareDemodArgs D;
   memset(&D, 0, sizeof D);
   D.P = A; D.alb = c->albMap; D.amin = amin;
-  hipError_t e = runAtrous(c, w, [&] { return demod ? sail_launch_tfilter_prepare_demod(D, c->stream)
-                                                      : sail_launch_tfilter_prepare(A, c->stream); },
+  PassTimer T(c, p.iterations + 2);
+  if (T.rc()) return T.rc();
+  hipError_t e = runAtrous(c, T, w, [&] { return demod ? sail_launch_tfilter_prepare_demod(D, c->stream)
+                                                         : sail_launch_tfilter_prepare(A, c->stream); },
                            p.iterations, p.sigma_l, p.sigma_x, p.display, p.gamma_c, out_rgba, out_var, out_rgba8, ms, &total,
-                           &rc, demod ? c->albMap : nullptr, amin);
-  if (rc) return rc;
+                           demod ? c->albMap : nullptr, amin);
   std::vector<uint32_t> bad(nt), tmp(nt);
-  if (e == hipSuccess) e = hipMemcpy(bad.data(), w.bad, nt * 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(tmp.data(), dTmp, nt * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = toHost(bad.data(), w.bad, nt);
+  if (e == hipSuccess) e = toHost(tmp.data(), dTmp, nt);
   if (e != hipSuccess) return fail(c, SAIL_E_HIP, "%s: %s", who, hipGetErrorString(e));
   if (info) {
     memset(info, 0, sizeof *info);
@@ -662,18 +734,8 @@ int tfilterCall(sail_ctx* c, const char* who, bool demod, const sail_tfilter_par
   return SAIL_OK;
 }
 
-uint32_t* albedoCounts(const sail_ctx* c) { return (uint32_t*)(c->albMap + (size_t)c->share.W * c->share.H); }
-
-// the albedo map and its two counts per tile, allocated on first use
-int ensureAlbedo(sail_ctx* c) {
-  return allocOnce(c, &c->albMap, (size_t)c->share.W * c->share.H * 16 + tiles16(c) * 8, "albedo map");
-}
-
-void albedoView(sail_ctx* c, const double mvp[16], const float eye[3]) {
-  memset(&c->albView, 0, sizeof c->albView);
-  for (int i = 0; i < 16; i++) c->albView.m[i] = (float)mvp[i];
-  memcpy(c->albView.eye, eye, sizeof c->albView.eye);
-}
+int ensureAlbedo(sail_ctx* c) { return ensureWork<AlbedoWork>(c, &c->albMap, "albedo map"); }
+int ensureGuides(sail_ctx* c) { return ensureWork<GuideWork>(c, &c->guideMaps, "guide maps"); }
 
 }  // namespace
 
@@ -696,35 +758,29 @@ int sail_albedo(sail_ctx* c, const double mvp[16], const float eye[3], int grid,
   if (!mvp || !eye) return fail(c, SAIL_E_INVALID, "sail_albedo: mvp and eye are required");
   if (!c->subs.empty()) return relay(c, sail_albedo(c->subs[0], mvp, eye, grid, out_rgba, info), c->subs[0]);
   if (!c->haveScene) return fail(c, SAIL_E_STATE, "sail_albedo: no scene (call sail_set_scene first)");
-  SailGbufferArgs G;
-  if (int rc = gbufferArgs(c, "sail_albedo", mvp, eye, &G)) return rc;
+  SailAlbedoArgs A;
+  memset(&A, 0, sizeof A);
+  if (int rc = viewArgs(c, "sail_albedo", mvp, eye, &A.V)) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   if (int rc = sail_sync(c)) return rc;
   if (int rc = ensureAlbedo(c)) return rc;
-  const size_t nt = tiles16(c), np = (size_t)c->share.W * c->share.H;
-  SailAlbedoArgs A;
-  memset(&A, 0, sizeof A);
-  A.prims = c->prims; A.texparams = c->tp; A.n = c->facts.n; A.tn = c->facts.tn;
+  const size_t nt = tiles16(c);
+  const AlbedoWork w = albedoWork(c);
+  A.texparams = c->tp; A.tn = c->facts.tn;
   A.texMask = c->facts.plugins.texture_mask;
-  memcpy(A.d, G.d, sizeof A.d);
-  memcpy(A.eye, eye, sizeof A.eye);
-  A.W = c->share.W; A.H = c->share.H; A.grid = grid;
-  A.A = c->albMap;
-  A.tileHit = albedoCounts(c); A.tilePartial = A.tileHit + nt;
+  A.grid = grid;
+  A.A = w.map;
+  A.tileHit = w.tileHit; A.tilePartial = w.tilePartial;
   c->albHave = false;  // a call that fails leaves no map
-  PooledEvents ev(c, 2);
-  if (ev.rc) return ev.rc;
+  PassTimer T(c, 2);
+  if (T.rc()) return T.rc();
   float ms = 0.0f;
-  hipError_t e = hipEventRecord(ev[0], c->stream);
-  if (e == hipSuccess) e = sail_launch_albedo(A, c->stream);
-  if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+  hipError_t e = T.one([&] { return sail_launch_albedo(A, c->stream); }, &ms);
   std::vector<uint32_t> host(nt * 2);
-  if (e == hipSuccess) e = hipMemcpy(host.data(), A.tileHit, nt * 8, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && out_rgba) e = hipMemcpy(out_rgba, c->albMap, np * 16, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = toHost(host.data(), w.tileHit, nt * 2);  // and tilePartial behind it
+  if (e == hipSuccess && out_rgba) e = toHost(out_rgba, w.map, pixels(c));
   if (e != hipSuccess) return fail(c, SAIL_E_HIP, "sail_albedo: %s", hipGetErrorString(e));
-  albedoView(c, mvp, eye);
+  setView(&c->albView, mvp, eye);
   c->albHave = true;
   if (info) {
     memset(info, 0, sizeof *info);
@@ -741,10 +797,9 @@ int sail_albedo_load(sail_ctx* c, const float* map, const double mvp[16], const 
   if (!map || !mvp || !eye) return fail(c, SAIL_E_INVALID, "sail_albedo_load: map, mvp and eye are required");
   if (!c->subs.empty()) return relay(c, sail_albedo_load(c->subs[0], map, mvp, eye), c->subs[0]);
   HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
   if (int rc = ensureAlbedo(c)) return rc;
-  HIPCHK(c, hipMemcpy(c->albMap, map, (size_t)c->share.W * c->share.H * 16, hipMemcpyHostToDevice));
-  albedoView(c, mvp, eye);
+  if (int rc = loadMap(c, c->albMap, map, pixels(c))) return rc;
+  setView(&c->albView, mvp, eye);
   c->albHave = true;
   return SAIL_OK;
 }
@@ -755,32 +810,8 @@ int sail_albedo_read(sail_ctx* c, float* out) {
   if (!c->subs.empty()) return relay(c, sail_albedo_read(c->subs[0], out), c->subs[0]);
   if (!c->albHave || !c->albMap)
     return fail(c, SAIL_E_STATE, "sail_albedo_read: no albedo map (sail_albedo or sail_albedo_load first; new rows drop it)");
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(out, c->albMap, (size_t)c->share.W * c->share.H * 16, hipMemcpyDeviceToHost));
-  return SAIL_OK;
+  return readMap(c, c->albMap, out, pixels(c));
 }
-
-}  // extern "C"
-
-namespace {
-
-uint32_t* guideCounts(const sail_ctx* c) { return (uint32_t*)(c->guideMaps + (size_t)c->share.W * c->share.H * 2); }
-
-// the two guide maps and their three counts per tile, allocated on first use
-int ensureGuides(sail_ctx* c) {
-  return allocOnce(c, &c->guideMaps, (size_t)c->share.W * c->share.H * 32 + tiles16(c) * 12, "guide maps");
-}
-
-void guidesView(sail_ctx* c, const double mvp[16], const float eye[3]) {
-  memset(&c->guideView, 0, sizeof c->guideView);
-  for (int i = 0; i < 16; i++) c->guideView.m[i] = (float)mvp[i];
-  memcpy(c->guideView.eye, eye, sizeof c->guideView.eye);
-}
-
-}  // namespace
-
-extern "C" {
 
 // ---- the guide maps of a view (include/sail_hip.h; the kernel is sail_guides.hip) ----------------------------------------------
 int sail_guides(sail_ctx* c, const double mvp[16], const float eye[3], int depth, float* out_n, float* out_x,
@@ -790,38 +821,32 @@ int sail_guides(sail_ctx* c, const double mvp[16], const float eye[3], int depth
   if (!mvp || !eye) return fail(c, SAIL_E_INVALID, "sail_guides: mvp and eye are required");
   if (!c->subs.empty()) return relay(c, sail_guides(c->subs[0], mvp, eye, depth, out_n, out_x, info), c->subs[0]);
   if (!c->haveScene) return fail(c, SAIL_E_STATE, "sail_guides: no scene (call sail_set_scene first)");
-  SailGbufferArgs G;
-  if (int rc = gbufferArgs(c, "sail_guides", mvp, eye, &G)) return rc;
+  SailGuidesArgs A;
+  memset(&A, 0, sizeof A);
+  if (int rc = viewArgs(c, "sail_guides", mvp, eye, &A.V)) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   if (int rc = sail_sync(c)) return rc;
   if (int rc = ensureGuides(c)) return rc;
-  const size_t nt = tiles16(c), np = (size_t)c->share.W * c->share.H;
-  SailGuidesArgs A;
-  memset(&A, 0, sizeof A);
-  A.prims = c->prims; A.texparams = c->tp; A.n = c->facts.n; A.tn = c->facts.tn;
+  const size_t nt = tiles16(c), np = pixels(c);
+  const GuideWork w = guideWork(c);
+  A.texparams = c->tp; A.tn = c->facts.tn;
   A.matMask = c->facts.plugins.material_mask; A.texMask = c->facts.plugins.texture_mask;
-  memcpy(A.d, G.d, sizeof A.d);
-  memcpy(A.eye, eye, sizeof A.eye);
-  A.W = c->share.W; A.H = c->share.H; A.depth = depth;
-  A.Ng = c->guideMaps; A.Xg = c->guideMaps + np;
-  A.tileHit = guideCounts(c); A.tileFollowed = A.tileHit + nt; A.tileTruncated = A.tileHit + 2 * nt;
+  A.depth = depth;
+  A.Ng = w.n; A.Xg = w.x;
+  A.tileHit = w.tileHit; A.tileFollowed = w.tileFollowed; A.tileTruncated = w.tileTruncated;
   c->guideHave = false;  // a call that fails leaves no maps
-  PooledEvents ev(c, 2);
-  if (ev.rc) return ev.rc;
+  PassTimer T(c, 2);
+  if (T.rc()) return T.rc();
   float ms = 0.0f;
-  hipError_t e = hipEventRecord(ev[0], c->stream);
-  if (e == hipSuccess) e = sail_launch_guides(A, c->stream);
-  if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+  hipError_t e = T.one([&] { return sail_launch_guides(A, c->stream); }, &ms);
   std::vector<uint32_t> host(nt * 3);
-  if (e == hipSuccess) e = hipMemcpy(host.data(), A.tileHit, nt * 12, hipMemcpyDeviceToHost);
-  std::vector<float> ng((info && !out_n) ? np * 4 : 0);  // max_depth is read off Ng.w
-  float* hn = out_n ? out_n : (ng.empty() ? nullptr : ng.data());
-  if (e == hipSuccess && hn) e = hipMemcpy(hn, A.Ng, np * 16, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && out_x) e = hipMemcpy(out_x, A.Xg, np * 16, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = toHost(host.data(), w.tileHit, nt * 3);  // tileFollowed and tileTruncated behind it
+  std::vector<float4> ng((info && !out_n) ? np : 0);  // max_depth is read off Ng.w
+  float* hn = out_n ? out_n : (ng.empty() ? nullptr : &ng[0].x);
+  if (e == hipSuccess && hn) e = toHost(hn, w.n, np);
+  if (e == hipSuccess && out_x) e = toHost(out_x, w.x, np);
   if (e != hipSuccess) return fail(c, SAIL_E_HIP, "sail_guides: %s", hipGetErrorString(e));
-  guidesView(c, mvp, eye);
+  setView(&c->guideView, mvp, eye);
   c->guideHave = true;
   if (info) {
     memset(info, 0, sizeof *info);
@@ -840,13 +865,12 @@ int sail_guides_load(sail_ctx* c, const float* n_map, const float* x_map, const 
   if (!n_map || !x_map || !mvp || !eye) return fail(c, SAIL_E_INVALID, "sail_guides_load: n_map, x_map, mvp and eye are required");
   if (!c->subs.empty()) return relay(c, sail_guides_load(c->subs[0], n_map, x_map, mvp, eye), c->subs[0]);
   HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
   if (int rc = ensureGuides(c)) return rc;
-  const size_t np = (size_t)c->share.W * c->share.H;
+  const GuideWork w = guideWork(c);
   c->guideHave = false;
-  HIPCHK(c, hipMemcpy(c->guideMaps, n_map, np * 16, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(c->guideMaps + np, x_map, np * 16, hipMemcpyHostToDevice));
-  guidesView(c, mvp, eye);
+  if (int rc = loadMap(c, w.n, n_map, pixels(c))) return rc;
+  if (int rc = loadMap(c, w.x, x_map, pixels(c))) return rc;
+  setView(&c->guideView, mvp, eye);
   c->guideHave = true;
   return SAIL_OK;
 }
@@ -858,11 +882,8 @@ int sail_guides_read(sail_ctx* c, int which, float* out) {
   if (!c->subs.empty()) return relay(c, sail_guides_read(c->subs[0], which, out), c->subs[0]);
   if (!c->guideHave || !c->guideMaps)
     return fail(c, SAIL_E_STATE, "sail_guides_read: no guide maps (sail_guides or sail_guides_load first; new rows drop them)");
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const size_t np = (size_t)c->share.W * c->share.H;
-  HIPCHK(c, hipMemcpy(out, c->guideMaps + (which == SAIL_GUIDE_X ? np : 0), np * 16, hipMemcpyDeviceToHost));
-  return SAIL_OK;
+  const GuideWork w = guideWork(c);
+  return readMap(c, which == SAIL_GUIDE_X ? w.x : w.n, out, pixels(c));
 }
 
 int sail_use_guides(sail_ctx* c, int on) {

@@ -5,13 +5,19 @@
 
 struct SailPrim;
 
-struct SailGbufferArgs {
+// A view of the scene as the passes that shoot a ray per pixel take it (sail_view.h): a member of the G-buffer, albedo
+// and guide kernels' arguments, filled by the host's viewArgs
+struct SailViewArgs {
   const SailPrim* prims;  // the scene's rows, swept in order
   int n;
   float d[4][3];          // corner directions of the zero-jitter inverse (the host's cornerDirs)
   float eye[3];
   int W, H;
-  float4* G;              // out: (X.xyz, (float)id); a miss stores (0, 0, 0, -1)
+};
+
+struct SailGbufferArgs {
+  SailViewArgs V;
+  float4* G;          // out: (X.xyz, (float)id); a miss stores (0, 0, 0, -1)
   float* rays;            // out, may be NULL: 6 floats per pixel, origin then direction
   float* t;               // out, may be NULL: the hit distance, 1e5 on a miss
 };

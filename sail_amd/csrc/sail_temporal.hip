@@ -13,9 +13,7 @@
 // MI355X design ("sail_gbuffer_kernel, sail_reproject_kernel, sail_temporal_resolve_kernel"):
 //  * all four: one 256-thread workgroup per 16x16 tile, one lane per pixel, each wave a 16x4 strip (the filter and
 //    noise kernels' shape): float4 loads and stores in 256-byte runs per row;
-//  * G-buffer: the pixel's ray is the trace kernels' for a sample of zero jitter (same corner interpolation, mkRay),
-//    the sweep is sail_pick_kernel's: primT over all rows in order, a hit on a strict `<`; the row index is
-//    wave-uniform, so the rows arrive through the scalar cache (constRow). One float4 store per pixel;
+//  * G-buffer: the pixel-centre ray and the first-hit sweep of the view passes (sail_view.h). One float4 store per pixel;
 //  * reproject: the tap of sp::gather reads Hist and accepts a texel with a count and a finite colour; up to four float4
 //    pairs (G_prev, Hist) per pixel, 16-byte loads, straight from L2 / HBM: neighbouring pixels of the new view land on
 //    neighbouring texels of the old one, so a wave's taps share cache lines. No LDS staging;
@@ -26,44 +24,31 @@
 //  * the counts are wave ballots, one barrier each (sp::tileCounts), summed per tile on the host;
 //  * lanes outside ragged tiles load nothing and store nothing;
 //  * plain vector stores only, no atomics: equal data give equal bits.
-// mkRay, primT and constRow are sail_geom.h's. No part of a run-time kernel's text (sail_amd/gen_jit_src.py). Built
+// mkRay is sail_geom.h's. No part of a run-time kernel's text (sail_amd/gen_jit_src.py). Built
 // with the library's flags (no contraction, no fast math: `/` is the IEEE divide).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "sail_geom.h"
+#include "sail_view.h"
 #include "sail_post.h"
 
 extern "C" __global__ void __launch_bounds__(256) sail_gbuffer_kernel(SailGbufferArgs A) {
+  const SailViewArgs& V = A.V;
   const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
-  if (x >= A.W || y >= A.H) return;
-  // the trace kernels' primary ray for a sample without jitter (sail_trace_kernel)
-  const float s = ((float)x + 0.5f) / (float)A.W, t = ((float)y + 0.5f) / (float)A.H;
-  const bool tri0 = s + t <= 1.0f;
-  const V3 eye = v3(A.eye[0], A.eye[1], A.eye[2]);
-  const V3 d0 = v3(A.d[0][0], A.d[0][1], A.d[0][2]), d1 = v3(A.d[1][0], A.d[1][1], A.d[1][2]);
-  const V3 d2 = v3(A.d[2][0], A.d[2][1], A.d[2][2]), d3 = v3(A.d[3][0], A.d[3][1], A.d[3][2]);
-  const Ray r = mkRay(eye, tri0 ? (d0 + (d2 - d0) * s + (d1 - d0) * t) : (d3 + (d1 - d3) * (1.0f - s) + (d2 - d3) * (1.0f - t)));
-  // sail_pick_kernel's sweep: every row in order, the first row with the smallest distance
-  Ctx c;
-  c.kShapes = ~0u;
-  float best = kMaxDistance;
-  int bi = -1;
-  for (int k = 0; k < A.n; k++) {
-    const float tk = primT(c, constRow<SailPrim>(A.prims, k), r, nullptr);
-    if (tk < best) { best = tk; bi = k; }
-  }
-  const size_t pix = (size_t)y * A.W + x;
+  if (x >= V.W || y >= V.H) return;
+  const Ray r = mkRay(sv::eye(V), sv::pixelDir(V, ((float)x + 0.5f) / (float)V.W, ((float)y + 0.5f) / (float)V.H));
+  const Sweep sw = sv::firstHit(sv::flatCtx(V.prims, V.n, nullptr, 0, 0u, 0u, 0u), V.prims, V.n, r);
+  const size_t pix = (size_t)y * V.W + x;
   float4 g = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
-  if (bi >= 0) {
-    const V3 X = r.o + r.d * best;  // a product and a sum per component, no fma
-    g = make_float4(X.x, X.y, X.z, (float)bi);
+  if (sw.bi >= 0) {
+    const V3 X = r.o + r.d * sw.best;  // a product and a sum per component, no fma
+    g = make_float4(X.x, X.y, X.z, (float)sw.bi);
   }
   A.G[pix] = g;
   if (A.rays) {
     float* q = A.rays + 6 * pix;
     q[0] = r.o.x; q[1] = r.o.y; q[2] = r.o.z; q[3] = r.d.x; q[4] = r.d.y; q[5] = r.d.z;
   }
-  if (A.t) A.t[pix] = best;
+  if (A.t) A.t[pix] = sw.best;
 }
 
 // The reproject pass over the colour history: sp::gather's taps that hold a count and a finite colour. MOVED = false is
@@ -135,7 +120,7 @@ extern "C" __global__ void __launch_bounds__(256) sail_temporal_resolve_kernel(S
 }
 
 hipError_t sail_launch_gbuffer(const SailGbufferArgs& A, hipStream_t s) {
-  hipLaunchKernelGGL(sail_gbuffer_kernel, dim3((A.W + 15) / 16, (A.H + 15) / 16), dim3(256), 0, s, A);
+  hipLaunchKernelGGL(sail_gbuffer_kernel, dim3((A.V.W + 15) / 16, (A.V.H + 15) / 16), dim3(256), 0, s, A);
   return hipGetLastError();
 }
 

@@ -126,6 +126,28 @@ def test_depth_0_equals_the_trace_kernels_aovs(gpu, fixtures, name, W, H):
         ctx.close()
 
 
+@pytest.mark.parametrize("W,H", [(1, 1), (33, 17)])
+@pytest.mark.parametrize("name", ["C1", "ALL"])
+def test_view_passes_agree(gpu, fixtures, name, W, H):
+    """The four passes that sweep for a first hit (sail_view.h) show the same row in every pixel, hit or miss: the
+    G-buffer's id is the guide maps' at depth 0, the albedo map's hits with one centred sub-ray and the picker's answer to
+    the G-buffer's rays. Integers: no tolerance. The CPU oracle's three references agree in the same way on these inputs."""
+    sc = fixtures["scenes"][name]
+    ctx = capi.Context(W, H)
+    try:
+        ctx.set_scene_dict(sc)
+        missed = 0
+        for mvp, eye in (scene_view(sc), tr.orbit(25)):
+            g = ctx.gbuffer(mvp, eye, rays=True)
+            assert np.array_equal(ctx.guides(mvp, eye, depth=0)["x"][..., 3], g["id"].astype(F))
+            assert np.array_equal(ctx.albedo(mvp, eye, grid=1)["rgba"][..., 3] > 0, g["id"] >= 0)
+            assert np.array_equal(ctx.pick(g["rays"].reshape(-1, 6))[0], g["id"].reshape(-1))
+            missed += int((g["id"] < 0).sum())
+        assert (W, H) == (1, 1) or 0 < missed < 2 * W * H  # the orbit view leaves some pixels without a hit
+    finally:
+        ctx.close()
+
+
 # ---- 2. the four filters with the switch on ------------------------------------------------------------------------------------
 def one_frame(ctx, view, B=3, mark=3, spp=8):
     """a temporal view begun, `mark` samples, the mark, the rest up to `spp`, resolved; returns the mark's accumulator"""
