@@ -96,7 +96,11 @@ int sail_set_scene(sail_ctx* ctx, const float* objects, int n, const float* texp
 /* Tracer.updateObjects(scene) (src/core/tracer.js:25-40): new object rows, same n; resets accumulation */
 int sail_update_objects(sail_ctx* ctx, const float* objects, int n);
 
-int sail_set_accum_mode(sail_ctx* ctx, int mode);        /* resets accumulation */
+/* Both restart the accumulation (see sail_reset), also when they set what is already set. A running mean cannot be split by
+ * samples: SAIL_ACCUM_MIX or SAIL_ACCUM_COMPAT8 under a sample partition over more than one rank (the devices of a
+ * multi-device context are its ranks), and such a partition under those modes, are refused with SAIL_E_INVALID and nothing
+ * changes. A multi-device context takes sail_set_partition(ctx, 0, 1, mode) only. */
+int sail_set_accum_mode(sail_ctx* ctx, int mode);
 int sail_set_partition(sail_ctx* ctx, int rank, int world, int mode);
 int sail_set_launch_samples(sail_ctx* ctx, int spp_per_launch); /* samples per kernel launch; 0 (default) = by kernel form: 1024 for the Cornell form with 16 samples in flight, else 64 */
 /* Test / study switches (no reference counterpart; none changes a result, which the parity suite checks).
@@ -157,12 +161,26 @@ int sail_set_debug(sail_ctx* ctx, int option, int value);
  * nothing observes the frame in between: every entry point that reads, filters, reduces, counts or changes the
  * context launches the queue first, and a change of eye or bounce count launches it before the new sample is
  * queued. The frame is bit-identical to one launch per call (samples are accumulated in the same order); a
- * launch error of a queued sample is reported by the call that launches it. */
+ * launch error of a queued sample is reported by the call that launches it. A sample's record (its corner directions, seed,
+ * running-mean weight and sample index) is taken when the call is made, and sail_stats.samples and the sample index of
+ * sail_save_accum count it from then on; the tile mask and the kernel are those of the launch.
+ * The calls that restart the accumulation (sail_reset) and sail_load_accum do not launch the queue, they drop it: its
+ * samples belong to the accumulation that goes. A refused call may leave the queue as it is. Calls that only read host state
+ * launch nothing: sail_get_active_tiles, sail_kernel_name, sail_get_kernel_info, sail_kernel_ready, sail_accum_parts.
+ * On a multi-device context every device has its own queue. The calls that show the reduced frame (sail_readback,
+ * sail_read_accum, sail_filter, sail_reduce, the noise, denoise and temporal calls) and the calls that fan out (sail_sync,
+ * sail_get_stats, the setters, sail_render_schedule) launch every device's; a call that works on one device's sub-context
+ * launches that device's only (sail_pick, sail_gbuffer, sail_albedo and sail_guides on device 0, sail_save_accum on its
+ * part), which no result shows: the frame is reduced from all of them before it is read. */
 int sail_render(sail_ctx* ctx, const float inv_mvp[16], const float eye[3], float time_seed, int max_bounces);
 /* spp samples in one call: inv_mvp = spp x 16 floats, seeds = spp floats (a deterministic schedule). */
 int sail_render_schedule(sail_ctx* ctx, const float* inv_mvp, const float* seeds, const float eye[3],
                          int spp, int max_bounces);
-/* Renderer.render with scene.moving: sampleCount = 0 (src/core/renderer.js:57-60) */
+/* Renderer.render with scene.moving: sampleCount = 0 (src/core/renderer.js:57-60). A restart of the accumulation, as are
+ * sail_set_scene, sail_update_objects, sail_move_objects, sail_set_accum_mode and sail_set_partition: the accumulator is
+ * zeroed, the sample index and sail_stats return to 0, queued samples are dropped, the tile mask and the noise mark go. The
+ * AOV maps restart at +0, and at -0 outside the tiles of a rank of a tile partition over several ranks (the identity of
+ * the reduce's sum). */
 int sail_reset(sail_ctx* ctx);
 int sail_sync(sail_ctx* ctx);
 
@@ -194,7 +212,10 @@ int sail_get_stats(sail_ctx* ctx, sail_stats* out);
  * frame, whose mean has twice the samples. A non-finite e (a NaN or Inf in the accumulator) counts in `nonfinite` and
  * adds nothing to any sum: one bad pixel does not keep a frame from converging. One pass over S and P on the device
  * (sail_noise_kernel: a sum per 16x16 tile, no atomics, so equal data give equal bits); the host adds the tiles in double.
- * sail_reset, sail_set_scene, sail_update_objects, sail_set_accum_mode and sail_set_partition drop the mark;
+ * A tile's sum is an f32 tree, fixed: the tile's rows 4 w .. 4 w + 3 are strip w, its 64 errors v[0..63] in row-major order
+ * (+0 outside the frame); for off = 32, 16, 8, 4, 2, 1: v[i] = v[i] + v[i + off] for i < off; the tile is
+ * (strip0 + strip1) + (strip2 + strip3). tile_err is that sum divided in double by the tile's in-frame pixels, as f32.
+ * sail_reset, sail_set_scene, sail_update_objects, sail_move_objects, sail_set_accum_mode and sail_set_partition drop the mark;
  * sail_load_accum keeps it (a loaded checkpoint continues a render). SAIL_ACCUM_COMPAT8 is refused (SAIL_E_STATE): its
  * 8-bit store makes the halves' difference meaningless. On a multi-device context both calls reduce first and work on
  * device 0's frame, like sail_filter. */
@@ -239,7 +260,7 @@ int sail_render_until(sail_ctx* ctx, const double mvp_rowmajor[16], const float 
  *   everything that restarts the accumulator removes the mask: sail_reset, sail_set_scene, sail_update_objects,
  *     sail_move_objects, sail_set_accum_mode, sail_set_partition, sail_load_accum (a host resuming a checkpoint sets it
  *     again: checkpoints do not hold it).
- *   refused, nothing changed: SAIL_E_STATE in SAIL_ACCUM_MIX and SAIL_ACCUM_COMPAT8 (no per-pixel count) and on a
+ *   refused, nothing changed, (NULL, 0) too: SAIL_E_STATE in SAIL_ACCUM_MIX and SAIL_ACCUM_COMPAT8 (no per-pixel count) and on a
  *     half-loaded checkpoint; SAIL_E_INVALID for a count that is not the number of tiles (or active == NULL with count != 0).
  *     On a multi-device context a device that fails while the mask is set (memory, a HIP error) gives the devices
  *     before it their previous mask back: the devices never trace under different masks.
@@ -718,7 +739,10 @@ int sail_use_guides(sail_ctx* ctx, int on);
  * A context's accumulation is `parts` raw accumulators (1 for sail_create, one per device for sail_create_multi),
  * each W*H*4 f32 in sail_read_accum's layout, plus the global sample index k of the next sample. Saving every part
  * and loading them into a fresh context with the same size, scene, partition and accumulation mode continues the
- * render bit for bit: render k -> save -> new context -> load -> render k more == the 2k-sample frame. */
+ * render bit for bit: render k -> save -> new context -> load -> render k more == the 2k-sample frame.
+ * sail_save_accum launches the part's queued samples first, so the sums hold every sample below the k it returns.
+ * sail_load_accum drops queued samples and the tile mask and keeps the noise mark (a new context has none);
+ * sail_stats.samples becomes sail_plan_reduce's `samples` for the loaded k and the context's partition. */
 int sail_accum_parts(sail_ctx* ctx, int* parts);
 /* copy accumulator `part` (this rank's own, never the reduced frame) and the sample index k */
 int sail_save_accum(sail_ctx* ctx, int part, float* sums, uint64_t* k);

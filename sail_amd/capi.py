@@ -1072,6 +1072,14 @@ class Context:
         self._check(self.lib.sail_temporal_load_history(self.h, _ptr(h), _ptr(gg), _ptr(m, ctypes.c_double), _ptr(e)),
                     "sail_temporal_load_history")
 
+    def update_objects(self, objects):
+        """New object rows, the same number as the scene's (sail_update_objects): the accumulation restarts and the
+        temporal state goes."""
+        o = _f32(objects)
+        if o.size % 18:
+            raise SailError("update_objects: object rows have 18 floats each")
+        self._check(self.lib.sail_update_objects(self.h, _ptr(o), o.size // 18), "sail_update_objects")
+
     def move_objects(self, objects, motion=None, hist_cap: float = 0.0):
         """New object rows that keep the temporal state (sail_move_objects). `motion` is (n, 3) f32, each row's
         translation since the rows the context holds now (None: no row moved); `hist_cap` 0 for none, else the count a
